@@ -14,10 +14,17 @@ its block of views, the packed maps are all-gathered (chunk by chunk, overlapped
 every rank votes its slab of the Gaussians, the labels are all-gathered (protocol v4).  --weak-views V gives every rank V
 views instead.
 
-Side numbers at N=1 (never `value`): the same run with the int32 maps already resident in HBM (`resident_value`), and
-the vote kernel alone over maps already packed in HBM (`kernel_resident_value`, round 1's headline).
+A plain run sets up, warms up, times the --steps steps and prints the result line (with the per-kernel HIP-event times of the
+timed steps).  Everything else runs only with --full: at N=1 the same run with the int32 maps already resident in HBM
+(`resident_value`), the vote kernel alone over maps already packed in HBM (`kernel_resident_value`, round 1's headline),
+the host hand-over alone, uint8 class images, the CPU baseline, the rasterizer leg and the roofline; at N>1 where a step's
+time goes (`phases_ms`) and the exchanged labels against a single-GPU vote.  None of them is ever `value`.
+
+--dump-outputs DIR writes the labels of the last timed step to DIR/labels.npy (float32); the inputs are seeded, so two
+builds run with the same arguments can be compared label for label.
 
   python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -37,6 +44,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak
+DUMP_MAX_LABELS = 16 << 20   # --dump-outputs: at most 64 MB of float32
 
 
 def parse():
@@ -66,6 +74,10 @@ def parse():
     ap.add_argument("--opt", action="append", default=[], help="library tuning option name=value (gsx_set_option)")
     ap.add_argument("--side-steps", type=int, default=3, help="steps of each side measurement at N=1 (0 = skip)")
     ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event kernel timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement beside the headline: side legs, CPU baseline, rasterizer leg, roofline, N>1 phases")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the labels of the last timed step to DIR/labels.npy (float32; a seeded sample of %d if more)" % DUMP_MAX_LABELS)
     ap.add_argument("--no-numa-bind", action="store_true",
                     help="do not bind this process to the CPUs of its GPU's NUMA node (one process per GPU: maps, pinned staging and "
                          "packer threads next to the GPU's PCIe root)")
@@ -151,6 +163,14 @@ def render_leg(pkg, ctx, args, W, H):
                                "unit": "GB/s", "frac": None if achieved is None else round(achieved / HBM_PEAK_GBS, 5),
                                "algorithmic_bytes": int(alg),
                                "note": "blend is fp32-VALU bound at 16x16 tiles (counters: profiles/r03/derived_r03d.json: traffic = 1.5 x these bytes); see DESIGN.md"}}
+
+
+def dump_outputs(d, labels):
+    """The labels as float32 (exact: -1 .. classes-1); past DUMP_MAX_LABELS Gaussians a fixed seeded sample of them, in index order."""
+    if labels.size > DUMP_MAX_LABELS:
+        labels = labels[np.sort(np.random.default_rng(0).choice(labels.size, DUMP_MAX_LABELS, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "labels.npy"), labels.astype(np.float32))
 
 
 def cpu_model():
@@ -283,10 +303,12 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = n * total_views / (elapsed / args.steps)
     labels_main = labels_buf.copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, labels_main)
     # ---- N > 1: where a step's time goes.  Extra steps OUTSIDE the timed region (the events' host waits would perturb it):
     # per phase the median over the steps, then the MAX over the ranks; per-rank hand-over rate of the int32 maps. ------------
     phases = None
-    if mode == "pipelined":
+    if mode == "pipelined" and args.full:
         rows, walls = [], []
         for _ in range(max(3, min(args.steps, 7))):
             fence()
@@ -315,7 +337,7 @@ def main():
             phases["host_ingest_GBps_of_int32_maps_per_rank"] = [round(float(a.item()), 2) for a in alls]
 
     labels_check = None
-    if mode in ("gather", "pipelined"):
+    if mode in ("gather", "pipelined") and args.full:
         # after the import every rank holds every view: a plain single-GPU vote of ALL Gaussians on this rank must give
         # the labels the exchange assembled from the ranks' slabs (rank-local, no collective)
         labels_check = bool(np.array_equal(ctx.vote_finalize(), labels_main))
@@ -328,7 +350,7 @@ def main():
     roofline = None
     kernels_ms = None
     vis_frac = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # visible fraction of the (Gaussian, view) pairs, from the device projection kernel itself
         probe = list(range(0, total_views, max(1, total_views // 10)))
         vis = [float((ctx.project_all(cams_all[v])[0] >= 0).mean()) for v in probe]
@@ -396,7 +418,7 @@ def main():
                     "kernel_ms": round(k_ms, 4), "launches": launches, "algorithmic_bytes": int(alg),
                     "second_bound": cached.get("valu_f64")}
 
-        if early_views and mode is None:
+        if args.full and early_views and mode is None:
             # the run's vote is two kernels: the early stage (second stream, hidden behind the hand-over) and the last stage
             # (between the last map and the labels).  The dominant one by GPU time carries the roofline, the other rides along.
             cand = [r for r in (roofline_of("vote_early_planes"), roofline_of("vote_fused_final"), roofline_of("vote_early_record"),
@@ -411,7 +433,7 @@ def main():
                                     "early_replay=0: vote_early_planes) + a last stage over the remaining views (vote_fused_replay replays the "
                                     "record behind its own walk; vote_fused_final folds the planes in); all walk views with the filtered fp64 "
                                     "projection of the one-piece kernel, which is latency-, not bandwidth-bound (DESIGN.md sections 4, 8)")
-        else:
+        elif args.full:
             roofline = roofline_of(kname)
             if roofline:
                 roofline["note"] = ("fp64-VALU bound kernel: the HBM fraction is reported as the contract asks, the binding "
@@ -421,7 +443,7 @@ def main():
 
     # ---- side measurements at N=1: int32 maps resident in HBM; packed maps resident (kernel only) ------------------------
     side = {}
-    if not multi and rank == 0 and args.side_steps > 0:
+    if args.full and not multi and rank == 0 and args.side_steps > 0:
         S = args.side_steps
         dev_maps = torch.from_numpy(np.stack(host_segs)).cuda()          # (V, H, W) int32 in HBM
         torch.cuda.synchronize()
@@ -504,7 +526,7 @@ def main():
 
     # ---- CPU baseline: the oracle (C port of the reference loop) on bounded samples of the same workload ----------------
     cpu = None
-    if rank == 0 and not multi and args.cpu_sample > 0:
+    if args.full and rank == 0 and not multi and args.cpu_sample > 0:
         import oracle
         sizes = [(W, H)] * V
         cams_cpu = cams_all[:V]
@@ -544,7 +566,7 @@ def main():
 
     # ---- rasterizer leg (reported beside the headline metric, never part of `value`) ---------------------
     render = None
-    if rank == 0 and not multi and args.render_views > 0:
+    if args.full and rank == 0 and not multi and args.render_views > 0:
         render = render_leg(pkg, ctx, args, W, H)
 
     if rank == 0:

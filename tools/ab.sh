@@ -15,7 +15,7 @@ for o in "$@"; do
   # leading NAME=VALUE words of an argument set are environment for that run only (GSX_HOST_AFFINITY=node, GSX_LIBRARY=..)
   envs=(); args=()
   for w in $o; do if [[ ${#args[@]} -eq 0 && $w =~ ^[A-Z_][A-Z0-9_]*=.*$ ]]; then envs+=("$w"); else args+=("$w"); fi; done
-  env "${envs[@]}" timeout -k 10 400 python bench.py --steps ${AB_STEPS:-10} --warmup ${AB_WARMUP:-3} --cpu-sample 0 --render-views 0 "${args[@]}" > $OUT/run_$i.json 2>>$OUT/err.log || { tail -5 $OUT/err.log; exit 1; }
+  env "${envs[@]}" timeout -k 10 400 python bench.py --steps ${AB_STEPS:-10} --warmup ${AB_WARMUP:-3} --cpu-sample 0 --render-views 0 --full "${args[@]}" > $OUT/run_$i.json 2>>$OUT/err.log || { tail -5 $OUT/err.log; exit 1; }
   python - "$o" $OUT/run_$i.json <<'PY' | tee -a $OUT/ab.txt
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --cpu-sample 0 --side-steps 2 --no-profile --render-views 4 $*"
+ARGS="--steps 3 --warmup 1 --cpu-sample 0 --side-steps 2 --no-profile --render-views 4 --full $*"
 echo "python3 bench.py $ARGS" > $OUT/command.txt
 pass() {  # name, rocprofv3 options...
   local name=$1; shift
