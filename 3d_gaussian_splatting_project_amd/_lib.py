@@ -40,6 +40,19 @@ class Camera(C.Structure):
         return c
 
 
+EDIT_TABLE_MAX = 100
+NO_SELECTION = -999999
+
+
+class RenderEdits(C.Structure):
+    """gsx_render_edits: the viewer's selection / colour / displacement uniforms and the hidden labels."""
+    _fields_ = [("selection_mode", C.c_int32), ("selected_label", C.c_int32), ("enable_custom_color", C.c_int32),
+                ("custom_color", C.c_float * 3), ("num_colors", C.c_int32), ("color_labels", C.c_int32 * EDIT_TABLE_MAX),
+                ("colors", C.c_float * (3 * EDIT_TABLE_MAX)), ("enable_displacement", C.c_int32),
+                ("num_displacements", C.c_int32), ("displacement_labels", C.c_int32 * EDIT_TABLE_MAX),
+                ("displacements", C.c_float * (3 * EDIT_TABLE_MAX)), ("num_hidden", C.c_int64), ("hidden_labels", C.c_void_p)]
+
+
 _SIGS = {
     "gsx_abi_version": (C.c_int, []),
     "gsx_device_count": (C.c_int, []),
@@ -104,6 +117,8 @@ _SIGS = {
     "gsx_upload_splats": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
     "gsx_upload_sh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "gsx_num_splats": (C.c_int64, [C.c_void_p]),
+    "gsx_render_set_edits": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gsx_render_num_hidden": (C.c_int64, [C.c_void_p]),
     "gsx_render_view": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p]),
     "gsx_render_views": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gsx_render_image_device": (C.c_void_p, [C.c_void_p]),

@@ -525,6 +525,14 @@ int gsx_upload_sh(gsx_ctx* ctx, const float* f_rest, int32_t sh_degree) {
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::upload_sh(c, f_rest, sh_degree); });
 }
+int gsx_render_set_edits(gsx_ctx* ctx, const gsx_render_edits* edits) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::render_set_edits(c, edits); });
+}
+int64_t gsx_render_num_hidden(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c ? c->r_edit_hidden_n : 0;
+}
 int64_t gsx_num_splats(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
     return c ? c->rn : 0;

@@ -254,6 +254,11 @@ struct Ctx {
     DevBuf r_fdc, r_shc;                 // f_dc (source order); SH coefficients coef[k][i][3] (importance order)
     bool r_sh_valid = false, r_sh_on = false;
     int r_sh_deg = 0;
+    // label edits (gsx_render_set_edits): the exact int32 labels in importance order (kept from the upload), and per state a
+    // 16-bit code per splat, the tables (render.hip: EditTables) and the sorted hidden labels
+    DevBuf r_labels, r_edit_code, r_edit_tab, r_edit_hidden;
+    bool r_edits_on = false;
+    int64_t r_edit_hidden_n = 0;         // splats the state hides
     DevBuf r_image;                      // float4[H][W] of the last view
     int r_W = 0, r_H = 0;
     DevBuf r_ranges, r_small, r_scan;
@@ -365,6 +370,7 @@ void debug_cull_planes(const gsx_camera* cam, double* out);
 int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const float* rot, const float* opacity,
                   const float* f_dc, const int32_t* labels);
 int upload_sh(Ctx* c, const float* f_rest, int deg);
+int render_set_edits(Ctx* c, const gsx_render_edits* edits);
 int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out);
 int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* const* rgba_out);
 void render_release_twin(Ctx* c);

@@ -26,6 +26,7 @@
 #include <cstring>
 #include <new>
 #include <thread>
+#include <vector>
 
 #include "gsx_ctx.hpp"
 #include "tile_test.hpp"
@@ -283,10 +284,15 @@ struct PreGeom {
     bool colour;
 };
 
-__device__ __forceinline__ PreGeom pre_geom(const uint4 t0, const uint4 t1, const ViewUniforms& u) {
+// DISP (label edits): (dx, dy, dz) is added to the centre the VERTEX SHADER sees (gs.js:701-704) - the depth key above it stays
+// that of the texture position, as runSort's buffer is never displaced (include/gsx.h).  Without DISP: the code as it was.
+template <bool DISP = false>
+__device__ __forceinline__ PreGeom pre_geom(const uint4 t0, const uint4 t1, const ViewUniforms& u, float dx_ = 0.f, float dy_ = 0.f,
+                                            float dz_ = 0.f) {
     PreGeom o;
-    const float cx_ = __uint_as_float(t0.x), cy_ = __uint_as_float(t0.y), cz_ = __uint_as_float(t0.z);
+    float cx_ = __uint_as_float(t0.x), cy_ = __uint_as_float(t0.y), cz_ = __uint_as_float(t0.z);
     o.depth = js_toint32((u.vp2 * (double)cx_ + u.vp6 * (double)cy_ + u.vp10 * (double)cz_) * 4096.0);
+    if (DISP) cx_ = cx_ + dx_, cy_ = cy_ + dy_, cz_ = cz_ + dz_;
     o.rect = kEmptyRect;
     o.r0 = make_float4(0.f, 0.f, 0.f, 0.f);
     o.g1x = o.g1y = o.fade = 0.f;
@@ -371,6 +377,96 @@ __device__ __forceinline__ PreGeom pre_geom(const uint4 t0, const uint4 t1, cons
 // the reference's colour: fade * rgba8 / 255 (gs.js:741-742); the SH colour replaces its first three channels
 __device__ __forceinline__ float rgba8_channel(const uint4 t1, int k, float fade) { return fade * (float)((t1.w >> (8 * k)) & 0xffu) / 255.0f; }
 
+// ---- label edits (include/gsx.h: gsx_render_set_edits) ----------------------------------------------------------------------
+// The shaders run two 100-entry loops per splat per frame (getDisplacement gs.js:686-693, getCustomColor gs.js:772-780).  Here
+// edit_code_kernel resolves them ONCE per state into 16 bits per splat; the pre kernels' EDIT instantiations read the code and
+// the tables (a 2.5 KB device struct: the flags and u_customColor are wave-uniform scalar loads, a table row is indexed by the
+// splat's slot).
+//   code bits 0-6: slot + 1 in the colour table (0: none), 7-13: slot + 1 in the displacement table, 14: hidden, 15: the label
+//   equals uSelectedLabel
+static constexpr unsigned kEditHidden = 1u << 14, kEditSelected = 1u << 15;
+struct EditTables {
+    float colour[GSX_EDIT_TABLE_MAX][3];
+    float disp[GSX_EDIT_TABLE_MAX][3];
+    int colour_label[GSX_EDIT_TABLE_MAX];
+    int disp_label[GSX_EDIT_TABLE_MAX];
+    float custom[3];
+    int n_colour, n_disp;
+    int selection_mode, enable_custom, enable_disp;
+    int selected;
+    int n_hidden;
+};
+
+// hidden: the labels hidden, SORTED (exact int32: the worker's Map key); everything else compares the label the shaders see,
+// int(uintBitsToFloat(cen.w))
+__global__ __launch_bounds__(kRB) void edit_code_kernel(const uint4* __restrict__ tex, const int* __restrict__ labels, long long n,
+                                                         const EditTables* __restrict__ ep, const int* __restrict__ hidden,
+                                                         uint16_t* __restrict__ code, unsigned long long* __restrict__ n_hidden_out) {
+    const EditTables& e = *ep;
+    const long long i = (long long)blockIdx.x * kRB + threadIdx.x;
+    bool hid = false;
+    if (i < n) {
+        const int vlabel = (int)__uint_as_float(tex[2 * i].w);
+        unsigned c = 0;
+        for (int k = e.n_colour - 1; k >= 0; --k)  // descending: the FIRST match is the one that stays
+            if (e.colour_label[k] == vlabel) c = (c & ~127u) | (unsigned)(k + 1);
+        for (int k = e.n_disp - 1; k >= 0; --k)
+            if (e.disp_label[k] == vlabel) c = (c & ~(127u << 7)) | ((unsigned)(k + 1) << 7);
+        if (vlabel == e.selected) c |= kEditSelected;
+        const int lab = labels[i];
+        int lo = 0, hi = e.n_hidden;  // first entry >= lab
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (hidden[mid] < lab) lo = mid + 1;
+            else hi = mid;
+        }
+        hid = lo < e.n_hidden && hidden[lo] == lab;
+        if (hid) c |= kEditHidden;
+        code[i] = (uint16_t)c;
+    }
+    const unsigned long long m = __ballot(hid);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_hidden_out, (unsigned long long)__popcll(m));
+}
+
+// the exact int32 labels in importance order (the worker's labelData): the texture word holds them rounded to fp32
+__global__ __launch_bounds__(kRB) void labels_pack_kernel(const uint32_t* __restrict__ order, long long n, const int* __restrict__ labels,
+                                                           int* __restrict__ out) {
+    const long long j = (long long)blockIdx.x * kRB + threadIdx.x;
+    if (j < n) out[j] = labels ? labels[order[j]] : -999999;
+}
+
+// the vertex shader's displacement of a splat (gs.js:701-704): the table row, or vec3(0.0) without one; nothing is added
+// while u_enableDisplacement is off
+__device__ __forceinline__ void edit_displacement(unsigned code, const EditTables& e, float& dx, float& dy, float& dz) {
+    const unsigned slot = (code >> 7) & 127u;
+    dx = dy = dz = 0.f;
+    if (e.enable_disp != 0 && slot != 0u) dx = e.disp[slot - 1][0], dy = e.disp[slot - 1][1], dz = e.disp[slot - 1][2];
+}
+
+__device__ __forceinline__ float glsl_mix(float x, float y, float a) { return x * (1.0f - a) + y * a; }
+
+// fragment shader, gs.js:786-797, on the splat's colour (it does not depend on the pixel): col[0..2] = vColor.rgb, faded.
+// Hidden: the alpha BYTE is 0 (gs.js:320), vColor.a = fade * 0 / 255.
+__device__ __forceinline__ void edit_colour(float col[4], unsigned code, const EditTables& e, float fade) {
+    const unsigned slot = code & 127u;
+    if (slot != 0u) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) col[k] = glsl_mix(col[k], e.colour[slot - 1][k], 0.6f);
+    }
+    if (code & kEditSelected) {
+        if (e.enable_custom != 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) col[k] = e.custom[k];
+        }
+        if (e.selection_mode != 0) {
+            col[0] = glsl_mix(col[0], 1.0f, 0.5f);
+            col[1] = glsl_mix(col[1], 0.0f, 0.5f);
+            col[2] = glsl_mix(col[2], 0.0f, 0.5f);
+        }
+    }
+    if (code & kEditHidden) col[3] = fade * 0.0f / 255.0f;
+}
+
 // One splat in one view, complete (pre_kernel).  The colour is only needed for splats that reach a pixel: 192 B of SH
 // coefficients per splat.  (Deferring it further, to the splats a depth phase really bins, was measured: those are visited in
 // DEPTH order, the coefficient reads become gathers and cost 9x what the skipped splats save.)
@@ -381,10 +477,13 @@ struct PreOut {
     float2 r2;
 };
 
-template <class Coef>
+template <bool EDIT, class Coef>
 __device__ __forceinline__ PreOut pre_one(const uint4 t0, const uint4 t1, const ViewUniforms& u, bool sh_on, int sh_deg, float cpx,
-                                          float cpy, float cpz, const Coef& cf) {
-    const PreGeom g = pre_geom(t0, t1, u);
+                                          float cpy, float cpz, const Coef& cf, unsigned code, const EditTables* ep) {
+    float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+    if (EDIT) edit_displacement(code, *ep, ddx, ddy, ddz);
+    // (u_enableDisplacement off: + 0 here where the shader adds nothing - only a -0.0 coordinate could tell, and no output does)
+    const PreGeom g = EDIT ? pre_geom<true>(t0, t1, u, ddx, ddy, ddz) : pre_geom(t0, t1, u);
     PreOut o;
     o.depth = g.depth;
     o.rect = g.rect;
@@ -401,6 +500,7 @@ __device__ __forceinline__ PreOut pre_one(const uint4 t0, const uint4 t1, const 
 #pragma unroll
             for (int k = 0; k < 3; ++k) col[k] = g.fade * rgb[k];
         }
+        if (EDIT) edit_colour(col, code, *ep, g.fade);
         o.r1 = make_float4(g.g1x, g.g1y, col[0], col[1]);
         o.r2 = make_float2(col[2], col[3]);
     }
@@ -429,10 +529,13 @@ __device__ __forceinline__ void depth_range_to(int lo, int hi, int* __restrict__
 // One pass over the texel pairs per view.  pre[4] = {min depth, max depth, splat 0's tile rectangle, -}: min / max over ALL
 // splats (gs.js:436-441); the rectangle of splat 0 is kept apart because the blend's epilogue draws splat 0 again even when
 // bucket_kernel drops it (and clears its entry of tile_rect).
+// EDIT: the label edits' instantiation (code: edit_code_kernel's 16 bits per splat); without it the kernel is what it was.
+template <bool EDIT>
 __global__ __launch_bounds__(kRB) void pre_kernel(const uint4* __restrict__ tex, long long n, ViewUniforms u,
                                                    const float* __restrict__ sh_coef, int sh_deg, float cpx, float cpy, float cpz,
                                                    int* __restrict__ depth, int* __restrict__ pre,
-                                                   float4* __restrict__ rec, uint32_t* __restrict__ tile_rect) {
+                                                   float4* __restrict__ rec, uint32_t* __restrict__ tile_rect,
+                                                   const uint16_t* __restrict__ code, const EditTables* __restrict__ ep) {
     __shared__ int slo[4], shi[4];
     int lo = 2147483647, hi = -2147483647 - 1;
     // grid-stride: the launch is capped at 2048 workgroups, i.e. 4096 same-address atomics per frame (one pair per
@@ -440,7 +543,7 @@ __global__ __launch_bounds__(kRB) void pre_kernel(const uint4* __restrict__ tex,
     for (long long i = (long long)blockIdx.x * kRB + threadIdx.x; i < n; i += (long long)gridDim.x * kRB) {
         const uint4 t0 = tex[2 * i], t1 = tex[2 * i + 1];
         const CoefMem cf{sh_coef, n, i};
-        const PreOut o = pre_one(t0, t1, u, sh_coef != nullptr, sh_deg, cpx, cpy, cpz, cf);
+        const PreOut o = pre_one<EDIT>(t0, t1, u, sh_coef != nullptr, sh_deg, cpx, cpy, cpz, cf, EDIT ? (unsigned)code[i] : 0u, ep);
         depth[i] = o.depth;
         lo = min(lo, o.depth);
         hi = max(hi, o.depth);
@@ -478,9 +581,12 @@ struct PreMultiArgs {
     float4* rec[kPreViews];
     uint32_t* rect[kPreViews];
     int nv;
+    // label edits (read by the EDIT instantiations only; behind everything else: the other offsets are what they were)
+    const uint16_t* code;
+    const EditTables* edits;
 };
 
-template <int NV>
+template <int NV, bool EDIT>
 __global__ __launch_bounds__(kRB) void pre_multi_kernel(const uint4* __restrict__ tex, long long n, const float* __restrict__ sh_coef,
                                                          int sh_deg, const PreMultiArgs* __restrict__ ap) {
     // (the arguments live in device memory: the views' uniforms are scalar loads)
@@ -493,6 +599,12 @@ __global__ __launch_bounds__(kRB) void pre_multi_kernel(const uint4* __restrict_
     for (long long i = (long long)blockIdx.x * kRB + threadIdx.x; i < n; i += (long long)gridDim.x * kRB) {
         const uint4 t0 = tex[2 * i], t1 = tex[2 * i + 1];
         const float px = __uint_as_float(t0.x), py = __uint_as_float(t0.y), pz = __uint_as_float(t0.z);
+        unsigned code = 0u;  // label edits: the splat's code and its displacement, the same for every view
+        float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+        if (EDIT) {
+            code = a.code[i];
+            edit_displacement(code, *a.edits, ddx, ddy, ddz);
+        }
         // ---- geometry of every view: depth key, rectangle and the first record go out at once; what the colour needs stays
         float g1x[NV], g1y[NV], fade[NV];
         unsigned want = 0;  // bit v: view v wants a colour for this splat
@@ -502,7 +614,7 @@ __global__ __launch_bounds__(kRB) void pre_multi_kernel(const uint4* __restrict_
             // of the splat loop as invariants, the uniforms of four views are 375 spilled SGPRs)
             const PreMultiArgs* av = ap;
             asm volatile("" : "+s"(av));
-            const PreGeom g = pre_geom(t0, t1, av->u[v]);
+            const PreGeom g = EDIT ? pre_geom<true>(t0, t1, av->u[v], ddx, ddy, ddz) : pre_geom(t0, t1, av->u[v]);
             __builtin_nontemporal_store(g.depth, &a.depth[v][i]);  // streaming stores: the records are not read again here
             lo[v] = min(lo[v], g.depth);
             hi[v] = max(hi[v], g.depth);
@@ -551,6 +663,7 @@ __global__ __launch_bounds__(kRB) void pre_multi_kernel(const uint4* __restrict_
 #pragma unroll
                     for (int c = 0; c < 3; ++c) col[c] = fade[v] * sh_clamp(acc[v][c]);
                 }
+                if (EDIT) edit_colour(col, code, *a.edits, fade[v]);
                 r1 = make_float4(g1x[v], g1y[v], col[0], col[1]);
                 r2 = make_float2(col[2], col[3]);
             }
@@ -845,6 +958,8 @@ int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const
                   const float* f_dc, const int32_t* labels) {
     GSX_HIP(c, hipSetDevice(c->device));
     c->rn = 0;
+    c->r_edits_on = false;  // the edit codes were resolved against the labels that go away here
+    c->r_edit_hidden_n = 0;
     if (n < 0 || (n > 0 && (!xyz || !f_dc || (scale && (!rot || !opacity)))))
         return fail(c, GSX_E_INVALID, "upload_splats: xyz and f_dc are required; scale needs rot and opacity");
     if (n > ((int64_t)1 << 30)) return fail(c, GSX_E_UNSUPPORTED, "upload_splats: n > 2^30");
@@ -891,10 +1006,83 @@ int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const
                            scale ? drot.as<float>() : nullptr, opacity ? dop.as<float>() : nullptr, ddc.as<float>(),
                            labels ? dlab.as<int>() : nullptr, c->r_buffer.as<uint4>(), c->r_tex.as<uint4>());
     }
+    GSX_HIP(c, c->r_labels.ensure(4 * n));
+    hipLaunchKernelGGL(labels_pack_kernel, dim3(grid_for(n)), dim3(kRB), 0, c->stream, c->r_order.as<uint32_t>(), (long long)n,
+                       labels ? dlab.as<int>() : nullptr, c->r_labels.as<int>());
     GSX_HIP(c, hipGetLastError());
     GSX_HIP(c, hipStreamSynchronize(c->stream));
     c->rn = n;
     c->r_sh_on = false;
+    return GSX_OK;
+}
+
+// gsx_render_set_edits: validate, resolve the tables into one code per splat (edit_code_kernel), keep the tables on the device
+int render_set_edits(Ctx* c, const gsx_render_edits* e) {
+    if (!e) {  // clear
+        c->r_edits_on = false;
+        c->r_edit_hidden_n = 0;
+        return GSX_OK;
+    }
+    if (e->num_colors < 0 || e->num_colors > GSX_EDIT_TABLE_MAX)
+        return fail(c, GSX_E_INVALID, "render_set_edits: num_colors %d outside [0, %d]", e->num_colors, GSX_EDIT_TABLE_MAX);
+    if (e->num_displacements < 0 || e->num_displacements > GSX_EDIT_TABLE_MAX)
+        return fail(c, GSX_E_INVALID, "render_set_edits: num_displacements %d outside [0, %d]", e->num_displacements, GSX_EDIT_TABLE_MAX);
+    if (e->num_hidden < 0 || e->num_hidden > ((int64_t)1 << 30) || (e->num_hidden > 0 && !e->hidden_labels))
+        return fail(c, GSX_E_INVALID, "render_set_edits: num_hidden %lld without hidden_labels, or outside [0, 2^30]", (long long)e->num_hidden);
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(e->custom_color[k])) return fail(c, GSX_E_INVALID, "render_set_edits: custom_color is not finite");
+    for (int i = 0; i < e->num_colors; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(e->colors[i][k])) return fail(c, GSX_E_INVALID, "render_set_edits: colors[%d] is not finite", i);
+    for (int i = 0; i < e->num_displacements; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(e->displacements[i][k]))
+                return fail(c, GSX_E_INVALID, "render_set_edits: displacements[%d] is not finite", i);
+    if (c->rn <= 0) return fail(c, GSX_E_STATE, "render_set_edits before upload_splats");
+    GSX_HIP(c, hipSetDevice(c->device));
+    EditTables t{};
+    for (int i = 0; i < e->num_colors; ++i) {
+        t.colour_label[i] = e->color_labels[i];
+        for (int k = 0; k < 3; ++k) t.colour[i][k] = e->colors[i][k];
+    }
+    for (int i = 0; i < e->num_displacements; ++i) {
+        t.disp_label[i] = e->displacement_labels[i];
+        for (int k = 0; k < 3; ++k) t.disp[i][k] = e->displacements[i][k];
+    }
+    for (int k = 0; k < 3; ++k) t.custom[k] = e->custom_color[k];
+    t.n_colour = e->num_colors;
+    t.n_disp = e->num_displacements;
+    t.selection_mode = e->selection_mode != 0;
+    t.enable_custom = e->enable_custom_color != 0;
+    t.enable_disp = e->enable_displacement != 0;
+    t.selected = e->selected_label;
+    std::vector<int> hidden(e->hidden_labels, e->hidden_labels + e->num_hidden);
+    hidden.erase(std::remove(hidden.begin(), hidden.end(), -999999), hidden.end());  // NO_SELECTION is never hidden, gs.js:619
+    std::sort(hidden.begin(), hidden.end());
+    hidden.erase(std::unique(hidden.begin(), hidden.end()), hidden.end());
+    t.n_hidden = (int)hidden.size();
+    const long long n = c->rn;
+    c->r_edits_on = false;
+    c->r_edit_hidden_n = 0;
+    GSX_HIP(c, c->r_edit_code.ensure(2 * (size_t)n));
+    constexpr size_t kCountAt = (sizeof(EditTables) + 7) / 8 * 8;  // a u64 behind the tables: the splats hidden
+    GSX_HIP(c, c->r_edit_tab.ensure(kCountAt + 8));
+    GSX_HIP(c, c->r_edit_hidden.ensure(4 * std::max<size_t>(hidden.size(), 1)));
+    unsigned long long* count_dev = reinterpret_cast<unsigned long long*>(c->r_edit_tab.as<char>() + kCountAt);
+    unsigned long long count = 0;
+    GSX_HIP(c, hipMemcpyAsync(c->r_edit_tab.p, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemsetAsync(count_dev, 0, 8, c->stream));
+    if (!hidden.empty()) GSX_HIP(c, hipMemcpyAsync(c->r_edit_hidden.p, hidden.data(), 4 * hidden.size(), hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, "render_edit_code");
+        hipLaunchKernelGGL(edit_code_kernel, dim3(grid_for(n)), dim3(kRB), 0, c->stream, c->r_tex.as<uint4>(), c->r_labels.as<int>(), n,
+                           c->r_edit_tab.as<EditTables>(), c->r_edit_hidden.as<int>(), c->r_edit_code.as<uint16_t>(), count_dev);
+    }
+    GSX_HIP(c, hipGetLastError());
+    GSX_HIP(c, hipMemcpyAsync(&count, count_dev, 8, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));  // (the host copies above live until here)
+    c->r_edit_hidden_n = (int64_t)count;
+    c->r_edits_on = true;
     return GSX_OK;
 }
 
@@ -1089,10 +1277,12 @@ int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out) {
         if (!ext_pre) {  // (a frame that is redone because a phase overflowed the pair buffers keeps the pre pass's records)
             GSX_HIP(c, hipMemcpyAsync(c->r_pre.p, kPreInit, sizeof kPreInit, hipMemcpyHostToDevice, c->stream));
             ProfScope ps(c, "render_pre");
-            hipLaunchKernelGGL(pre_kernel, dim3(std::min<unsigned>(grid_for(n), 2048u)), dim3(kRB), 0, c->stream, c->r_tex.as<uint4>(), n, u,
+            hipLaunchKernelGGL(c->r_edits_on ? pre_kernel<true> : pre_kernel<false>, dim3(std::min<unsigned>(grid_for(n), 2048u)), dim3(kRB), 0,
+                               c->stream, c->r_tex.as<uint4>(), n, u,
                                c->r_sh_on ? c->r_shc.as<float>() : nullptr, c->r_sh_deg, (float)cam->p[0], (float)cam->p[1],
                                (float)cam->p[2], c->r_depth.as<int>(), c->r_pre.as<int>(), c->r_rec.as<float4>(),
-                               c->r_rect.as<uint32_t>());
+                               c->r_rect.as<uint32_t>(), c->r_edits_on ? c->r_edit_code.as<uint16_t>() : (const uint16_t*)nullptr,
+                               c->r_edits_on ? c->r_edit_tab.as<EditTables>() : (const EditTables*)nullptr);
         }
         {
             ProfScope ps(c, "render_bucket");
@@ -1219,6 +1409,9 @@ static int twin_sync_scene(Ctx* c, int k) {
     Ctx* t = c->twins[k];
     t->r_tex.alias(c->r_tex);
     t->r_shc.alias(c->r_shc);
+    t->r_edit_code.alias(c->r_edit_code);  // label edits: every frame in flight draws the same state
+    t->r_edit_tab.alias(c->r_edit_tab);
+    t->r_edits_on = c->r_edits_on;
     t->rn = c->rn;
     t->r_sh_on = c->r_sh_on;
     t->r_sh_deg = c->r_sh_deg;
@@ -1243,7 +1436,7 @@ void render_release_twin(Ctx* c) {
     for (Ctx*& t : c->twins) {
         if (!t) continue;
         (void)hipStreamSynchronize(t->stream);
-        for (DevBuf* b : {&t->r_tex, &t->r_shc, &t->r_image, &t->r_ranges, &t->r_small, &t->r_scan, &t->r_depth, &t->r_bucket, &t->r_rect,
+        for (DevBuf* b : {&t->r_tex, &t->r_shc, &t->r_edit_code, &t->r_edit_tab, &t->r_image, &t->r_ranges, &t->r_small, &t->r_scan, &t->r_depth, &t->r_bucket, &t->r_rect,
                           &t->r_count, &t->r_offset, &t->r_rec, &t->r_keys0, &t->r_keys1, &t->r_vals0, &t->r_vals1,
                           &t->r_tile_order, &t->r_sat, &t->r_d0, &t->r_d1, &t->r_d2, &t->r_d3, &t->r_rects, &t->sort_hist, &t->r_pre})
             b->release();
@@ -1321,15 +1514,20 @@ int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* con
             a.pre[v] = ps.pre.as<int>();
             a.rec[v] = ps.rec.as<float4>();
             a.rect[v] = ps.rect.as<uint32_t>();
+            a.code = c->r_edits_on ? c->r_edit_code.as<uint16_t>() : nullptr;
+            a.edits = c->r_edits_on ? c->r_edit_tab.as<EditTables>() : nullptr;
             GSX_HIP(c, hipMemcpyAsync(ps.pre.p, kPreInit, sizeof kPreInit, hipMemcpyHostToDevice, c->stream));
         }
         PreMultiArgs* a_dev = c->r_pre_args.as<PreMultiArgs>() + set;
         GSX_HIP(c, hipMemcpyAsync(a_dev, &a, sizeof a, hipMemcpyHostToDevice, c->stream));
         using PK = void (*)(const uint4*, long long, const float*, int, const PreMultiArgs*);
-        static const PK kernels[kPreViews] = {pre_multi_kernel<1>, pre_multi_kernel<2>, pre_multi_kernel<3>,
-                                              pre_multi_kernel<4>, pre_multi_kernel<5>, pre_multi_kernel<6>};
+        static const PK kernels[2][kPreViews] = {
+            {pre_multi_kernel<1, false>, pre_multi_kernel<2, false>, pre_multi_kernel<3, false>, pre_multi_kernel<4, false>,
+             pre_multi_kernel<5, false>, pre_multi_kernel<6, false>},
+            {pre_multi_kernel<1, true>, pre_multi_kernel<2, true>, pre_multi_kernel<3, true>, pre_multi_kernel<4, true>,
+             pre_multi_kernel<5, true>, pre_multi_kernel<6, true>}};  // [1]: the label edits' instantiations
         static_assert(kPreViews == 6, "one instantiation per group size");
-        hipLaunchKernelGGL(kernels[a.nv - 1], dim3(std::min<unsigned>(grid_for(c->rn), 2048u)), dim3(kRB), 0, c->stream, c->r_tex.as<uint4>(),
+        hipLaunchKernelGGL(kernels[c->r_edits_on ? 1 : 0][a.nv - 1], dim3(std::min<unsigned>(grid_for(c->rn), 2048u)), dim3(kRB), 0, c->stream, c->r_tex.as<uint4>(),
                            (long long)c->rn, c->r_sh_on ? c->r_shc.as<float>() : nullptr, c->r_sh_deg, a_dev);
         GSX_HIP(c, hipGetLastError());
         GSX_HIP(c, hipEventRecord(c->r_pre_ev[set], c->stream));

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Camera, check
+from ._lib import EDIT_TABLE_MAX, NO_SELECTION, Camera, RenderEdits, check
 
 try:  # CPython binding of the per-view hand-over (csrc/gsxfast.c); without it the ctypes path below does the same
     from . import _gsxfast as _fast
@@ -374,6 +374,41 @@ class Context:
         if k1:
             fr = np.ascontiguousarray(np.asarray(f_rest, dtype=np.float32).reshape(self.n_splats, 3 * k1))
         check(self._lib.gsx_upload_sh(self.h, None if fr is None else fr.ctypes.data, int(degree)), self.h)
+
+    def set_render_edits(self, selected=None, selection_mode=False, colours=None, custom_colour=None, displacements=None,
+                         hidden=()):
+        """Label edits of the viewer (gsx_render_set_edits) for every following frame, until clear_render_edits() or the
+        next upload_splats: `selected` + `selection_mode` highlight a label red, `colours` {label: rgb} recolours labels
+        (mix 0.6), `custom_colour` rgb replaces the selected label's colour, `displacements` {label: xyz} moves labels
+        (drawing only: depth order and hit_test stay), `hidden` labels are drawn with alpha 0.  A dict's insertion order
+        is the table order, as the viewer's Map iterates; at most 100 entries each."""
+        e = RenderEdits()
+        e.selection_mode = 1 if selection_mode else 0
+        e.selected_label = NO_SELECTION if selected is None else int(selected)
+        if custom_colour is not None:
+            e.enable_custom_color = 1
+            for k, v in enumerate(np.asarray(custom_colour, np.float32).reshape(3)):
+                e.custom_color[k] = v
+        colours, displacements = dict(colours or {}), dict(displacements or {})
+        e.num_colors, e.num_displacements = len(colours), len(displacements)  # (> 100: the library says so)
+        for i, (label, rgb) in enumerate(list(colours.items())[:EDIT_TABLE_MAX]):
+            e.color_labels[i] = int(label)
+            e.colors[3 * i:3 * i + 3] = [float(v) for v in np.asarray(rgb, np.float32).reshape(3)]
+        for i, (label, xyz) in enumerate(list(displacements.items())[:EDIT_TABLE_MAX]):
+            e.displacement_labels[i] = int(label)
+            e.displacements[3 * i:3 * i + 3] = [float(v) for v in np.asarray(xyz, np.float32).reshape(3)]
+        e.enable_displacement = 1 if displacements else 0  # gs.js:919: displacementMap.size > 0
+        hid = np.ascontiguousarray(list(hidden), dtype=np.int32)
+        e.num_hidden = len(hid)
+        e.hidden_labels = hid.ctypes.data if len(hid) else None
+        check(self._lib.gsx_render_set_edits(self.h, C.byref(e)), self.h)
+
+    def clear_render_edits(self):
+        check(self._lib.gsx_render_set_edits(self.h, None), self.h)
+
+    def render_num_hidden(self):
+        """Splats the current edit state hides."""
+        return self._lib.gsx_render_num_hidden(self.h)
 
     def render_view(self, camera, width, height, to_host=True):
         """One frame of the viewer's pipeline -> (height, width, 4) float32 premultiplied RGBA."""

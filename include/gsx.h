@@ -388,6 +388,69 @@ int64_t gsx_render_num_pairs_consumed(const gsx_ctx* ctx);
  * *index_out = importance-order row of that splat or -1.  Uses the splats of gsx_upload_splats. */
 int gsx_hit_test(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, double x, double y,
                  int32_t* label_out, int64_t* index_out);
+/* Label edits — what the viewer does WITH the labels of gsx_upload_splats: highlight, recolour, hide and displace the
+ * splats of a label.  The state mirrors the shaders' uniforms and the worker's visibilityMap; it changes how every
+ * following gsx_render_view / gsx_render_views frame is drawn (all frames in flight see the same state) and nothing
+ * while it is not set: frames without edits are bit-identical to those of a context that never had any.
+ *
+ *   selection_mode, selected_label   uSelectionMode / uSelectedLabel, gs.js:757-758, 795-797:
+ *                                    rgb = mix(rgb, (1, 0, 0), 0.5) for the splats of the selected label
+ *   enable_custom_color, custom_color  u_enableCustomColor / u_customColor, gs.js:760-761, 790-792: replaces the rgb of the
+ *                                    selected label's splats (before the highlight)
+ *   num_colors, color_labels, colors u_numCustomColors / u_customColorLabels / u_customColors, gs.js:762-780, 787 (filled as
+ *                                    gs.js:26-42 does): rgb = mix(vColor.rgb, colors[i], 0.6) for the FIRST entry i whose
+ *                                    label matches
+ *   enable_displacement, num_displacements, displacement_labels, displacements
+ *                                    u_enableDisplacement / u_numDisplacements / u_displacementLabels / u_displacementMap,
+ *                                    gs.js:674-677, 686-704 (filled as gs.js:906-923): the first matching entry is added to
+ *                                    the splat's centre before view * centre; with the flag set a splat without an entry
+ *                                    gets + (0, 0, 0) as in the shader
+ *   num_hidden, hidden_labels        the labels the worker's visibilityMap holds as false, gs.js:302-307, 320: the alpha
+ *                                    byte of their splats is multiplied by 0.  NO_SELECTION (-999999) in the list is
+ *                                    ignored as the worker ignores it (gs.js:617-622).
+ *
+ * Order, as in the fragment shader (gs.js:786-797): table colour, then custom_color, then the highlight.  vColor.rgb already
+ * carries the depth fade (gs.js:741), so a table colour is 0.4 * fade * c + 0.6 * colors[i] (NOT faded), and custom_color is
+ * not faded at all.  Alpha is never edited except by hiding.  With the SH colour switched on (gsx_upload_sh) vColor.rgb is
+ * fade * clamp(0.5 + SH) and the edits apply on top of it in the same order; the SH direction is taken from the UNDISPLACED
+ * position.  Neither is pinned by the reference (it has no SH colour).
+ *
+ * Label compare: the shaders see int(uintBitsToFloat(cen.w)), the label after a round trip through fp32 (gs.js:314, 699);
+ * colours, custom_color, highlight and displacements compare THAT value with the int32 entries, so two labels beyond
+ * +-2^24 that round to the same float are edited alike.  Hiding compares the exact int32 label (the worker's Map key,
+ * gs.js:302-304).
+ *
+ * Displacement moves the vertex shader's centre only: the cull (gs.js:709-713), the Jacobian, the window position, the tile
+ * rectangle and the depth fade.  The DEPTH ORDER DOES NOT MOVE: runSort (gs.js:417-462) reads the worker's buffer, which the
+ * live viewer never displaces (nothing posts 'updateDisplacement'), so depth keys, the depth range and the dropped farthest
+ * splat stay those of the undisplaced scene, and gsx_hit_test ignores every edit.  A reference quirk, reproduced.
+ *
+ * A hidden splat stays in the tile lists with alpha 0 (it contributes exactly 0 wherever its fade is finite).
+ *
+ * gsx_render_set_edits(ctx, NULL) clears the state; so does every gsx_upload_splats (the labels the state was resolved
+ * against are gone).  The call resolves the tables ONCE into a 16-bit code per splat (one kernel over the n labels) instead
+ * of the shader's two 100-entry loops per splat per frame; the arrays are copied, the caller may free them at once.
+ * Errors: GSX_E_INVALID for a count outside 0..100, a NULL hidden_labels with num_hidden > 0, a non-finite colour or
+ * displacement; GSX_E_STATE before gsx_upload_splats. */
+#define GSX_EDIT_TABLE_MAX 100
+typedef struct gsx_render_edits {
+    int32_t selection_mode;
+    int32_t selected_label;
+    int32_t enable_custom_color;
+    float custom_color[3];
+    int32_t num_colors;
+    int32_t color_labels[GSX_EDIT_TABLE_MAX];
+    float colors[GSX_EDIT_TABLE_MAX][3];
+    int32_t enable_displacement;
+    int32_t num_displacements;
+    int32_t displacement_labels[GSX_EDIT_TABLE_MAX];
+    float displacements[GSX_EDIT_TABLE_MAX][3];
+    int64_t num_hidden;
+    const int32_t* hidden_labels;
+} gsx_render_edits;
+int gsx_render_set_edits(gsx_ctx* ctx, const gsx_render_edits* edits);
+/* splats the current edit state hides (0 without one) */
+int64_t gsx_render_num_hidden(const gsx_ctx* ctx);
 /* test hooks (any pointer may be NULL): the packed .splat rows (n x 32 bytes) and importance
  * permutation (gs.js:527), the texture words (n x 8 u32, gs.js:311-353) and the last view's 16-bit
  * depth buckets (65536 = dropped by the JS counting sort, gs.js:443-457) */

@@ -9,7 +9,12 @@
 // createNewDrawable with loader callbacks that never show anything; every frame is rendered into an FBO.
 //
 // The GL calls restate the viewer's host side (file = Web_Viewer_Gaussians_Selection/gaussians_selection.js):
-//   program, uniforms .......... :1006-1053   (uSelectionMode 0, no displacement, no custom colours: all other uniforms stay 0)
+//   program, uniforms .......... :1006-1053   (uSelectionMode 0, no displacement, no custom colours: all other uniforms stay 0 -
+//                                              unless in.bin ends with the optional EDIT block, see below)
+//   label edits (EDIT block) .... :1588-1589   uSelectionMode / uSelectedLabel; :26-42 u_customColors / u_customColorLabels /
+//                                              u_numCustomColors (uniform3fv of 100 vec3, uniform1iv of 100, uniform1i);
+//                                              u_enableCustomColor / u_customColor; :906-923 u_enableDisplacement /
+//                                              u_displacementMap / u_displacementLabels / u_numDisplacements
 //   blend state ................. :1033-1038   disable DEPTH_TEST; BLEND; blendFuncSeparate(ONE_MINUS_DST_ALPHA, ONE, same);
 //                                              FUNC_ADD
 //   quad (-2,-2 2,-2 2,2 -2,2) .. :1056-1063
@@ -22,6 +27,10 @@
 //
 // usage: gl_frames <vertex.glsl> <fragment.glsl> <in.bin> <out.f32>
 //   in.bin : int32 W, H, n, texw, texh; f32 view[16], proj[16], focal[2], viewport[2]; u32 tex[texw*texh*4]; i32 index[n]
+//            optionally followed by the EDIT block (tests/golden/make_golden_gl_edits.py), 810 words:
+//              i32 'EDIT' (0x45444954), uSelectionMode, uSelectedLabel, u_enableCustomColor; f32 u_customColor[3];
+//              i32 u_numCustomColors, u_customColorLabels[100]; f32 u_customColors[300];
+//              i32 u_enableDisplacement, u_numDisplacements, u_displacementLabels[100]; f32 u_displacementMap[300]
 //   out.f32: f32 [H][W][4], row 0 = TOP row of the image (GL's bottom-up rows flipped)
 #include <dlfcn.h>
 #include <stdint.h>
@@ -89,9 +98,12 @@ int main(int argc, char** argv) {
     const float *view = fl, *proj = fl + 16, *focal = fl + 32, *viewport = fl + 34;
     const uint32_t* tex = (const uint32_t*)(fl + 36);
     const int32_t* index = (const int32_t*)(tex + (size_t)texw * texh * 4);
-    if (W < 1 || H < 1 || n < 0 || texw != 2048 || texh < 1 ||
-        in_len != 20 + 36 * 4 + (size_t)texw * texh * 16 + (size_t)n * 4)
+    enum { kEditWords = 810, kEditMagic = 0x45444954 };
+    const size_t plain_len = 20 + 36 * 4 + (size_t)texw * texh * 16 + (size_t)n * 4;
+    if (W < 1 || H < 1 || n < 0 || texw != 2048 || texh < 1 || (in_len != plain_len && in_len != plain_len + kEditWords * 4))
         die("in.bin: bad header or size");
+    const int32_t* edit = in_len == plain_len ? NULL : index + n;  // the optional EDIT block
+    if (edit && edit[0] != kEditMagic) die("in.bin: bad EDIT block");
 
     void* drv = dlopen("/usr/lib/x86_64-linux-gnu/dri/swrast_dri.so", RTLD_NOW | RTLD_GLOBAL);
     if (!drv) die(dlerror());
@@ -135,7 +147,9 @@ int main(int argc, char** argv) {
     GLF(PFNGLGETUNIFORMLOCATIONPROC, glGetUniformLocation);
     GLF(PFNGLGETATTRIBLOCATIONPROC, glGetAttribLocation);
     GLF(PFNGLUNIFORM1IPROC, glUniform1i);
+    GLF(PFNGLUNIFORM1IVPROC, glUniform1iv);
     GLF(PFNGLUNIFORM2FVPROC, glUniform2fv);
+    GLF(PFNGLUNIFORM3FVPROC, glUniform3fv);
     GLF(PFNGLUNIFORMMATRIX4FVPROC, glUniformMatrix4fv);
     GLF(PFNGLGENBUFFERSPROC, glGenBuffers);
     GLF(PFNGLBINDBUFFERPROC, glBindBuffer);
@@ -207,6 +221,21 @@ int main(int argc, char** argv) {
     glBlendEquationSeparate(GL_FUNC_ADD, GL_FUNC_ADD);
     glUniform1i(glGetUniformLocation(prog, "uSelectionMode"), 0);
     glUniform1i(glGetUniformLocation(prog, "uSelectedLabel"), -2);  // NO_SELECTION: matches no label (uSelectionMode is 0 anyway)
+    if (edit) {  // the viewer's label edits, each uniform set with the call the viewer uses
+        const int32_t* ei = edit;
+        const float* ef = (const float*)edit;
+        glUniform1i(glGetUniformLocation(prog, "uSelectionMode"), ei[1]);
+        glUniform1i(glGetUniformLocation(prog, "uSelectedLabel"), ei[2]);
+        glUniform1i(glGetUniformLocation(prog, "u_enableCustomColor"), ei[3]);
+        glUniform3fv(glGetUniformLocation(prog, "u_customColor"), 1, ef + 4);
+        glUniform3fv(glGetUniformLocation(prog, "u_customColors"), 100, ef + 108);
+        glUniform1iv(glGetUniformLocation(prog, "u_customColorLabels"), 100, ei + 8);
+        glUniform1i(glGetUniformLocation(prog, "u_numCustomColors"), ei[7]);
+        glUniform1i(glGetUniformLocation(prog, "u_enableDisplacement"), ei[408]);
+        glUniform3fv(glGetUniformLocation(prog, "u_displacementMap"), 100, ef + 510);
+        glUniform1iv(glGetUniformLocation(prog, "u_displacementLabels"), 100, ei + 410);
+        glUniform1i(glGetUniformLocation(prog, "u_numDisplacements"), ei[409]);
+    }
 
     GLuint vao;
     glGenVertexArrays(1, &vao);

@@ -1,7 +1,9 @@
 // Runs the CPU half of the reference viewer (gaussians_selection.js: createWorker, getViewMatrix,
 // calculateProjectionMatrix, multiply4) under node, in a vm sandbox, on a PLY file and a list of
 // cameras, and dumps what the worker posts: the 32-byte splat buffer, the RGBA32UI texture words,
-// and depthIndex per camera.  Build-container only (needs /root/reference); emits DATA only.
+// and depthIndex per camera.  A camera entry may carry `hidden`: a list of labels that are switched off through the worker's
+// own 'toggleVisibility' message (gs.js:617-622) before the view is set; its texture (alpha bytes of those labels x 0) is
+// then dumped per camera.  Build-container only (needs /root/reference); emits DATA only.
 //   node tools/make_golden_js.js <in.ply> <cameras.json> <out.json>
 const fs = require("fs");
 const vm = require("vm");
@@ -38,6 +40,7 @@ for (let ci = 0; ci < cams.length; ci++) {
     ref.createWorker(self);
     const ab = ply.buffer.slice(ply.byteOffset, ply.byteOffset + ply.byteLength);
     self.onmessage({data: {ply: ab}});
+    for (const label of (cam.hidden || [])) self.onmessage({data: {type: "toggleVisibility", label: label, visible: false}});
     const view = ref.getViewMatrix(cam);
     const proj = ref.calculateProjectionMatrix(cam.fx, cam.fy, cam.render_width, cam.render_height);
     const viewProj = ref.multiply4(proj, view);
@@ -45,6 +48,7 @@ for (let ci = 0; ci < cams.length; ci++) {
     const buf = posted.find((m) => m.buffer);
     const tex = posted.find((m) => m.texdata);
     const srt = posted.find((m) => m.depthIndex);
+    const texs = posted.filter((m) => m.texdata);   // (the worker generates the texture again after every toggle)
     if (ci === 0) {
         out.vertexCount = buf.vertexCount;
         out.buffer = b64(new Uint8Array(buf.buffer));
@@ -60,7 +64,9 @@ for (let ci = 0; ci < cams.length; ci++) {
                                viewport: [cam.render_width, cam.render_height]}});
         hits.push(posted.find((m) => m.type === "selection").label);
     }
-    out.cameras.push({view: Array.from(view), proj: Array.from(proj), viewProj: Array.from(viewProj),
-                      depthIndex: b64(srt.depthIndex), hits});
+    const rec = {view: Array.from(view), proj: Array.from(proj), viewProj: Array.from(viewProj),
+                 depthIndex: b64(srt.depthIndex), hits};
+    if (cam.hidden) rec.texdata = b64(texs[texs.length - 1].texdata);  // the texture the worker generated LAST
+    out.cameras.push(rec);
 }
 fs.writeFileSync(outPath, JSON.stringify(out));
