@@ -166,6 +166,7 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
     if (!name) return gsx::fail(c, GSX_E_INVALID, "set_option: name is NULL");
     const std::string k(name);
     if (k == "spatial_sort") c->opt_spatial_sort = value != 0;
+    else if (k == "nn_brute") c->opt_nn_brute = value != 0;
     else if (k == "xcd_swizzle") {
         if (value < 0 || value > 65536) return gsx::fail(c, GSX_E_INVALID, "set_option: xcd_swizzle must be in [0,65536]");
         c->opt_xcd_swizzle = (int)value;
@@ -574,6 +575,30 @@ int gsx_kmeans(gsx_ctx* ctx, int64_t n, const float* points, const float* colors
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::kmeans(c, n, points, colors, k, init_index, max_iter, tol, labels_out, centroids_out, iterations_out,
                        converged_out); });
+}
+
+int gsx_normals(gsx_ctx* ctx, int64_t n, const float* points, int64_t k, double* normals_out, double* residuals_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::normals(c, n, points, k, normals_out, residuals_out); });
+}
+int gsx_debug_normals_moments(gsx_ctx* ctx, int64_t n, const float* points, int64_t k, double* moments_out) {
+    CTX_OR_FAIL(ctx);
+    if (!moments_out) return gsx::fail(c, GSX_E_INVALID, "debug_normals_moments: moments_out is NULL");
+    return gsx::guard(c, __func__, [&] { return gsx::normals(c, n, points, k, nullptr, nullptr, moments_out); });
+}
+int gsx_knn(gsx_ctx* ctx, int64_t n, const float* points, int32_t k, int32_t* index_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::knn(c, n, points, k, index_out); });
+}
+void* gsx_knn_device(gsx_ctx* ctx) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return c && c->nn_index_rows ? c->nn_index.p : nullptr;
+}
+int gsx_region_growing(gsx_ctx* ctx, int64_t n, const float* points, int64_t k_normals, int32_t k, double residual_threshold,
+                       double angle_threshold, int32_t* labels_out, double* normals_out, double* residuals_out, int32_t* n_regions_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::region_growing(c, n, points, k_normals, k, residual_threshold, angle_threshold, labels_out,
+                               normals_out, residuals_out, n_regions_out); });
 }
 
 int gsx_vote_culled(gsx_ctx* ctx, int64_t* wave_views, int32_t reset) {

@@ -299,6 +299,13 @@ struct Ctx {
     DevBuf r_d0, r_d1, r_d2, r_d3;       // level-1 sort ping-pong (bucket, splat)
     DevBuf r_rects;                      // the tile rectangles of a phase's splats in the phase's order (bin COUNT -> EMIT)
 
+    // nearest-neighbour search (normals.hip)
+    int opt_nn_brute = 0;                // 1: a 1 x 1 x 1 grid, i.e. every query visits every point (the search the grid is tested against)
+    DevBuf nn_index;                     // int32[n][k]: the lists of the last gsx_knn
+    int64_t nn_index_rows = 0;           // 0: none
+    DevBuf nn_pts, nn_cs;                // float4[n] (x, y, z, index) in cell order; u32[cells + 1]
+    DevBuf nn_out, nn_flag;              // double normals[3n] | residuals[n] | moments[9n] (before the search: the raw points of the finite check); int
+
     // profiling
     bool prof_on = false;
     std::vector<std::string> prof_names;
@@ -366,6 +373,12 @@ int filter_check(Ctx* c, double* out);
 int kmeans(Ctx* c, int64_t n, const float* points, const float* colors, int k, const int64_t* init_index, int max_iter,
            double tol, int32_t* labels_out, float* centroids_out, int32_t* iterations_out, int32_t* converged_out);
 void debug_cull_planes(const gsx_camera* cam, double* out);
+// normals.hip
+int normals(Ctx* c, int64_t n, const float* points, int64_t k, double* normals_out, double* residuals_out, double* moments_out = nullptr,
+            bool checked = false);
+int knn(Ctx* c, int64_t n, const float* points, int k, int32_t* index_out, bool checked = false);
+int region_growing(Ctx* c, int64_t n, const float* points, int64_t k_normals, int k, double residual_threshold, double angle_threshold,
+                   int32_t* labels_out, double* normals_out, double* residuals_out, int32_t* n_regions_out);
 // render.hip
 int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const float* rot, const float* opacity,
                   const float* f_dc, const int32_t* labels);

@@ -280,6 +280,44 @@ class Context:
                                    float(tol), labels.ctypes.data, cent.ctypes.data, C.byref(iters), C.byref(conv)), self.h)
         return cent, labels, int(iters.value), bool(conv.value)
 
+    # -- region-growing labeler (3D_clustering/region_growing.py; csrc/normals.hip, csrc/region_grow.cpp) --------------------
+    def normals(self, points, k):
+        """compute_normals + compute_residuals (region_growing.py:78-163) over the exact k nearest points of every point.
+        Returns (normals float64 (n, 3), residuals float64 (n,))."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        nrm = np.empty((len(pts), 3), np.float64)
+        res = np.empty(len(pts), np.float64)
+        check(self._lib.gsx_normals(self.h, len(pts), pts.ctypes.data, int(k), nrm.ctypes.data, res.ctypes.data), self.h)
+        return nrm, res
+
+    def debug_normals_moments(self, points, k):
+        """test hook: (centroid (n, 3), covariance (n, 3, 3)) of every point's k nearest points, as gsx_normals forms them"""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        mo = np.empty((len(pts), 9), np.float64)
+        check(self._lib.gsx_debug_normals_moments(self.h, len(pts), pts.ctypes.data, int(k), mo.ctypes.data), self.h)
+        cov = mo[:, [3, 4, 5, 4, 6, 7, 5, 7, 8]].reshape(-1, 3, 3)
+        return mo[:, :3].copy(), cov
+
+    def knn(self, points, k):
+        """kd_tree.query(points[i], k)[1] for every i (region_growing.py:205): int32 (n, k), ascending distance, then index."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        idx = np.empty((len(pts), max(int(k), 0)), np.int32)
+        check(self._lib.gsx_knn(self.h, len(pts), pts.ctypes.data, int(k), idx.ctypes.data), self.h)
+        return idx
+
+    def region_growing(self, points, k_normals=2000, k=10, residual_threshold=0.1, angle_threshold=0.05):
+        """The reference's run (region_growing.py:270-278).  Returns (labels int32 (n,), normals, residuals, n_regions);
+        label 0 is the largest region."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        labels = np.empty(len(pts), np.int32)
+        nrm = np.empty((len(pts), 3), np.float64)
+        res = np.empty(len(pts), np.float64)
+        nreg = C.c_int32(0)
+        check(self._lib.gsx_region_growing(self.h, len(pts), pts.ctypes.data, int(k_normals), int(k), float(residual_threshold),
+                                           float(angle_threshold), labels.ctypes.data, nrm.ctypes.data, res.ctypes.data,
+                                           C.byref(nreg)), self.h)
+        return labels, nrm, res, int(nreg.value)
+
     # -- exchange protocol v4 (see include/gsx.h) ------------------------------------------------------------------------
     def vote_num_views(self):
         return int(self._lib.gsx_vote_num_views(self.h))
@@ -587,3 +625,18 @@ def host_pack(seg_map, n_classes, tiled=True, coarse=True, threads=1, packed_u8=
     check(L.gsx_debug_host_pack(seg.ctypes.data, dt, w, h, n_classes, int(tiled), int(coarse), threads, out.ctypes.data, out.size,
                                 C.byref(nbytes), C.byref(coff), C.byref(bad)))
     return out, coff.value, bool(bad.value)
+
+
+def region_grow(normals, residuals, knn, residual_threshold=0.1, angle_threshold=0.05):
+    """segmentation_3D (3D_clustering/region_growing.py:166-226) on the host, no context: normals (n, 3), residuals (n,),
+    knn (n, k) neighbour lists in visiting order.  Returns (labels int32 (n,), n_regions); label 0 is the largest region."""
+    nrm = np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+    res = np.ascontiguousarray(residuals, np.float64).reshape(-1)
+    nb = np.ascontiguousarray(knn, np.int32)
+    if nb.ndim != 2 or len(nb) != len(nrm) or len(res) != len(nrm):
+        raise ValueError("normals (n, 3), residuals (n,) and knn (n, k) must agree in n")
+    labels = np.empty(len(nrm), np.int32)
+    nreg = C.c_int32(0)
+    check(_lib.lib().gsx_region_grow(len(nrm), nrm.ctypes.data, res.ctypes.data, nb.ctypes.data, nb.shape[1], float(residual_threshold),
+                                     float(angle_threshold), labels.ctypes.data, C.byref(nreg)))
+    return labels, int(nreg.value)

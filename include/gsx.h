@@ -547,6 +547,51 @@ int gsx_kmeans(gsx_ctx* ctx, int64_t n, const float* points, const float* colors
                int32_t* converged_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * region-growing labeler: 3D_clustering/region_growing.py ("rg.py"), the reference's geometry-only producer of a
+ * segmentation.  points: n x 3 float32, row-major, on the host (rg.py:270 reads them from the PLY;
+ * scipy's KD-tree widens them to float64, so distances are fp64 of the widened coordinates).
+ * Order among neighbours, where scipy leaves equidistant points unspecified: nearer first, then lower index.
+ * Option "nn_brute" (default 0): 1 = every query visits every point instead of a ring of grid cells, O(n^2): the
+ * same lists bit for bit; normals and residuals equal up to the order in which the moments are added (tests).
+ * ------------------------------------------------------------------------------------------- */
+/* compute_normals (rg.py:78-129) and compute_residuals (rg.py:132-163) in one pass: for every point the covariance
+ * of its k nearest points (itself included, as kd_tree.query includes it, rg.py:98), the eigenvector of the smallest
+ * eigenvalue, flipped when dot(normal, p - centroid) > 0 (rg.py:120-121), normalised (rg.py:126); residual =
+ * |dot(normal, p - centroid)| (rg.py:161).  All fp64 (the reference's float32 centroid, covariance and eigh are not
+ * reproduced; tests/test_region_growing_gpu.py holds the measured distance).  normals_out double[n][3],
+ * residuals_out double[n]; either may be NULL.  Where the two smallest eigenvalues coincide the normal is undefined
+ * in the reference too: a unit vector comes back, never NaN.  No neighbour list is stored, whatever k.
+ * GSX_E_INVALID: NULL points, n < 1, k < 3, k > n (the reference raises an IndexError), a non-finite coordinate. */
+int gsx_normals(gsx_ctx* ctx, int64_t n, const float* points, int64_t k, double* normals_out, double* residuals_out);
+/* test hook: the moments gsx_normals takes its normal from - moments_out double[n][9] = centroid x y z (the mean of the
+ * k nearest points, rg.py:103), then the upper triangle xx xy xz yy yz zz of centered^T centered (rg.py:109) */
+int gsx_debug_normals_moments(gsx_ctx* ctx, int64_t n, const float* points, int64_t k, double* moments_out);
+/* kd_tree.query(points[i], k)[1] for every i (rg.py:205): index_out int32[n][k], ascending distance (the point itself
+ * first unless a duplicate with a lower index precedes it).  2 <= k <= min(64, n).  index_out may be NULL: the lists
+ * stay on the device. */
+int gsx_knn(gsx_ctx* ctx, int64_t n, const float* points, int32_t k, int32_t* index_out);
+/* device pointer of the int32[n][k] lists of the last successful gsx_knn (NULL: none); valid until the next gsx_knn /
+ * gsx_region_growing on the ctx */
+void* gsx_knn_device(gsx_ctx* ctx);
+/* segmentation_3D (rg.py:166-226) on the host; needs no ctx and no GPU (errors: gsx_last_error(NULL)).
+ * normals double[n][3], residuals double[n], knn int32[n][k] (row i = the neighbours of i in visiting order).
+ * A region starts at the available point of smallest residual (rg.py:194; lowest index among equals) and grows
+ * through a FIFO front (rg.py:199-203): a neighbour still available is accepted iff |dot(normal[seed], normal[nb])| >
+ * cos(angle_threshold) (rg.py:209-211) and joins the front iff residual[nb] < residual_threshold (rg.py:216-218).
+ * labels_out[i] = rank of i's region by size, largest first, creation order among equal sizes (rg.py:224: Python's
+ * stable sort); *n_regions_out (may be NULL) = number of regions.  The reference only recolours f_dc per region
+ * (rg.py:229-245); the label is the form the other two labelers produce.
+ * GSX_E_INVALID: a NULL array, n < 1, k < 1, a NaN residual or threshold, a neighbour index outside [0, n) - and, as
+ * everywhere in this library (the C boundary maps std::bad_alloc so), running out of host memory; the text tells. */
+int gsx_region_grow(int64_t n, const double* normals, const double* residuals, const int32_t* knn, int32_t k,
+                    double residual_threshold, double angle_threshold, int32_t* labels_out, int32_t* n_regions_out);
+/* the reference's main (rg.py:270-278): gsx_normals with k_normals, gsx_knn with k, gsx_region_grow.
+ * normals_out, residuals_out, n_regions_out may be NULL. */
+int gsx_region_growing(gsx_ctx* ctx, int64_t n, const float* points, int64_t k_normals, int32_t k, double residual_threshold,
+                       double angle_threshold, int32_t* labels_out, double* normals_out, double* residuals_out,
+                       int32_t* n_regions_out);
+
+/* ---------------------------------------------------------------------------------------------
  * profiling hooks (HIP events on the ctx stream around each kernel launch)
  * ------------------------------------------------------------------------------------------- */
 int gsx_profile_enable(gsx_ctx* ctx, int on);

@@ -1,0 +1,245 @@
+"""GPU: exact k-NN, PCA normals and residuals (csrc/normals.hip) and the whole region-growing labeler against the reference's
+own results (tests/golden/region_growing.npz) and, at sizes the fixture cannot hold, against the numpy model
+(tests/region_growing_model.py).
+
+Bounds.  Against the reference: 2x the distance the fp64 model itself lies from the reference's float32 arithmetic,
+stored per scene by the fixture generator; the angle is signed except where the reference's flip-rule dot product (=
+its residual) is below 1e-6.  Against the model: 1e-9 rad on normals and 1e-9 of the model's residual on residuals, on
+the points whose eigen-gap (l1 - l0) / l2 exceeds 1e-3 (the test asserts that fewer than 1 % of the points are excluded).
+Measured (MI355X): worst angle 1.7e-14 rad, worst relative residual error 3.5e-10 (40 000 points, k = 2000).
+Moments (centroid, covariance of the k nearest): the GPU and the model add the same k terms in different orders; a sum
+of k terms carries at most (k - 1) u sum|x_i| of rounding error (u = 2^-53), so with S = the largest coordinate and R2
+= the largest squared neighbour distance of the query, |centroid difference| <= 4 k u S and |covariance difference|
+<= 8 k u k R2 per entry (both sides' bounds added, doubled for the subtraction k m m^T).  One wrong neighbour among k
+moves the centroid by about (spacing / k), ten orders above that.  Regions and neighbour lists are exact, no tolerance."""
+import importlib
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+import region_growing_model as model
+from conftest import GOLDEN, ROOT
+
+pytestmark = pytest.mark.gpu
+
+Z = np.load(os.path.join(GOLDEN, "region_growing.npz"))
+CASES = [str(c) for c in Z["cases"]]
+
+
+def case(name):
+    return {k.split("/", 1)[1]: Z[k] for k in Z.files if k.startswith(name + "/")}
+
+
+def angles(a, b, sign_free=None):
+    cosang = np.einsum("ij,ij->i", a, b)
+    if sign_free is not None:
+        cosang = np.where(sign_free, np.abs(cosang), cosang)
+    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=1), cosang)
+
+
+def check_against_model(pts, k, nrm, res, queries=None, what=""):
+    """normals / residuals of the GPU against the model on `queries` (default: all)"""
+    q = np.arange(len(pts)) if queries is None else queries
+    nbr, _ = model.knn(pts, k, q)
+    m_nrm, m_res, m_dot, gap = model.normals_from_neighbours(pts, nbr, q)
+    ok = gap > 1e-3
+    assert (~ok).mean() < 0.01, f"{what}: {(~ok).mean():.2%} of the points have a degenerate eigen-gap: not a scene for this test"
+    P = pts.astype(np.float64)
+    vnorm = np.linalg.norm(P[q] - P[nbr].mean(axis=1), axis=1)
+    ang = angles(nrm[q], m_nrm, sign_free=np.abs(m_dot) < 1e-12 * vnorm)
+    rel = np.abs(res[q] - m_res) / np.maximum(m_res, 1e-300)
+    print(f"{what}: GPU vs model over {ok.sum()} points: max angle {ang[ok].max():.3e} rad, max relative residual error {rel[ok].max():.3e}")
+    assert np.isfinite(nrm).all() and np.allclose(np.linalg.norm(nrm, axis=1), 1.0, atol=1e-12)
+    assert ang[ok].max() <= 1e-9 and rel[ok].max() <= 1e-9, what
+    return nbr
+
+
+def check_moments(ctx, pts, k, nbr, queries=None, what=""):
+    """the neighbour SET of a large k, through the centroid and the covariance gsx_normals forms (bounds: module docstring)"""
+    q = np.arange(len(pts)) if queries is None else queries
+    cen, cov = ctx.debug_normals_moments(pts, k)
+    m_cen, m_cov, r2 = model.moments(pts, nbr, q)
+    u, S = 2.0 ** -53, float(np.abs(pts).max())
+    dc = np.abs(cen[q] - m_cen).max(axis=1)
+    dv = np.abs(cov[q] - m_cov).max(axis=(1, 2))
+    print(f"{what}: moments: centroid off by {dc.max():.3e} (bound {4 * k * u * S:.3e}), covariance by {(dv / (k * r2)).max():.3e} of k R2 "
+          f"(bound {8 * k * u:.3e})")
+    assert dc.max() <= 4 * k * u * S and (dv <= 8 * k * u * k * r2).all(), what
+
+
+def check_lists(pts, nbr):
+    """every row of a k-NN result on its own: the point itself is there, (d2, index) ascends strictly"""
+    P = pts.astype(np.float64)
+    d = P[nbr] - P[:, None, :]
+    d2 = (d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2]
+    assert (nbr == np.arange(len(pts))[:, None]).any(axis=1).all()
+    step = np.diff(d2, axis=1)
+    assert ((step > 0) | ((step == 0) & (np.diff(nbr, axis=1) > 0))).all()
+    return d2
+
+
+def planes_and_blob(rng, n):
+    """tilted planar patches with noise plus a curved sheet: well-defined normals nearly everywhere"""
+    parts = []
+    m = n // 4
+    for j in range(3):
+        u = rng.normal(size=3)
+        v = rng.normal(size=3)
+        w = np.cross(u, v)
+        w /= np.linalg.norm(w)
+        u /= np.linalg.norm(u)
+        v = np.cross(w, u)
+        a = rng.uniform(-1, 1, (m, 2))
+        parts.append(rng.normal(size=3) * 2 + a[:, :1] * u + a[:, 1:] * v + rng.normal(0, 0.01, (m, 1)) * w)
+    a = rng.uniform(-1, 1, (n - 3 * m, 2))
+    parts.append(np.column_stack((a[:, 0] + 5, a[:, 1], 0.3 * np.sin(2 * a[:, 0]) + 0.2 * a[:, 1] ** 2 + rng.normal(0, 0.01, len(a)))))
+    pts = np.vstack(parts)
+    return np.ascontiguousarray(pts[rng.permutation(n)], np.float32)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_fixture_parity(ctx, name):
+    c = case(name)
+    pts, kn, k = c["points"], int(c["k_normals"]), int(c["k"])
+    rt, at = float(c["residual_threshold"]), float(c["angle_threshold"])
+    assert np.array_equal(ctx.knn(pts, k), c["knn"])
+    nrm, res = ctx.normals(pts, kn)
+    ang = angles(nrm, c["normals"], sign_free=c["residuals"] < 1e-6)
+    dres = np.abs(res - c["residuals"])
+    print(f"{name}: GPU vs reference: max angle {ang.max():.3e} rad (model: {float(c['tol_angle']):.3e}), max residual difference "
+          f"{dres.max():.3e} (model: {float(c['tol_residual']):.3e})")
+    assert ang.max() <= 2 * float(c["tol_angle"]) and dres.max() <= 2 * float(c["tol_residual"])
+    labels, nrm2, res2, nreg = ctx.region_growing(pts, k_normals=kn, k=k, residual_threshold=rt, angle_threshold=at)
+    assert np.array_equal(nrm2, nrm) and np.array_equal(res2, res)      # the chain is the three calls
+    assert nreg == int(c["n_regions"]) and model.same_regions(c["labels"], labels)
+    m_nbr = check_against_model(pts, kn, nrm, res, what=name)
+    check_moments(ctx, pts, kn, m_nbr, what=name)
+
+
+def test_model_40000_points_reference_default_k(ctx):
+    """k_normals = 2000, the reference's default (rg.py:272): far more neighbours than any list that could be stored"""
+    rng = np.random.default_rng(11)
+    pts = planes_and_blob(rng, 40000)
+    nrm, res = ctx.normals(pts, 2000)
+    m_nbr = check_against_model(pts, 2000, nrm, res, what="40000 points, k 2000")
+    check_moments(ctx, pts, 2000, m_nbr, what="40000 points, k 2000")
+    nbr = ctx.knn(pts, 10)
+    m_nbr, _ = model.knn(pts, 10)
+    assert np.array_equal(nbr, m_nbr)
+    labels, _, _, nreg = ctx.region_growing(pts, k_normals=2000, k=10, residual_threshold=0.1, angle_threshold=0.05)
+    want, wreg = model.grow(nrm, res, m_nbr, 0.1, 0.05)
+    assert nreg == wreg and np.array_equal(labels, want)
+
+
+def test_model_200000_points_k64(ctx):
+    """the model answers a random subset of the queries against all 200 000 points"""
+    rng = np.random.default_rng(12)
+    pts = planes_and_blob(rng, 200000)
+    q = np.sort(rng.choice(len(pts), 1500, replace=False))
+    nrm, res = ctx.normals(pts, 64)
+    m_nbr = check_against_model(pts, 64, nrm, res, queries=q, what="200000 points, k 64")
+    check_moments(ctx, pts, 64, m_nbr, queries=q, what="200000 points, k 64")
+    nbr = ctx.knn(pts, 64)
+    assert np.array_equal(nbr[q], m_nbr)
+    # every one of the 200 000 lists, not only the sampled ones: well-formed, and no point outside a list is nearer than
+    # the list's last entry for 5000 further queries checked against ALL points in fp64
+    d2 = check_lists(pts, nbr)
+    P = pts.astype(np.float64)
+    for i in rng.choice(len(pts), 5000, replace=False):
+        d = P - P[i]
+        assert np.count_nonzero((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2] <= d2[i, -1]) == 64, i
+    # the labels at this size check the host growth alone: the model grows from the GPU's own normals, residuals and lists
+    labels, _, _, nreg = ctx.region_growing(pts, k_normals=64, k=10, residual_threshold=0.1, angle_threshold=0.05)
+    want, wreg = model.grow(nrm, res, nbr[:, :10], 0.1, 0.05)      # the 10 nearest are the head of the 64 nearest
+    assert nreg == wreg and np.array_equal(labels, want)
+
+
+def grid_scenes():
+    rng = np.random.default_rng(13)
+    centres = rng.uniform(-50, 50, (12, 3))
+    clustered = (centres[rng.integers(0, 12, 6000)] + rng.normal(0, 0.05, (6000, 3))).astype(np.float32)
+    clustered[:40] = rng.uniform(-400, 400, (40, 3))                # outliers beyond the robust bounding box
+    dupes = rng.uniform(-1, 1, (5000, 3)).astype(np.float32)
+    dupes[2500:] = dupes[rng.integers(0, 300, 2500)]                # many copies of few positions: ties everywhere
+    one_cell = np.tile(np.float32([1.5, -2.0, 0.25]), (3000, 1))
+    flat = rng.uniform(-1, 1, (5000, 3)).astype(np.float32)
+    flat[:, 2] = 0.5                                                # zero extent along one axis
+    return [("clustered", clustered), ("duplicates", dupes), ("one_cell", one_cell), ("flat", flat)]
+
+
+@pytest.mark.parametrize("name,pts", grid_scenes(), ids=[s[0] for s in grid_scenes()])
+def test_grid_search_equals_brute_force(ctx, name, pts):
+    got = ctx.knn(pts, 64)
+    nrm, res = ctx.normals(pts, 500)
+    ctx.set_option("nn_brute", 1)
+    try:
+        brute = ctx.knn(pts, 64)
+        b_nrm, b_res = ctx.normals(pts, 500)
+    finally:
+        ctx.set_option("nn_brute", 0)
+    assert np.array_equal(got, brute), name                          # bit for bit
+    want, _ = model.knn(pts, 64)                                     # nearer first, then lower index
+    assert np.array_equal(got, want), name
+    assert np.isfinite(nrm).all() and np.allclose(np.linalg.norm(nrm, axis=1), 1.0, atol=1e-12)
+    # the same neighbour sets, added up in another order
+    _, _, _, gap = model.normals(pts, 500)
+    ok = gap > 1e-3
+    scale = float(np.abs(pts).max())
+    if ok.any():
+        assert angles(nrm, b_nrm, sign_free=res < 1e-12 * scale)[ok].max() <= 1e-9, name
+        assert np.abs(res - b_res)[ok].max() <= 1e-9 * scale, name
+
+
+def test_errors(ctx):
+    pts = np.random.default_rng(1).uniform(-1, 1, (50, 3)).astype(np.float32)
+    for k in (2, 51):
+        with pytest.raises(ValueError):
+            ctx.normals(pts, k)
+    for k in (1, 65):
+        with pytest.raises(ValueError):
+            ctx.knn(np.tile(pts, (2, 1)), k)
+    with pytest.raises(ValueError):
+        ctx.knn(pts[:5], 6)
+    for call in (lambda: ctx._lib.gsx_normals(ctx.h, 50, None, 5, None, None), lambda: ctx._lib.gsx_knn(ctx.h, 50, None, 5, None),
+                 lambda: ctx._lib.gsx_debug_normals_moments(ctx.h, 50, pts.ctypes.data, 5, None)):
+        assert call() == -1                                          # GSX_E_INVALID: NULL with a live context
+    bad = pts.copy()
+    bad[17, 1] = np.nan
+    with pytest.raises(ValueError, match="finite"):
+        ctx.normals(bad, 5)
+    bad[17, 1] = np.inf
+    with pytest.raises(ValueError, match="finite"):
+        ctx.knn(bad, 5)
+    assert ctx.knn(pts, 2).shape == (50, 2)
+    assert ctx._lib.gsx_knn_device(ctx.h)
+
+
+def test_cli_end_to_end(gsx, tmp_path):
+    c = case("patches")
+    pts = c["points"]
+    n = len(pts)
+    rng = np.random.default_rng(3)
+    cols = {"x": pts[:, 0].copy(), "y": pts[:, 1].copy(), "z": pts[:, 2].copy()}
+    for name in ("f_dc_0", "f_dc_1", "f_dc_2", "opacity"):
+        cols[name] = rng.normal(size=n).astype(np.float32)
+    src, dst, dst2 = (str(tmp_path / f) for f in ("in.ply", "out.ply", "out_recolor.ply"))
+    ply_io = importlib.import_module("3d_gaussian_splatting_project_amd.ply_io")
+    ply_io.write_vertex_ply(src, cols)
+    spec = importlib.util.spec_from_file_location("cli_region_growing", os.path.join(ROOT, "3D_clustering", "region_growing.py"))
+    cli = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cli)
+    args = ["--file_path", src, "--k_normals", str(int(c["k_normals"])), "--k", str(int(c["k"])), "--residual_threshold",
+            str(float(c["residual_threshold"])), "--angle_threshold", str(float(c["angle_threshold"]))]
+    cli.main(args + ["--save_path", dst])
+    out = ply_io.PlyData.read(dst)["vertex"]
+    assert out.properties == list(cols) + ["label"]
+    for name, col in cols.items():
+        assert np.array_equal(out[name], col), name
+    assert model.same_regions(c["labels"], out["label"])
+    cli.main(args + ["--save_path", dst2, "--recolor", "--seed", "4"])
+    out2 = ply_io.PlyData.read(dst2)["vertex"]
+    assert np.array_equal(out2["label"], out["label"]) and np.array_equal(out2["opacity"], cols["opacity"])
+    for r in range(3):                                               # one colour per region
+        assert len(np.unique(np.stack([out2[f"f_dc_{ch}"][out2["label"] == r] for ch in range(3)]), axis=1).T) == 1
