@@ -62,6 +62,7 @@ _SIGS = {
     "gsx_stream": (C.c_void_p, [C.c_void_p]),
     "gsx_synchronize": (C.c_int, [C.c_void_p]),
     "gsx_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "gsx_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     "gsx_upload_positions": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsx_upload_positions_strided": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                C.c_int64]),
@@ -109,6 +110,8 @@ _SIGS = {
     "gsx_vote_import_undo": (C.c_int, [C.c_void_p]),
     "gsx_vote_import_uniform": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_int64]),
+    "gsx_vote_map_stride": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "gsx_vote_views_match_uniform": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "gsx_vote_slab_labels": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "gsx_host_threads": (C.c_int, [C.c_void_p]),
     "gsx_default_host_threads": (C.c_int, []),

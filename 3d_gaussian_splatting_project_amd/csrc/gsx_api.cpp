@@ -238,6 +238,20 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
     return GSX_OK;
 }
 
+int gsx_get_option(gsx_ctx* ctx, const char* name, int64_t* value) {
+    CTX_OR_FAIL(ctx);
+    if (!name || !value) return gsx::fail(c, GSX_E_INVALID, "get_option: NULL argument");
+    const std::string k(name);
+    if (k == "early_vote") *value = c->opt_early_vote;
+    else if (k == "early_vote_at") *value = c->opt_early_at;
+    else if (k == "early_replay") *value = c->opt_early_replay ? 1 : 0;
+    else if (k == "seg_tiled") *value = c->opt_seg_tiled ? 1 : 0;
+    else if (k == "seg_coarse") *value = c->opt_seg_coarse ? 1 : 0;
+    else
+        return gsx::fail(c, GSX_E_INVALID, "get_option: option '%s' cannot be read back", name);
+    return GSX_OK;
+}
+
 int gsx_synchronize(gsx_ctx* ctx) {
     CTX_OR_FAIL(ctx);
     GSX_HIP(c, hipSetDevice(c->device));
@@ -496,6 +510,15 @@ int gsx_vote_import_uniform(gsx_ctx* ctx, int32_t n_parts, const int32_t* part_v
 int gsx_vote_import_undo(gsx_ctx* ctx) {
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::vote_import_undo(c); });
+}
+int gsx_vote_map_stride(gsx_ctx* ctx, int32_t seg_w, int32_t seg_h, int64_t* stride) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::vote_map_stride(c, seg_w, seg_h, stride); });
+}
+int gsx_vote_views_match_uniform(gsx_ctx* ctx, int32_t n, const gsx_camera* cams, int32_t seg_w, int32_t seg_h, int32_t img_w, int32_t img_h,
+                                 int32_t* match) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::vote_views_match_uniform(c, n, cams, seg_w, seg_h, img_w, img_h, match); });
 }
 int gsx_vote_slab_labels(gsx_ctx* ctx, int32_t slab, int32_t slabs, int64_t* slab_size) {
     CTX_OR_FAIL(ctx);

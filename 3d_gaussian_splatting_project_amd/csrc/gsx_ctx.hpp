@@ -335,6 +335,8 @@ int vote_import(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* p
 int vote_import_uniform(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* part_offsets, const gsx_camera* cams,
                         int seg_w, int seg_h, int img_w, int img_h, const void* pool_all_dev, int64_t pool_all_bytes);
 int vote_import_undo(Ctx* c);
+int vote_map_stride(Ctx* c, int seg_w, int seg_h, int64_t* stride);
+int vote_views_match_uniform(Ctx* c, int n, const gsx_camera* cams, int seg_w, int seg_h, int img_w, int img_h, int32_t* match);
 int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size);
 int host_threads(Ctx* c);
 int vote_flush_pending(Ctx* c);  // queue the DMA of packed host maps that are still waiting for their group to fill

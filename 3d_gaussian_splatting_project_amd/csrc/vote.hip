@@ -2984,6 +2984,49 @@ int vote_import(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* p
 // gsx_vote_view gives a map of that geometry under this context's options (all ranks run the same build with the same
 // options).  So the descriptors are derived here, the same way gsx_vote_view derives them (fill_view_desc + map_layout),
 // and the header exchange of the blobs and its host wait disappear from the protocol.
+static MapLayout uniform_layout(const Ctx* c, int seg_w, int seg_h) {
+    return map_layout(seg_w, seg_h, c->opt_seg_tiled != 0, c->opt_seg_coarse && c->bins <= 255);  // as view_prologue
+}
+// a staged view has the map geometry that (L, image size) derive: everything of a descriptor that does not come from the camera
+static bool same_geometry(const ViewDesc& d, const MapLayout& L, int img_w, int img_h) {
+    return d.seg_w == L.w && d.seg_h == L.h && d.wscale == (double)L.w / (double)img_w && d.hscale == (double)L.h / (double)img_h &&
+           d.seg_row_bytes == L.strip_bytes && d.coarse_row_bytes == L.cstrip_bytes && d.coarse_delta == (unsigned)L.coarse_off;
+}
+
+int vote_map_stride(Ctx* c, int seg_w, int seg_h, int64_t* stride) {
+    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_map_stride before vote_begin (the layout depends on the number of classes)");
+    if (!stride) return fail(c, GSX_E_INVALID, "vote_map_stride: NULL argument");
+    if (seg_w < 1 || seg_h < 1 || seg_w > 65535 || seg_h > 65535) return fail(c, GSX_E_INVALID, "vote_map_stride: map %dx%d", seg_w, seg_h);
+    const MapLayout L = uniform_layout(c, seg_w, seg_h);
+    *stride = (int64_t)((L.map_bytes + 255) / 256 * 256);
+    return GSX_OK;
+}
+
+// Are this context's own views exactly views [0, n) of a uniform run as gsx_vote_import_uniform would derive them: n of them, view i
+// from cams[i] with this map and image size, at byte i * stride of the pool?  A rank asks before it votes on a schedule that assumes so.
+int vote_views_match_uniform(Ctx* c, int n, const gsx_camera* cams, int seg_w, int seg_h, int img_w, int img_h, int32_t* match) {
+    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_views_match_uniform before vote_begin");
+    if (c->pool_base) return fail(c, GSX_E_STATE, "vote_views_match_uniform after gsx_vote_import: the context holds imported views");
+    if (n < 0 || (n > 0 && !cams) || !match) return fail(c, GSX_E_INVALID, "vote_views_match_uniform: bad arguments");
+    if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1 || seg_w > 65535 || seg_h > 65535)
+        return fail(c, GSX_E_INVALID, "vote_views_match_uniform: map %dx%d, image %dx%d", seg_w, seg_h, img_w, img_h);
+    const MapLayout L = uniform_layout(c, seg_w, seg_h);
+    const size_t stride = (L.map_bytes + 255) / 256 * 256;
+    *match = 0;
+    if ((size_t)n != c->views.size()) return GSX_OK;
+    for (int i = 0; i < n; ++i) {
+        ViewDesc d;
+        fill_view_desc(d, &cams[i], L.w, L.h, img_w, img_h);
+        d.seg_off = (long long)((size_t)i * stride);
+        d.seg_row_bytes = L.strip_bytes;
+        d.coarse_row_bytes = L.cstrip_bytes;
+        d.coarse_delta = (unsigned)L.coarse_off;
+        if (std::memcmp(&d, &c->views[(size_t)i], sizeof d) != 0) return GSX_OK;  // (fill_view_desc zeroes the padding)
+    }
+    *match = 1;
+    return GSX_OK;
+}
+
 int vote_import_uniform(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* part_offsets, const gsx_camera* cams,
                         int seg_w, int seg_h, int img_w, int img_h, const void* pool_all_dev, int64_t pool_all_bytes) {
     if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_import_uniform before vote_begin");
@@ -2998,8 +3041,22 @@ int vote_import_uniform(Ctx* c, int n_parts, const int32_t* part_views, const in
     }
     if (total > 65535) return fail(c, GSX_E_RANGE, "vote_import_uniform: %lld views exceed 65535", total);
     if (total > 0 && !cams) return fail(c, GSX_E_INVALID, "vote_import_uniform: cams is NULL");
-    const MapLayout L = map_layout(seg_w, seg_h, c->opt_seg_tiled != 0, c->opt_seg_coarse && c->bins <= 255);  // as view_prologue
+    const MapLayout L = uniform_layout(c, seg_w, seg_h);
     const size_t stride = (L.map_bytes + 255) / 256 * 256;
+    // the caller laid the parts out with a stride of its own: parts that overlap at THIS stride were sized for another geometry
+    std::vector<std::pair<unsigned long long, unsigned long long>> spans;  // (first byte, bytes) of the parts that hold views
+    for (int r = 0; r < n_parts; ++r)
+        if (part_views[r] > 0) spans.emplace_back((unsigned long long)part_offsets[r], (unsigned long long)part_views[r] * stride);
+    std::sort(spans.begin(), spans.end());
+    for (size_t s = 0; s + 1 < spans.size(); ++s)
+        if (spans[s].first + spans[s].second > spans[s + 1].first)
+            return fail(c, GSX_E_INVALID, "vote_import_uniform: the part offsets leave less than %llu bytes a view, the stride of a %dx%d map",
+                        (unsigned long long)stride, seg_w, seg_h);
+    // what this context staged itself is part of the run: its geometry must be the one the descriptors are derived for
+    for (const ViewDesc& o : c->pool_base ? c->own_views : c->views)
+        if (!same_geometry(o, L, img_w, img_h))
+            return fail(c, GSX_E_INVALID, "vote_import_uniform: map %dx%d / image %dx%d, but gsx_vote_view staged a %dx%d map (scales %g, %g)",
+                        seg_w, seg_h, img_w, img_h, o.seg_w, o.seg_h, o.wscale, o.hscale);
     std::vector<ViewDesc> all((size_t)total);
     size_t k = 0;
     for (int r = 0; r < n_parts; ++r)

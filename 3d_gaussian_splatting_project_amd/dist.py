@@ -48,11 +48,24 @@ class _GpuShard:
     def __init__(self, ctx):
         self.ctx = ctx
         self._ext = None
+        self._early_vote = None     # the caller's setting while this shard holds the option at 0
+        self.hold()
+
+    def hold(self):
+        """A rank of a multi-rank run never holds ALL views when it votes its own block: the early vote's result would always be
+        discarded (1.2 GB of planes and 1.6 ms of GPU work competing with the all-gather on rank 0, whose block starts at view 0).
+        So the option is 0 from here (before the hand-over: the constructor, GatherPipeline()) until the exchange has finished
+        (release(), called by every exchange_labels_* and by GatherPipeline.finish): a later single-GPU vote on the same context runs
+        with the caller's setting again.  A shard reused for a further non-pipelined exchange calls hold() before its hand-over."""
         world = dist.get_world_size() if dist.is_initialized() else 1
-        if _collectives_needed(world) and hasattr(ctx, "set_option"):
-            # a rank of a multi-rank run never holds ALL views when it votes its own block: the early vote's result would always be
-            # discarded (1.2 GB of planes and 1.6 ms of GPU work competing with the all-gather on rank 0, whose block starts at view 0)
-            ctx.set_option("early_vote", 0)
+        if self._early_vote is None and _collectives_needed(world) and hasattr(self.ctx, "set_option"):
+            self._early_vote = self.ctx.get_option("early_vote")
+            self.ctx.set_option("early_vote", 0)
+
+    def release(self):
+        if self._early_vote is not None:
+            self.ctx.set_option("early_vote", self._early_vote)
+            self._early_vote = None
 
     def stream(self):
         if self._ext is None:
@@ -105,6 +118,21 @@ def _into(out, labels):
     return out
 
 
+def _releases(fn):
+    """the shard's hold on the context's options (_GpuShard.hold) ends with the exchange, however it ends"""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(shard, *args, **kw):
+        try:
+            return fn(shard, *args, **kw)
+        finally:
+            if hasattr(shard, "release"):
+                shard.release()
+    return wrapped
+
+
+@_releases
 def exchange_labels(shard, group=None, to_host=True, out=None):
     """Steps 2-5 above.  `shard` is a GpuVoteShard (RCCL) or HostVoteShard (gloo)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -203,6 +231,7 @@ def _all_gather_into(full, part, group, async_op=False):
         dist.all_gather_into_tensor(full, part.contiguous(), group=group)
 
 
+@_releases
 def exchange_labels_a2a(shard, group=None, to_host=True, out=None):
     """Steps 2-4 of protocol v2.  `shard` is a GpuSlabShard (RCCL) or HostSlabShard (gloo)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -279,6 +308,7 @@ class HostSparseShard:
         return _into(out, self.shard.finish(all_labels.numpy()))
 
 
+@_releases
 def exchange_labels_sparse(shard, group=None, to_host=True, out=None):
     """Protocol v3.  `shard` is a GpuSparseShard (RCCL) or HostSparseShard (gloo)."""
     with _stream_of(shard):
@@ -336,7 +366,8 @@ class GpuGatherShard(_GpuShard):
         _, used, blobs = self.ctx.vote_export(0)
         h = np.zeros(_HDR + 256 * cap_views, np.uint8)
         h[:_HDR].view(np.int64)[:] = (len(blobs), used)
-        h[_HDR:_HDR + blobs.size] = blobs.reshape(-1)
+        k = min(len(blobs), int(cap_views))     # more views than the agreed bound: the count says so, and EVERY rank raises after the gather
+        h[_HDR:_HDR + 256 * k] = blobs[:k].reshape(-1)
         return torch.from_numpy(h).to(torch.device("cuda", self.ctx.device), non_blocking=False)
 
     def pool(self, chunk):
@@ -368,6 +399,29 @@ class GpuGatherShard(_GpuShard):
     def undo_import(self):
         self.ctx.vote_import_undo()
 
+    def map_stride(self, map_size):
+        """bytes per staged map of this size: a function of the size and the context's packing options alone"""
+        return self.ctx.vote_map_stride(map_size)
+
+    def own_cameras(self, cameras):
+        """this rank's block of the shared camera list, in the form views_match takes (built once, before the hand-over)"""
+        from .labeler import camera_array
+        return camera_array(cameras)
+
+    def views_match(self, own_cameras, map_size, image_size):
+        """did gsx_vote_view stage exactly what import_uniform will derive for this rank's views?  (no stream work)"""
+        return self.ctx.vote_views_match_uniform(own_cameras, map_size, image_size)
+
+    def slab_zeros(self, rank, world):
+        """a slab's worth of labels nobody will read: what a rank that cannot vote the agreed schedule puts into the labels gather"""
+        return torch.zeros(_slab_size(self.ctx.n, world), dtype=torch.int32, device=self.device())
+
+    def host_labels(self, n):
+        """the host buffer a pipelined run's labels land in before the flags are known (kept: no allocation per run)"""
+        if getattr(self, "_host_labels", None) is None or len(self._host_labels) != n:
+            self._host_labels = np.empty(n, np.int32)
+        return self._host_labels
+
     def event(self):
         """a timing event recorded on the ctx stream (torch's current stream must be the ctx stream: `with shard.stream()`)"""
         e = torch.cuda.Event(enable_timing=True)
@@ -393,16 +447,20 @@ class HostGatherShard:
 
     def __init__(self, shard):
         self.shard = shard
+        self._strides = {}
 
     def header(self, cap_views):
         blobs, used = self.shard.export()
         h = np.zeros(_HDR + 256 * cap_views, np.uint8)
         h[:_HDR].view(np.int64)[:] = (len(blobs), used)
-        h[_HDR:_HDR + blobs.size] = blobs.reshape(-1)
+        k = min(len(blobs), int(cap_views))     # more views than the agreed bound: the count says so, and EVERY rank raises after the gather
+        h[_HDR:_HDR + 256 * k] = blobs[:k].reshape(-1)
         return torch.from_numpy(h)
 
     def pool(self, chunk):
-        return torch.from_numpy(self.shard.pool(chunk))
+        """the first `chunk` bytes of the pool, grown to that size (as the device pool after gsx_vote_export(chunk): a pool that
+        holds more than the caller's schedule assumed is not an error here, the schedule's own checks have to see it)"""
+        return torch.from_numpy(self.shard.pool(max(int(chunk), self.shard.staged()[1])))[:chunk]
 
     def pool_all(self, nbytes):
         return torch.empty(nbytes, dtype=torch.uint8)
@@ -425,6 +483,45 @@ class HostGatherShard:
     def undo_import(self):
         self.shard.views = None
 
+    def map_stride(self, map_size):
+        """gsx_vote_map_stride without a context: the library's own host packer (gsx_debug_host_pack, no GPU needed) lays out a
+        map of this size under the default options"""
+        from .labeler import host_pack
+        w, h = int(map_size[0]), int(map_size[1])
+        if w < 1 or h < 1:
+            raise ValueError(f"map_stride: map {w}x{h}")
+        if (w, h) not in self._strides:
+            self._strides[(w, h)] = (len(host_pack(np.zeros((h, w), np.int32), self.shard.n_classes, threads=1)[0]) + 255) // 256 * 256
+        return self._strides[(w, h)]
+
+    def own_cameras(self, cameras):
+        return list(cameras)
+
+    def views_match(self, own_cameras, map_size, image_size):
+        """gsx_vote_views_match_uniform on the stand-in's blobs (oracle.NumpyGatherShard: 24 float64 = camera, map and image
+        size, pool offset): this rank's own views are exactly `own_cameras` with maps of map_size for images of image_size, view
+        i at byte i * stride of its pool"""
+        blobs, _ = self.shard.export()
+        if len(own_cameras) != len(blobs):
+            return False
+        stride = self.map_stride(map_size)
+        for i, (cam, blob) in enumerate(zip(own_cameras, blobs)):
+            want = np.zeros(32, np.float64)
+            want[:2] = cam["fx"], cam["fy"]
+            want[2:4] = cam["width"], cam["height"]
+            want[4:13] = np.asarray(cam["rotation"], np.float64).reshape(-1)
+            want[13:16] = cam["position"]
+            want[16:21] = int(map_size[0]), int(map_size[1]), int(image_size[0]), int(image_size[1]), i * stride
+            if not np.array_equal(np.ascontiguousarray(blob).view(np.float64), want):
+                return False
+        return True
+
+    def slab_zeros(self, rank, world):
+        return torch.zeros(_slab_size(self.shard.n, world), dtype=torch.int32)
+
+    def host_labels(self, n):
+        return np.empty(n, np.int32)
+
     def slab_labels(self, rank, world):
         return torch.from_numpy(self.shard.slab_labels(rank, world))
 
@@ -435,6 +532,7 @@ class HostGatherShard:
         return _into(out, self.shard.finish(all_labels.numpy()))
 
 
+@_releases
 def exchange_labels_gather(shard, group=None, to_host=True, out=None, cap_views=None):
     """Protocol v4.  `shard` is a GpuGatherShard (RCCL) or HostGatherShard (gloo).  cap_views: an upper bound on the
     views of any one rank that all ranks agree on (default: 1024); sizes the header exchange."""
@@ -476,6 +574,11 @@ def exchange_labels_gather(shard, group=None, to_host=True, out=None, cap_views=
         return shard.finish(full, to_host, out=out)
 
 
+def _slab_size(n, world):
+    """Gaussians per rank in protocol v4 (gsx_vote_slab_labels): ceil(n / world) rounded up to 256, at least 256"""
+    return ((int(n) + world - 1) // world + 255) // 256 * 256 or 256
+
+
 def chunk_bounds(n_max, chunks):
     """Cut points 0 = b_0 < b_1 < .. < b_C = n_max of the ranks' view blocks (a function of (n_max, chunks) alone: every rank
     derives the same).  Balanced chunks and a SHORT last one (an eighth of the block, at least one view): the last chunk's
@@ -508,9 +611,14 @@ class GatherPipeline:
       * cameras + map_size given (round 3; a capture from ONE camera model, which is what a cameras.json describes): every rank
         derives every view's descriptor itself (gsx_vote_import_uniform) - no header exchange, no host wait anywhere between the
         first vote_view and the labels.  Collectives: C chunk all_gathers, one 4-byte flag all_gather nobody waits for until
-        the labels are there, the labels all_gather.  A rank whose own pool is not what the schedule assumes (fewer views than
-        its share, a map of another geometry) raises its flag; every rank sees the flags next to the labels and all fall back
-        to the plain gather together.
+        the labels are there, the labels all_gather - ALWAYS these, with sizes from (total_views, world, chunks, map_size) and the
+        packing options alone (gsx_vote_map_stride), never from what a rank staged.  A rank whose own views are not what the
+        schedule assumes (fewer views than its share, a map of another geometry or scale, another camera: gsx_vote_views_match_uniform)
+        still joins every collective - its chunks carry whatever lies in a buffer of the agreed size, its labels are zeros - and
+        lowers its flag; every rank sees the flags next to the labels and all fall back to the plain gather together.  `out` is
+        written only once the flags are known to be all 1 (or by the fallback): a finish() that raises leaves it alone.
+        (When view_range leaves a rank without views, one 8-byte all_gather of the derived strides comes first; ranks that derived
+        different strides - builds or options that differ - raise the same ValueError everywhere.)
       * otherwise (round 2): one agreement all_gather of the ranks' map strides (skipped with assume_uniform), the chunk
         all_gathers, a header all_gather carrying the view blobs (the host waits for it), the labels all_gather; mixed
         geometries fall back to the plain gather of exchange_labels_gather.
@@ -541,10 +649,28 @@ class GatherPipeline:
         self.timing = bool(timing)
         self.phases_ms = None
         self._t_first = self._t_last = None
+        self.fell_back = False   # finish() ended in the plain gather
+        if hasattr(shard, "hold"):
+            shard.hold()         # (a shard that an earlier exchange has released)
+        if self.local_views and self.active:
+            lo, hi = view_range(self.total, self.rank, self.world)
+            self.own_cameras = shard.own_cameras(cameras[lo:hi])
 
     # -- agreement on the map stride: the first collective of every rank -------------------------------------------------
     def _agree(self):
         nv, used = self.shard.staged()
+        if self.local_views:
+            # the stride every rank derives from map_size and the packing options: what a rank staged has no say in any size
+            self.stride = int(self.shard.map_stride(self.map_size))
+            if min(self.n) < 1:
+                dev = self.shard.device()
+                alls = torch.empty(self.world, dtype=torch.int64, device=dev)
+                _all_gather_into(alls, torch.tensor([self.stride], dtype=torch.int64, device=dev), self.group)
+                vals = [int(v) for v in alls.cpu().tolist()]
+                if len(set(vals)) != 1:
+                    raise ValueError(f"GatherPipeline: the ranks derive different map strides {vals} for maps of {tuple(self.map_size)}")
+            self._reserve()
+            return
         mine = used // nv if nv and used % nv == 0 else (-1 if nv == 0 else 0)   # -1: no view yet (no opinion); 0: irregular
         if self.assume_uniform and min(self.n) >= 1:
             if not nv:  # the peers are about to join chunk collectives this rank cannot size: fail loudly, not silently out of step
@@ -559,10 +685,13 @@ class GatherPipeline:
             have = [v for v in vals if v >= 0]
             self.stride = have[0] if have and all(v == have[0] and v > 0 and v % 256 == 0 for v in have) else 0
         if self.stride:
-            with _stream_of(self.shard):
-                need = self.bounds[-1] * self.stride
-                self.pool_src = self.shard.pool(need)                     # reserves: chunk j reads (b_j+1 - b_j) * stride bytes
-                self.pool_all = self.shard.pool_all(self.world * need)
+            self._reserve()
+
+    def _reserve(self):
+        with _stream_of(self.shard):
+            need = self.bounds[-1] * self.stride
+            self.pool_src = self.shard.pool(need)                     # reserves: chunk j reads (b_j+1 - b_j) * stride bytes
+            self.pool_all = self.shard.pool_all(self.world * need)
 
     def _chunk_at(self, j):
         """byte offset of chunk j's region in the gathered buffer, bytes per rank in it"""
@@ -571,8 +700,10 @@ class GatherPipeline:
     def _issue(self, j):
         if self.stride:
             at, cb = self._chunk_at(j)
-            self.shard.flush()
             with _stream_of(self.shard):
+                # queues the staged maps' DMA (as flush()) and asks for the pool again: maps larger than map_size promised may have
+                # moved it since _reserve (the rank will lower its flag; it must not hand a freed pool to the gather before that)
+                self.pool_src = self.shard.pool(self.bounds[-1] * self.stride)
                 w = _all_gather_into(self.pool_all[at:at + self.world * cb], self.pool_src[self.bounds[j] * self.stride:self.bounds[j] * self.stride + cb],
                                      self.group, async_op=True)
             if w is not None:
@@ -612,10 +743,22 @@ class GatherPipeline:
             events.append((name, self.shard.event()))
 
     def finish(self, to_host=True, out=None):
-        import time
-        shard, world, rank = self.shard, self.world, self.rank
+        shard = self.shard
         if not self.active:
             return exchange_labels_gather(shard, self.group, to_host, out, cap_views=max(1, self.total))
+        try:
+            return self._finish(to_host, out)
+        finally:
+            if hasattr(shard, "release"):
+                shard.release()
+
+    def _fallback(self, to_host, out):
+        self.fell_back = True
+        return exchange_labels_gather(self.shard, self.group, to_host, out, cap_views=max(1, self.total))
+
+    def _finish(self, to_host, out):
+        import time
+        shard, world, rank = self.shard, self.world, self.rank
         t_fin = time.perf_counter()
         if self.stride is None:
             self._agree()                                   # a rank without views gets here first
@@ -626,6 +769,8 @@ class GatherPipeline:
         events = []
         self._mark(events, "start")
         if self.local_views:
+            # ... and what this rank staged is what every rank is about to derive for its views
+            regular = regular and bool(shard.views_match(self.own_cameras, self.map_size, self.image_size))
             return self._finish_local(regular, events, t_fin, to_host, out)
         # header: counts, bytes, blobs - and whether my pool is what the chunk schedule assumed
         cap = max(1, max(self.n))
@@ -643,7 +788,7 @@ class GatherPipeline:
                 w.wait()
         self.works = []
         if not ok:                                          # every rank sees the same flags: all take the plain path together
-            return exchange_labels_gather(shard, self.group, to_host, out, cap_views=max(1, self.total))
+            return self._fallback(to_host, out)
         blobs = np.concatenate([heads[r, _HDR:_HDR + 256 * int(part_views[r])] for r in range(world)])
         pv, po = self._parts(relative=True)
         with _stream_of(shard):
@@ -671,24 +816,31 @@ class GatherPipeline:
             self.works = []
             self._mark(events, "gathers")
             res = None
-            if self.stride:
+            if regular:
                 pv, po = self._parts(relative=False)
                 shard.import_uniform(pv, po, self.cameras, self.map_size, self.image_size,
                                      self.pool_all[:world * self.bounds[-1] * self.stride])
                 slab = shard.slab_labels(rank, world)
-                self._mark(events, "vote")
-                full = shard.labels_all(slab.numel() * world)
-                _all_gather_into(full, slab, self.group)
-                self._mark(events, "labels")
-                res = shard.finish(full, to_host, out=out)   # the host waits here (labels D2H), for the first time in the run
+            else:                                           # this rank knows the run will fall back: it votes nothing, but the
+                slab = shard.slab_zeros(rank, world)        # peers' labels gather needs its part
+            self._mark(events, "vote")
+            full = shard.labels_all(slab.numel() * world)
+            _all_gather_into(full, slab, self.group)
+            self._mark(events, "labels")
+            if regular:
+                # into a buffer of the shard's, not the caller's: a peer's flag may still say that these labels mean nothing
+                mine = shard.host_labels(len(out)) if to_host and out is not None else None
+                res = shard.finish(full, to_host, out=mine)  # the host waits here (labels D2H), for the first time in the run
         if fw is not None:
             fw.wait()
-        ok = bool(self.stride) and bool(flags.cpu().numpy().all())
-        if not ok:                                          # every rank sees the same flags: all take the plain path together
-            if self.stride:
+        if not bool(flags.cpu().numpy().all()):             # every rank sees the same flags: all take the plain path together
+            if regular:
                 shard.undo_import()                         # ... from their own views again
-            return exchange_labels_gather(shard, self.group, to_host, out, cap_views=max(1, self.total))
+            return self._fallback(to_host, out)
         self._phases(events, t_fin)
+        if to_host and out is not None:
+            out[...] = res
+            return out
         return res
 
     def _phases(self, events, t_fin):

@@ -68,6 +68,12 @@ class Context:
         """Tuning knobs of gsx_set_option (spatial_sort, xcd_swizzle, vote_unroll); never change results."""
         check(self._lib.gsx_set_option(self.h, name.encode(), int(value)), self.h)
 
+    def get_option(self, name):
+        """gsx_get_option: the current value of an option that can be read back (early_vote, ...)."""
+        out = C.c_int64(0)
+        check(self._lib.gsx_get_option(self.h, name.encode(), C.byref(out)), self.h)
+        return int(out.value)
+
     # -- scene ---------------------------------------------------------------------------------
     def upload_positions(self, positions):
         """positions: (N,3) float array, or a structured array with a 'position' field
@@ -361,6 +367,21 @@ class Context:
 
     def vote_import_undo(self):
         check(self._lib.gsx_vote_import_undo(self.h), self.h)
+
+    def vote_map_stride(self, map_size):
+        """gsx_vote_map_stride: bytes from one staged map of map_size = (width, height) to the next (after vote_begin)."""
+        out = C.c_int64(0)
+        check(self._lib.gsx_vote_map_stride(self.h, int(map_size[0]), int(map_size[1]), C.byref(out)), self.h)
+        return int(out.value)
+
+    def vote_views_match_uniform(self, cams, map_size, image_size):
+        """gsx_vote_views_match_uniform: are this context's own views exactly the views of `cams` (in order) with this map and
+        image size, as vote_import_uniform would derive them?"""
+        arr = cams if isinstance(cams, C.Array) else camera_array(cams)
+        out = C.c_int32(0)
+        check(self._lib.gsx_vote_views_match_uniform(self.h, len(arr), C.addressof(arr) if len(arr) else None, int(map_size[0]),
+                                                     int(map_size[1]), int(image_size[0]), int(image_size[1]), C.byref(out)), self.h)
+        return bool(out.value)
 
     def vote_slab_labels(self, slab, slabs):
         """-> slab size S; the slab's labels (Morton order) are the first S words at keys_device()."""

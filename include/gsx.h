@@ -173,6 +173,9 @@ int gsx_synchronize(gsx_ctx* ctx);
  *                               lines per view instead of ~16 (HBM traffic per launch 5.2 GB -> 0.5 GB).  Needs
  *                               n_classes <= 254, unit scale and "seg_tiled"; otherwise the one-level path runs */
 int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value);
+/* the current value of an option that other code overrides for a while and has to put back: "early_vote", "early_vote_at",
+ * "early_replay", "seg_tiled", "seg_coarse"; GSX_E_INVALID for any other name */
+int gsx_get_option(gsx_ctx* ctx, const char* name, int64_t* value);
 
 /* ---------------------------------------------------------------------------------------------
  * scene upload — replaces load_gaussians (dls.py:25-40), which keeps only x,y,z
@@ -331,9 +334,24 @@ int gsx_vote_import(gsx_ctx* ctx, int32_t n_parts, const int32_t* part_views, co
  * camera model), without the blobs: every rank holds the whole camera list (load_cameras, dls.py:17-22) and derives the
  * descriptors itself, exactly as gsx_vote_view does - cams[k] is the camera of global view k (part order), view v of part r
  * lies at part_offsets[r] + v * (the pool stride gsx_vote_view gives a map of this geometry under this context's options:
- * all ranks must run the same build with the same options).  No exchange of view blobs is needed then. */
+ * all ranks must run the same build with the same options).  No exchange of view blobs is needed then.
+ * GSX_E_INVALID, and nothing imported, when the sizes cannot be those of the run: a view of a part would end outside the pool
+ * or inside the next part (the caller laid the parts out with another stride than gsx_vote_map_stride(seg_w, seg_h)), or a view
+ * this context staged itself has another map size, scale (seg / img), strip size or coarse offset than the derived descriptors
+ * (a swapped (h, w), a map_size of another resolution, a wrong image size). */
 int gsx_vote_import_uniform(gsx_ctx* ctx, int32_t n_parts, const int32_t* part_views, const int64_t* part_offsets, const gsx_camera* cams,
                             int32_t seg_w, int32_t seg_h, int32_t img_w, int32_t img_h, const void* pool_all_dev, int64_t pool_all_bytes);
+/* *stride = bytes from one staged map to the next in the pool for maps of seg_w x seg_h under this context's options and class
+ * count (after gsx_vote_begin): the packed size (u8 strips of 16 columns, rows padded to 8, + the 4x4-coarsened level; one byte
+ * per pixel stands for the int labels of logits.argmax, dls.py:142) rounded up to 256.  What gsx_vote_view advances by and
+ * gsx_vote_import_uniform steps by: a multi-rank run sizes its all-gathers from this, never from a rank's own pool. */
+int gsx_vote_map_stride(gsx_ctx* ctx, int32_t seg_w, int32_t seg_h, int64_t* stride);
+/* *match = 1 when the views this context staged itself are exactly n views of a uniform run as gsx_vote_import_uniform derives
+ * them - n of them, view i from cams[i] (camera frame, dls.py:60-66, and seg / img scales, dls.py:267-271) with a seg_w x seg_h
+ * map of img_w x img_h images, at byte i * gsx_vote_map_stride of the pool - else 0.  A rank of a run without header exchange asks
+ * before it trusts a schedule built on (cameras, map size, image size) alone.  GSX_E_STATE while imported views are in place. */
+int gsx_vote_views_match_uniform(gsx_ctx* ctx, int32_t n, const gsx_camera* cams, int32_t seg_w, int32_t seg_h, int32_t img_w,
+                                 int32_t img_h, int32_t* match);
 /* takes the last gsx_vote_import / gsx_vote_import_uniform back: the context holds this rank's own views in its own pool again
  * (a protocol that imports before it knows whether every rank's pool was what the schedule assumed can fall back) */
 int gsx_vote_import_undo(gsx_ctx* ctx);

@@ -436,6 +436,16 @@ def pack_map_numpy(seg, n_classes):
     return out, coarse_off
 
 
+def map_stride_numpy(w, h):
+    """bytes from one staged map of w x h to the next in a pool: the size of pack_map_numpy's form (both levels), rounded up to
+    256 (the library's gsx_vote_map_stride under its default options, <= 254 classes)"""
+    w, h = int(w), int(h)
+    fine_bytes = (h + 7) // 8 * 128 * ((w + 15) // 16)
+    cw, ch = (w + 3) // 4, (h + 3) // 4
+    coarse_bytes = (ch + 7) // 8 * 128 * ((cw + 15) // 16)
+    return ((fine_bytes + 255) // 256 * 256 + coarse_bytes + 255) // 256 * 256
+
+
 def expand_compact_numpy(rec, w, h, table_bytes, stream_off):
     """The pool form of a map from its COMPACT transfer form (csrc/host_pack.hpp; what seg_expand_kernel does on the GPU),
     restated in numpy: -> bytes equal to pack_map_numpy(seg)[0]."""
@@ -538,13 +548,22 @@ class NumpyGatherShard:
         """the views from the shared camera list and ONE map geometry (dist.GatherPipeline with cameras=...): view v of part r
         lies at part_offsets[r] + v * stride of the gathered pool"""
         w, h = int(map_size[0]), int(map_size[1])
-        stride = (pack_map_numpy(np.zeros((h, w), np.int32), self.n_classes)[0].size + 255) // 256 * 256
+        stride = self.map_stride(map_size)
+        spans = sorted((int(o), int(nv) * stride) for o, nv in zip(part_offsets, part_views) if int(nv) > 0)
+        if any(a + n > b for (a, n), (b, _) in zip(spans, spans[1:])) or (spans and spans[-1][0] + spans[-1][1] > len(pool_all)):
+            raise ValueError(f"import_uniform: the part offsets leave less than {stride} bytes a view, the stride of a {w}x{h} map")
         self.views, k = [], 0
         for r, nv in enumerate(part_views):
             for v in range(int(nv)):
                 seg = unpack_map_numpy(pool_all[int(part_offsets[r]) + v * stride:], w, h)
                 self.views.append((cameras[k], seg, (int(image_size[0]), int(image_size[1]))))
                 k += 1
+
+    def map_stride(self, map_size):
+        """gsx_vote_map_stride: a function of the map size alone (default packing options)"""
+        if min(int(map_size[0]), int(map_size[1])) < 1:
+            raise ValueError(f"map_stride: map {tuple(map_size)}")
+        return map_stride_numpy(map_size[0], map_size[1])
 
     def slab_labels(self, rank, world):
         sn = ((self.n + world - 1) // world + 255) // 256 * 256 or 256

@@ -820,6 +820,38 @@ def test_import_uniform_and_undo(gsx):
         with pytest.raises(ValueError):
             c.vote_import_uniform([V], [0], cams, (0, H), (W, H), pool.data_ptr(), pool.numel())
         assert np.array_equal(c.vote_finalize(), want)                        # failed imports left the context alone
+        # sizes that are not those of the staged views are REPORTED, by the own-view check a rank of a multi-rank run asks before
+        # it votes (-> lowered flag) and by the import itself (GSX_E_INVALID): a swapped (H, W) on this non-square map, a map_size
+        # of another resolution, a wrong image size; parts laid out with another stride than the map's; another camera order
+        assert c.vote_map_stride((W, H)) == stride == c.vote_pool_bytes() // c.vote_num_views()
+        assert c.vote_views_match_uniform(cams, (W, H), (W, H))
+        for map_size, image_size in (((H, W), (H, W)), ((H, W), (W, H)), ((W // 2, H // 2), (W, H)), ((W, H), (2 * W, 2 * H)), ((W, H), (H, W))):
+            assert not c.vote_views_match_uniform(cams, map_size, image_size), (map_size, image_size)
+            with pytest.raises(ValueError):
+                c.vote_import_uniform([V], [0], cams, map_size, image_size, pool.data_ptr(), pool.numel())
+        assert not c.vote_views_match_uniform(cams[::-1], (W, H), (W, H)) and not c.vote_views_match_uniform(cams[:-1], (W, H), (W, H))
+        with pytest.raises(ValueError):
+            c.vote_import_uniform([3, 4], [0, 2 * stride], cams, (W, H), (W, H), pool.data_ptr(), pool.numel())   # part 0 runs into part 1
+        c.vote_import_uniform([V], [0], cams, (W, H), (W, H), pool.data_ptr(), pool.numel())
+        with pytest.raises(gsx.GsxError):
+            c.vote_views_match_uniform(cams, (W, H), (W, H))                  # imported views are in place: not the rank's own
+        c.vote_import_undo()
+        assert c.vote_views_match_uniform(cams, (W, H), (W, H)) and np.array_equal(c.vote_finalize(), want)
+    # gsx_vote_map_stride is what gsx_vote_view advances the pool by, for every layout the library has: two levels, one level
+    # (no coarse level; 256 bins leave no byte value for "mixed"), row-major maps; sizes that are no multiples of the tiles
+    for opts, n_classes in (({}, 150), ({"seg_coarse": 0}, 150), ({"seg_tiled": 0}, 150), ({}, 255)):
+        with gsx.Context(0) as c:
+            for k, v in opts.items():
+                c.set_option(k, v)
+            c.upload_positions(pos[:1000])
+            for w, h in ((320, 180), (180, 320), (200, 120), (100, 100), (33, 7), (16, 8), (1, 1)):
+                c.vote_begin(n_classes, 0, 3)
+                cam = dict(cams[0], width=w, height=h)
+                for _ in range(3):
+                    c.vote_view(cam, np.zeros((h, w), np.int32), (w, h))
+                assert c.vote_map_stride((w, h)) == c.vote_pool_bytes() // c.vote_num_views(), (opts, n_classes, w, h)
+                assert c.vote_pool_bytes() == 3 * c.vote_map_stride((w, h)) and c.vote_views_match_uniform([cam] * 3, (w, h), (w, h))
+                assert not c.vote_views_match_uniform([cam] * 3, (h, w), (w, h)) or w == h
 
 
 def test_seg_dtypes_and_device_maps(ctx):
@@ -1290,6 +1322,7 @@ for name, shard_cls, fn, a2a in (("gather", pkg.dist.GpuGatherShard, pkg.dist.ex
     ctx.close()
 # the pipelined gather: chunk all_gathers issued (async) between the hand-over calls, on the ctx stream
 ctx = pkg.Context(0)
+early_vote_before = ctx.get_option("early_vote")
 ctx.upload_positions(pos)
 for rep, chunks in enumerate((4, 1, 9, 3)):
     ctx.vote_begin(12, 0, V)
@@ -1320,6 +1353,7 @@ for cam, seg in zip(cams[:-1], segs[:-1]):                      # one view short
     ctx.vote_view(cam, seg)
     pipe.after_view()
 ok["local_short_rank_falls_back"] = bool(np.array_equal(pipe.finish(), oracle.assign_labels(pos, cams[:-1], segs[:-1], [(W, H)] * (V - 1), threads=0)))
+ok["early_vote_restored"] = ctx.get_option("early_vote") == early_vote_before      # the shards held it at 0 during their exchanges only
 # ... and its fallback when the maps are not of one geometry
 ctx.vote_begin(12, 0, V)
 pipe = pkg.dist.GatherPipeline(pkg.dist.GpuGatherShard(ctx), V)
