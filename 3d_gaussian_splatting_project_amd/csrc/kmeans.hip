@@ -6,7 +6,8 @@
 //            evaluates exactly that, without FMA (this file is compiled with -ffp-contract=off), for all k
 //            centroids (held in LDS as doubles) and keeps the first minimum.
 //   update   (k_means.py:125-128)  numpy's float32 mean over axis 0 adds the member rows IN INDEX ORDER into a float32
-//            accumulator.  Floating-point addition does not reassociate, so the sum is made the same way: a stable
+//            accumulator that starts at +0.0 (so a column of -0.0 members has the mean +0.0, also for one member).
+//            Floating-point addition does not reassociate, so the sum is made the same way: a stable
 //            radix sort of the row indices by label puts every cluster's members in index order, and one wave per
 //            workgroup per cluster adds them one after the other (fifteen waves stage the rows through a transposed
 //            LDS ring, six lanes - one per dimension - do the adds, four members per LDS read).  The division by float32(count) and the convergence test (:132-136) run on
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kKmBlock) void kmeans_assign_kernel(const float* __
         if (lc[t]) atomicAdd(&counts[t], lc[t]);
 }
 
-// One workgroup per cluster: sums[c][d] = ((row[o0][d] + row[o1][d]) + row[o2][d]) + ... in float32, members in
+// One workgroup per cluster: sums[c][d] = (((+0.0 + row[o0][d]) + row[o1][d]) + row[o2][d]) + ... in float32, members in
 // index order.  The chain of additions is serial by definition (it is the kernel's floor: one dependent v_add_f32 per
 // member), so everything else is kept out of its way: waves 1..15 fetch the next kSumRows member rows into one half of
 // an LDS ring, TRANSPOSED to [dimension][row], while lanes 0..5 of wave 0 (one per dimension) add the previous kSumRows
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(kSumThreads) void kmeans_sum_kernel(const float* __
     const int c = blockIdx.x, tid = threadIdx.x;
     const uint32_t beg = offsets[c], end = offsets[c + 1];
     float acc = 0.0f;
-    bool first = true;  // numpy's reduction starts FROM the first row, not from +0.0 (the sign of a zero sum)
+    bool first = true;  // numpy's axis-0 reduction starts from +0.0 and adds the first row to it: members that are all -0.0 sum to +0.0
     auto load = [&](uint32_t t0, int buf) {  // loader waves only
         if (tid < 64) return;
         float* sb = stage + (size_t)buf * 6 * kSumRows;
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(kSumThreads) void kmeans_sum_kernel(const float* __
             const int m = (int)min((uint32_t)kSumRows, end - t0);
             int j = 0;
             if (first && m > 0) {
-                acc = col[0];
+                acc = 0.0f + col[0];  // (+0.0) + (-0.0) = +0.0; every other value is unchanged
                 first = false;
                 j = 1;
             }

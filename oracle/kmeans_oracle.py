@@ -9,8 +9,8 @@ What the reference computes, line by line:
             dimensions, no FMA); the smallest wins.  Restated as an arg-min (first minimum).  Exact ties between two
             centroids are broken by the tree's traversal order in the reference: parity on such inputs is unpinned.
   :125-128  new centroid = float32 mean of the member rows: numpy reduces axis 0 of an (M, 6) float32 array by adding
-            the rows IN ORDER into a float32 accumulator, then divides by float32(M); an empty cluster keeps its
-            centroid
+            the rows IN ORDER into a float32 accumulator that starts at +0.0 (a column whose members are all -0.0 has
+            the mean +0.0, for M = 1 too), then divides by float32(M); an empty cluster keeps its centroid
   :132-136  stop when the float32 Frobenius norm of the centroid change is < tol (numpy computes it through BLAS
             sdot; the oracle calls numpy's own norm, so it takes the same decision) - before adopting the new centroids
   :138      otherwise adopt them and iterate, at most max_iter times
@@ -32,7 +32,12 @@ def sq_distances(data32, centroids32):
     return s + d[:, :, 5]
 
 
-def assign(data32, centroids32, chunk=200_000):
+def assign(data32, centroids32, chunk=None):
+    """First-minimum arg-min of sq_distances, `chunk` rows at a time.  The arithmetic is elementwise, so the chunk size
+    cannot change a label; the default keeps one (chunk, k, 6) float64 temporary near 8 MB - k = 2048 fits in memory, and
+    temporaries that stay in cache make it about twice as fast as 200 MB ones."""
+    if chunk is None:
+        chunk = max(1, min(200_000, 8_000_000 // (len(centroids32) * 6 * 8)))
     out = np.empty(len(data32), np.int64)
     for a in range(0, len(data32), chunk):
         out[a:a + chunk] = np.argmin(sq_distances(data32[a:a + chunk], centroids32), axis=1)
