@@ -696,6 +696,134 @@ int gsx_debug_sort_pairs_drop(gsx_ctx* ctx, uint32_t* keys, uint32_t* values, in
     return GSX_OK;
 }
 
+// The count lives on the device, the launch is sized for the capacity (what every frame of the rasterizer does): the whole
+// result buffer comes back, with the slots the sort must not have touched.
+int gsx_debug_sort_pairs_dev(gsx_ctx* ctx, uint32_t* keys, uint32_t* values, int64_t capacity, int64_t count, int32_t bits,
+                             int32_t* where_out) {
+    CTX_OR_FAIL(ctx);
+    if (capacity < 1 || count < 0 || bits < 1 || bits > 32 || !keys || !values || !where_out)
+        return gsx::fail(c, GSX_E_INVALID, "debug_sort_pairs_dev: bad arguments");
+    GSX_HIP(c, hipSetDevice(c->device));
+    gsx::DevBuf k0, v0, k1, v1, cnt;
+    const size_t nb = sizeof(uint32_t) * (size_t)capacity;
+    GSX_HIP(c, k0.ensure(nb));
+    GSX_HIP(c, v0.ensure(nb));
+    GSX_HIP(c, k1.ensure(nb));
+    GSX_HIP(c, v1.ensure(nb));
+    GSX_HIP(c, cnt.ensure(8));
+    const unsigned long long count_host = (unsigned long long)count;
+    GSX_HIP(c, hipMemcpyAsync(cnt.p, &count_host, 8, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(k0.p, keys, nb, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(v0.p, values, nb, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemsetAsync(k1.p, 0xff, nb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(v1.p, 0xff, nb, c->stream));
+    int where = 0;
+    int rc = gsx::radix_sort_pairs_dev(c, k0.as<uint32_t>(), v0.as<uint32_t>(), k1.as<uint32_t>(), v1.as<uint32_t>(), capacity,
+                                       cnt.as<unsigned long long>(), bits, &where);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // count_host and the buffers go away
+        return rc;
+    }
+    GSX_HIP(c, hipMemcpyAsync(keys, where ? k1.p : k0.p, nb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(values, where ? v1.p : v0.p, nb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    *where_out = where;
+    return GSX_OK;
+}
+
+int gsx_debug_sort_values_wide(gsx_ctx* ctx, const uint32_t* keys, const uint32_t* values, int64_t capacity, int64_t count,
+                               int32_t bits, int32_t nranges, uint32_t* values_out, int32_t* ranges_out) {
+    CTX_OR_FAIL(ctx);
+    if (capacity < 1 || count < 0 || bits < 1 || bits > 11 || nranges < 1 || nranges > 2048 || !keys || !values || !values_out ||
+        !ranges_out)
+        return gsx::fail(c, GSX_E_INVALID, "debug_sort_values_wide: bad arguments");
+    GSX_HIP(c, hipSetDevice(c->device));
+    gsx::DevBuf k0, v0, v1, rg, cnt;
+    const size_t nb = sizeof(uint32_t) * (size_t)capacity, rb = sizeof(int2) * (size_t)nranges;
+    GSX_HIP(c, k0.ensure(nb));
+    GSX_HIP(c, v0.ensure(nb));
+    GSX_HIP(c, v1.ensure(nb));
+    GSX_HIP(c, rg.ensure(rb));
+    GSX_HIP(c, cnt.ensure(8));
+    const unsigned long long count_host = (unsigned long long)count;
+    GSX_HIP(c, hipMemcpyAsync(cnt.p, &count_host, 8, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(k0.p, keys, nb, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(v0.p, values, nb, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemsetAsync(v1.p, 0xff, nb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(rg.p, 0xa5, rb, c->stream));  // (a range the sort does not write must not read as (0, 0))
+    int rc = gsx::radix_sort_values_wide(c, k0.as<uint32_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), capacity,
+                                         cnt.as<unsigned long long>(), bits, rg.as<int2>(), nranges);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    GSX_HIP(c, hipMemcpyAsync(values_out, v1.p, nb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(ranges_out, rg.p, rb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    return GSX_OK;
+}
+
+int gsx_debug_exclusive_scan(gsx_ctx* ctx, const uint32_t* in, int64_t n, uint32_t* out, uint64_t* grand_out) {
+    CTX_OR_FAIL(ctx);
+    if (n < 1 || n > ((int64_t)1 << 31) || !in || !out || !grand_out)
+        return gsx::fail(c, GSX_E_INVALID, "debug_exclusive_scan: bad arguments");
+    GSX_HIP(c, hipSetDevice(c->device));
+    gsx::DevBuf din, dout, grand;
+    const size_t nb = sizeof(uint32_t) * (size_t)n;
+    GSX_HIP(c, din.ensure(nb));
+    GSX_HIP(c, dout.ensure(nb));
+    GSX_HIP(c, grand.ensure(8));
+    GSX_HIP(c, hipMemcpyAsync(din.p, in, nb, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemsetAsync(dout.p, 0xff, nb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(grand.p, 0xff, 8, c->stream));
+    int rc = gsx::debug_exclusive_scan(c, din.as<uint32_t>(), dout.as<uint32_t>(), n, grand.as<unsigned long long>());
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    unsigned long long g = 0;
+    GSX_HIP(c, hipMemcpyAsync(out, dout.p, nb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(&g, grand.p, 8, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    *grand_out = (uint64_t)g;
+    return GSX_OK;
+}
+
+int gsx_debug_ranges(gsx_ctx* ctx, const uint32_t* sorted_keys, int64_t capacity, int64_t total, int32_t nlists, int32_t* ranges_out) {
+    CTX_OR_FAIL(ctx);
+    if (capacity < 1 || capacity > 0x7fffffff || total < 0 || nlists < 1 || !sorted_keys || !ranges_out)
+        return gsx::fail(c, GSX_E_INVALID, "debug_ranges: bad arguments");
+    GSX_HIP(c, hipSetDevice(c->device));
+    gsx::DevBuf dk, rg, tot;
+    const size_t nb = sizeof(uint32_t) * (size_t)capacity, rb = sizeof(int2) * (size_t)nlists;
+    GSX_HIP(c, dk.ensure(nb));
+    GSX_HIP(c, rg.ensure(rb));
+    GSX_HIP(c, tot.ensure(8));
+    const unsigned long long total_host = (unsigned long long)total;
+    GSX_HIP(c, hipMemcpyAsync(tot.p, &total_host, 8, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(dk.p, sorted_keys, nb, hipMemcpyHostToDevice, c->stream));
+    int rc = gsx::debug_ranges(c, dk.as<uint32_t>(), tot.as<unsigned long long>(), capacity, nlists, rg.as<int2>());
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    GSX_HIP(c, hipMemcpyAsync(ranges_out, rg.p, rb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    return GSX_OK;
+}
+
+int gsx_debug_spatial_order(gsx_ctx* ctx, uint32_t* perm_out) {
+    CTX_OR_FAIL(ctx);
+    if (!perm_out) return gsx::fail(c, GSX_E_INVALID, "debug_spatial_order: perm_out is NULL");
+    if (!c->sorted || c->n < 2)
+        return gsx::fail(c, GSX_E_INVALID, "debug_spatial_order: the context holds no sorted order (fewer than two positions, or the option "
+                                           "\"spatial_sort\" was off at the upload)");
+    GSX_HIP(c, hipSetDevice(c->device));
+    GSX_HIP(c, hipMemcpyAsync(perm_out, c->perm.p, sizeof(uint32_t) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    return GSX_OK;
+}
+
 // ---- profiling -----------------------------------------------------------------------------------
 int gsx_profile_enable(gsx_ctx* ctx, int on) {
     CTX_OR_FAIL(ctx);

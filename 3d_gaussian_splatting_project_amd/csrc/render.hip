@@ -741,7 +741,9 @@ __global__ __launch_bounds__(kRB) void scan_sums_kernel(const uint32_t* __restri
 }
 
 // sums: one u32 per workgroup (a few hundred): each workgroup re-adds the ones before it instead of a third launch.
-// The last workgroup also writes the grand total (64 bit: the pair count of a close-up view can pass 2^32).
+// The last workgroup also writes the grand total in 64 bits (the pair count of a close-up view can pass 2^32).  It is exact
+// as long as every 4096-entry tile's OWN sum stays below 2^32 (`sums` keeps one u32 per tile; they are added up in 64 bits);
+// the offsets are the exclusive sums mod 2^32.
 __global__ __launch_bounds__(kRB) void scan_down_kernel(const uint32_t* __restrict__ in, long long n,
                                                          const uint32_t* __restrict__ sums, uint32_t* __restrict__ out,
                                                          unsigned long long* __restrict__ grand) {
@@ -950,6 +952,18 @@ static int exclusive_scan_u32(Ctx* c, const uint32_t* in, uint32_t* out, long lo
         hipLaunchKernelGGL(scan_sums_kernel, dim3(m), dim3(kRB), 0, c->stream, in, n, sums);
         hipLaunchKernelGGL(scan_down_kernel, dim3(m), dim3(kRB), 0, c->stream, in, n, sums, out, grand_dev);
     }
+    GSX_HIP(c, hipGetLastError());
+    return GSX_OK;
+}
+
+// test hooks (gsx_debug_exclusive_scan, gsx_debug_ranges): the scan and the ranges launched as a frame launches them
+int debug_exclusive_scan(Ctx* c, const uint32_t* in, uint32_t* out, long long n, unsigned long long* grand_dev) {
+    return exclusive_scan_u32(c, in, out, n, grand_dev);
+}
+
+int debug_ranges(Ctx* c, const uint32_t* keys, const unsigned long long* total_dev, long long cap, int nlists, int2* ranges) {
+    GSX_HIP(c, hipMemsetAsync(ranges, 0, sizeof(int2) * (size_t)nlists, c->stream));
+    hipLaunchKernelGGL(ranges_kernel, dim3(grid_for(cap)), dim3(kRB), 0, c->stream, keys, total_dev, (unsigned long long)cap, nlists, ranges);
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;
 }

@@ -434,7 +434,8 @@ int radix_sort_values_wide(Ctx* c, const uint32_t* k0, const uint32_t* v0, uint3
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Morton order of the positions (performance only: results never depend on the order)
+// Morton order of the positions.  The vote's results do not depend on the order, its speed does (locality): the order itself
+// is pinned, element for element, against tests/sort_cases.py: morton_model through gsx_debug_spatial_order.
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float finite_or(float v, float alt) { return (v - v == 0.0f) ? v : alt; }
 

@@ -537,6 +537,47 @@ class Context:
         check(self._lib.gsx_debug_sort_pairs_drop(self.h, k.ctypes.data, v.ctypes.data, len(k), bits, C.byref(kept)), self.h)
         return k[:kept.value], v[:kept.value]
 
+    def sort_pairs_dev(self, keys, values, count, bits=32):
+        """radix_sort_pairs_dev: len(keys) is the buffers' capacity, `count` is read on the device.  Returns (keys, values,
+        where): the whole result buffer and which buffer pair it was (test hook, gsx_debug_sort_pairs_dev)."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32).copy()
+        v = np.ascontiguousarray(values, dtype=np.uint32).copy()
+        where = C.c_int32(-1)
+        check(self._lib.gsx_debug_sort_pairs_dev(self.h, k.ctypes.data, v.ctypes.data, len(k), int(count), bits, C.byref(where)), self.h)
+        return k, v, where.value
+
+    def sort_values_wide(self, keys, values, count, bits, nranges):
+        """The rasterizer's one-pass pair sort: (values (capacity,) u32 in the stable order of key bits [0, bits), ranges
+        (nranges, 2) int32) (test hook, gsx_debug_sort_values_wide)."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        v = np.ascontiguousarray(values, dtype=np.uint32)
+        out = np.empty(len(k), np.uint32)
+        ranges = np.empty((int(nranges), 2), np.int32)
+        check(self._lib.gsx_debug_sort_values_wide(self.h, k.ctypes.data, v.ctypes.data, len(k), int(count), bits, int(nranges),
+                                                   out.ctypes.data, ranges.ctypes.data), self.h)
+        return out, ranges
+
+    def exclusive_scan(self, values):
+        """(offsets (n,) u32, grand total as a Python int) of the rasterizer's scan (test hook, gsx_debug_exclusive_scan)."""
+        a = np.ascontiguousarray(values, dtype=np.uint32)
+        out = np.empty(len(a), np.uint32)
+        grand = C.c_uint64(0)
+        check(self._lib.gsx_debug_exclusive_scan(self.h, a.ctypes.data, len(a), out.ctypes.data, C.byref(grand)), self.h)
+        return out, int(grand.value)
+
+    def ranges(self, sorted_keys, total, nlists):
+        """(nlists, 2) int32 ranges of the sorted keys' first `total` entries (test hook, gsx_debug_ranges)."""
+        k = np.ascontiguousarray(sorted_keys, dtype=np.uint32)
+        out = np.empty((int(nlists), 2), np.int32)
+        check(self._lib.gsx_debug_ranges(self.h, k.ctypes.data, len(k), int(total), int(nlists), out.ctypes.data), self.h)
+        return out
+
+    def spatial_order(self):
+        """The Morton order of the last upload_positions: perm[i] = uploaded index of slot i (test hook, gsx_debug_spatial_order)."""
+        perm = np.empty(int(self._lib.gsx_num_gaussians(self.h)), np.uint32)
+        check(self._lib.gsx_debug_spatial_order(self.h, perm.ctypes.data), self.h)
+        return perm
+
     def synchronize(self):
         check(self._lib.gsx_synchronize(self.h), self.h)
         self._keep_alive.clear()

@@ -513,6 +513,31 @@ int gsx_debug_sort_pairs(gsx_ctx* ctx, uint32_t* keys, uint32_t* values, int64_t
 /* the rasterizer's level-1 sort (csrc/sort.hip: radix_sort_pairs_drop): pairs whose key is 0xffffffff are left out by the first
  * pass; the others come back sorted (stable) in the first *kept_out slots, the slots behind them hold unspecified values */
 int gsx_debug_sort_pairs_drop(gsx_ctx* ctx, uint32_t* keys, uint32_t* values, int64_t n, int32_t bits, int64_t* kept_out);
+/* test hook: radix_sort_pairs_dev as a frame of the rasterizer calls it - the buffers hold `capacity` pairs, the launches are
+ * sized for the capacity and the count is read on the device (a count above the capacity reads as 0).  keys / values
+ * (capacity entries each) come back as the WHOLE result buffer; *where_out = 0: the sort ended in the buffers the input was
+ * uploaded to (a slot the sort did not write still holds its input), 1: in the second pair, which held 0xff bytes before */
+int gsx_debug_sort_pairs_dev(gsx_ctx* ctx, uint32_t* keys, uint32_t* values, int64_t capacity, int64_t count, int32_t bits,
+                             int32_t* where_out);
+/* test hook: the rasterizer's one-pass pair sort (csrc/sort.hip: radix_sort_values_wide), bits in [1, 11], nranges in
+ * [1, 2048], the count on the device as above.  values_out (capacity entries, 0xff bytes where the sort wrote nothing): the
+ * values in the stable order of key bits [0, bits); ranges_out (nranges x 2 int32): [first, last + 1) slot of every key
+ * below nranges, written whatever the count */
+int gsx_debug_sort_values_wide(gsx_ctx* ctx, const uint32_t* keys, const uint32_t* values, int64_t capacity, int64_t count,
+                               int32_t bits, int32_t nranges, uint32_t* values_out, int32_t* ranges_out);
+/* test hook: the rasterizer's exclusive scan of n >= 1 uint32 (csrc/render.hip: exclusive_scan_u32).  out[i] = the sum of
+ * in[0 .. i) mod 2^32; *grand_out = the sum of all of them in 64 bits, exact while every 4096-entry tile's own sum is
+ * below 2^32 */
+int gsx_debug_exclusive_scan(gsx_ctx* ctx, const uint32_t* in, int64_t n, uint32_t* out, uint64_t* grand_out);
+/* test hook: the lists' ranges from the sorted pair keys (csrc/render.hip: ranges_kernel) launched as a frame launches it -
+ * sized for the capacity, the total on the device (above the capacity it reads as 0), the table zeroed first.
+ * ranges_out (nlists x 2 int32): [first, last + 1) slot of every key that occurs below nlists, (0, 0) for the others */
+int gsx_debug_ranges(gsx_ctx* ctx, const uint32_t* sorted_keys, int64_t capacity, int64_t total, int32_t nlists,
+                     int32_t* ranges_out);
+/* test hook: the Morton order of the last upload with the option "spatial_sort" on - perm_out[i] (gsx_num_gaussians
+ * entries) = the uploaded index of the position in slot i.  GSX_E_INVALID when the context holds no sorted order (fewer
+ * than two positions, or the option was off) */
+int gsx_debug_spatial_order(gsx_ctx* ctx, uint32_t* perm_out);
 /* test hook, host only (no context, no GPU): the packed form of one map exactly as gsx_vote_view stages it in
  * pinned memory - u8 bins in strips of 16 pixel columns (tiled != 0; row-major otherwise) followed, at *coarse_off
  * (-1: none), by the 4x4-coarsened level.  out == NULL only reports *bytes.  *bad = 1 if a label was out of range. */
