@@ -591,6 +591,11 @@ int gsx_render_debug(gsx_ctx* ctx, uint8_t* buffer_out, uint32_t* order_out, uin
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::render_debug(c, buffer_out, order_out, texdata_out, bucket_out); });
 }
+int gsx_debug_render_pre(gsx_ctx* ctx, int32_t num_views, const gsx_camera* cams, int32_t width, int32_t height, int32_t multi,
+                         int32_t compact, const gsx_debug_pre_view* out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::debug_render_pre(c, num_views, cams, width, height, multi, compact, out); });
+}
 
 int gsx_kmeans(gsx_ctx* ctx, int64_t n, const float* points, const float* colors, int32_t k, const int64_t* init_index,
                int32_t max_iter, double tol, int32_t* labels_out, float* centroids_out, int32_t* iterations_out,

@@ -1189,6 +1189,64 @@ static ViewUniforms view_uniforms(const gsx_camera* cam, int W, int H) {
     return u;
 }
 
+// ---- the launches of the per-splat pre pass: ONE place for gsx_render_view, gsx_render_views and the test hook
+// gsx_debug_render_pre, so that what the hook observes is the product's launch (grid cap, arguments, initial pre[])
+static unsigned pre_grid(long long n) { return std::min<unsigned>(grid_for(n), 2048u); }
+
+// one view: pre[] is reset, then pre_kernel writes depth[n], rect[n], rec[3n] (where it writes a record at all) and pre[0..2]
+static int launch_pre(Ctx* c, const gsx_camera* cam, const ViewUniforms& u, int* depth, int* pre, float4* rec, uint32_t* rect) {
+    const long long n = c->rn;
+    GSX_HIP(c, hipMemcpyAsync(pre, kPreInit, sizeof kPreInit, hipMemcpyHostToDevice, c->stream));
+    ProfScope ps(c, "render_pre");
+    hipLaunchKernelGGL(c->r_edits_on ? pre_kernel<true> : pre_kernel<false>, dim3(pre_grid(n)), dim3(kRB), 0,
+                       c->stream, c->r_tex.as<uint4>(), n, u,
+                       c->r_sh_on ? c->r_shc.as<float>() : nullptr, c->r_sh_deg, (float)cam->p[0], (float)cam->p[1],
+                       (float)cam->p[2], depth, pre, rec, rect, c->r_edits_on ? c->r_edit_code.as<uint16_t>() : (const uint16_t*)nullptr,
+                       c->r_edits_on ? c->r_edit_tab.as<EditTables>() : (const EditTables*)nullptr);
+    return GSX_OK;
+}
+
+// nv views (1 .. kPreViews) in one launch of pre_multi_kernel: view v writes into *sets[v].  a / a_dev: the host and device
+// copies of the arguments - the asynchronous copy may read `a` until the stream has passed it
+static int launch_pre_multi(Ctx* c, int nv, const gsx_camera* cams, int W, int H, Ctx::PreSet* const* sets, PreMultiArgs& a,
+                            PreMultiArgs* a_dev) {
+    a = PreMultiArgs{};
+    a.nv = nv;
+    for (int v = 0; v < nv; ++v) {
+        const gsx_camera* cam = cams + v;
+        Ctx::PreSet& ps = *sets[v];
+        a.u[v] = view_uniforms(cam, W, H);
+        for (int k = 0; k < 3; ++k) a.cam[v][k] = (float)cam->p[k];
+        a.depth[v] = ps.depth.as<int>();
+        a.pre[v] = ps.pre.as<int>();
+        a.rec[v] = ps.rec.as<float4>();
+        a.rect[v] = ps.rect.as<uint32_t>();
+        a.code = c->r_edits_on ? c->r_edit_code.as<uint16_t>() : nullptr;
+        a.edits = c->r_edits_on ? c->r_edit_tab.as<EditTables>() : nullptr;
+        GSX_HIP(c, hipMemcpyAsync(ps.pre.p, kPreInit, sizeof kPreInit, hipMemcpyHostToDevice, c->stream));
+    }
+    GSX_HIP(c, hipMemcpyAsync(a_dev, &a, sizeof a, hipMemcpyHostToDevice, c->stream));
+    using PK = void (*)(const uint4*, long long, const float*, int, const PreMultiArgs*);
+    static const PK kernels[2][kPreViews] = {
+        {pre_multi_kernel<1, false>, pre_multi_kernel<2, false>, pre_multi_kernel<3, false>, pre_multi_kernel<4, false>,
+         pre_multi_kernel<5, false>, pre_multi_kernel<6, false>},
+        {pre_multi_kernel<1, true>, pre_multi_kernel<2, true>, pre_multi_kernel<3, true>, pre_multi_kernel<4, true>,
+         pre_multi_kernel<5, true>, pre_multi_kernel<6, true>}};  // [1]: the label edits' instantiations
+    static_assert(kPreViews == 6, "one instantiation per group size");
+    hipLaunchKernelGGL(kernels[c->r_edits_on ? 1 : 0][nv - 1], dim3(pre_grid(c->rn)), dim3(kRB), 0, c->stream, c->r_tex.as<uint4>(),
+                       (long long)c->rn, c->r_sh_on ? c->r_shc.as<float>() : nullptr, c->r_sh_deg, a_dev);
+    GSX_HIP(c, hipGetLastError());
+    return GSX_OK;
+}
+
+// depth buckets and level-1 sort keys of one view from its depth keys and range; dropped splats lose their rectangle
+static void launch_bucket(Ctx* c, const int* depth, const int* pre, uint32_t* bucket, uint32_t* key, uint32_t* idx, uint32_t* rect,
+                          int* dropped, int compact) {
+    ProfScope ps(c, "render_bucket");
+    hipLaunchKernelGGL(bucket_kernel, dim3(grid_for(c->rn)), dim3(kRB), 0, c->stream, depth, (long long)c->rn, pre, bucket, key, idx, rect,
+                       dropped, compact);
+}
+
 // One frame.  Per view: pre_kernel (depth keys, vertex shader, colours, tile rectangles), bucket_kernel, the level-1
 // sort of the splats by depth bucket; then the splats are rasterized FRONT TO BACK IN DEPTH PHASES (the nearest
 // n/r^(K-1) splats, the next ones up to n/r^(K-2), .., the rest): each phase bins its splats into the tiles that are not
@@ -1289,21 +1347,11 @@ int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out) {
         GSX_HIP(c, hipMemsetAsync(c->r_sat.p, 0, sat_bytes, c->stream));
         GSX_HIP(c, hipMemsetAsync(small, 0, kSmallBytes, c->stream));  // counters
         if (!ext_pre) {  // (a frame that is redone because a phase overflowed the pair buffers keeps the pre pass's records)
-            GSX_HIP(c, hipMemcpyAsync(c->r_pre.p, kPreInit, sizeof kPreInit, hipMemcpyHostToDevice, c->stream));
-            ProfScope ps(c, "render_pre");
-            hipLaunchKernelGGL(c->r_edits_on ? pre_kernel<true> : pre_kernel<false>, dim3(std::min<unsigned>(grid_for(n), 2048u)), dim3(kRB), 0,
-                               c->stream, c->r_tex.as<uint4>(), n, u,
-                               c->r_sh_on ? c->r_shc.as<float>() : nullptr, c->r_sh_deg, (float)cam->p[0], (float)cam->p[1],
-                               (float)cam->p[2], c->r_depth.as<int>(), c->r_pre.as<int>(), c->r_rec.as<float4>(),
-                               c->r_rect.as<uint32_t>(), c->r_edits_on ? c->r_edit_code.as<uint16_t>() : (const uint16_t*)nullptr,
-                               c->r_edits_on ? c->r_edit_tab.as<EditTables>() : (const EditTables*)nullptr);
+            const int rcp = launch_pre(c, cam, u, c->r_depth.as<int>(), c->r_pre.as<int>(), c->r_rec.as<float4>(), c->r_rect.as<uint32_t>());
+            if (rcp) return rcp;
         }
-        {
-            ProfScope ps(c, "render_bucket");
-            hipLaunchKernelGGL(bucket_kernel, dim3(grid_for(n)), dim3(kRB), 0, c->stream, c->r_depth.as<int>(), n, c->r_pre.as<int>(),
-                               c->r_bucket.as<uint32_t>(), c->r_d0.as<uint32_t>(), c->r_d1.as<uint32_t>(), c->r_rect.as<uint32_t>(),
-                               small + 2, c->opt_render_compact);
-        }
+        launch_bucket(c, c->r_depth.as<int>(), c->r_pre.as<int>(), c->r_bucket.as<uint32_t>(), c->r_d0.as<uint32_t>(), c->r_d1.as<uint32_t>(),
+                      c->r_rect.as<uint32_t>(), small + 2, c->opt_render_compact);
         GSX_HIP(c, hipGetLastError());
         // level 1: splats by depth bucket (stable)
         int dwhere = 0;
@@ -1517,33 +1565,11 @@ int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* con
         // the host copy of the arguments lives in the context, one slot per record set: the asynchronous copy below may read it
         // after this function has returned (a slot is rewritten three groups later)
         PreMultiArgs& a = reinterpret_cast<PreMultiArgs*>(c->r_pre_args_host.data())[set];
-        a = PreMultiArgs{};
-        a.nv = std::min(F, n - g * F);
-        for (int v = 0; v < a.nv; ++v) {
-            const gsx_camera* cam = cams + (g * F + v);
-            Ctx::PreSet& ps = ctxs[v]->r_sets[set];
-            a.u[v] = view_uniforms(cam, W, H);
-            for (int k = 0; k < 3; ++k) a.cam[v][k] = (float)cam->p[k];
-            a.depth[v] = ps.depth.as<int>();
-            a.pre[v] = ps.pre.as<int>();
-            a.rec[v] = ps.rec.as<float4>();
-            a.rect[v] = ps.rect.as<uint32_t>();
-            a.code = c->r_edits_on ? c->r_edit_code.as<uint16_t>() : nullptr;
-            a.edits = c->r_edits_on ? c->r_edit_tab.as<EditTables>() : nullptr;
-            GSX_HIP(c, hipMemcpyAsync(ps.pre.p, kPreInit, sizeof kPreInit, hipMemcpyHostToDevice, c->stream));
-        }
-        PreMultiArgs* a_dev = c->r_pre_args.as<PreMultiArgs>() + set;
-        GSX_HIP(c, hipMemcpyAsync(a_dev, &a, sizeof a, hipMemcpyHostToDevice, c->stream));
-        using PK = void (*)(const uint4*, long long, const float*, int, const PreMultiArgs*);
-        static const PK kernels[2][kPreViews] = {
-            {pre_multi_kernel<1, false>, pre_multi_kernel<2, false>, pre_multi_kernel<3, false>, pre_multi_kernel<4, false>,
-             pre_multi_kernel<5, false>, pre_multi_kernel<6, false>},
-            {pre_multi_kernel<1, true>, pre_multi_kernel<2, true>, pre_multi_kernel<3, true>, pre_multi_kernel<4, true>,
-             pre_multi_kernel<5, true>, pre_multi_kernel<6, true>}};  // [1]: the label edits' instantiations
-        static_assert(kPreViews == 6, "one instantiation per group size");
-        hipLaunchKernelGGL(kernels[c->r_edits_on ? 1 : 0][a.nv - 1], dim3(std::min<unsigned>(grid_for(c->rn), 2048u)), dim3(kRB), 0, c->stream, c->r_tex.as<uint4>(),
-                           (long long)c->rn, c->r_sh_on ? c->r_shc.as<float>() : nullptr, c->r_sh_deg, a_dev);
-        GSX_HIP(c, hipGetLastError());
+        const int nv = std::min(F, n - g * F);
+        Ctx::PreSet* sets[kPreViews];
+        for (int v = 0; v < nv; ++v) sets[v] = &ctxs[v]->r_sets[set];
+        const int rcp = launch_pre_multi(c, nv, cams + g * F, W, H, sets, a, c->r_pre_args.as<PreMultiArgs>() + set);
+        if (rcp) return rcp;
         GSX_HIP(c, hipEventRecord(c->r_pre_ev[set], c->stream));
         pre_issued.store(g + 1, std::memory_order_release);
         return GSX_OK;
@@ -1765,6 +1791,64 @@ int render_debug(Ctx* c, uint8_t* buffer_out, uint32_t* order_out, uint32_t* tex
     }
     GSX_HIP(c, hipStreamSynchronize(c->stream));
     return GSX_OK;
+}
+
+// gsx_debug_render_pre: the product's pre pass (launch_pre per view, or ONE launch_pre_multi) and bucket_kernel into buffers
+// of the call's own - the context's record sets, its frame buffers and its counters are not touched
+int debug_render_pre(Ctx* c, int nv, const gsx_camera* cams, int W, int H, int multi, int compact, const gsx_debug_pre_view* out) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    if (nv < 1 || nv > kPreViews || !cams || !out || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "debug_render_pre: bad arguments");
+    if ((W + 15) / 16 > 256 || (H + 15) / 16 > 256) return fail(c, GSX_E_UNSUPPORTED, "debug_render_pre: %dx%d exceeds 4096 pixels per side", W, H);
+    const long long n = c->rn;
+    if (n <= 0) return fail(c, GSX_E_STATE, "debug_render_pre before upload_splats");
+    const size_t n4 = 4 * (size_t)n;
+    Ctx::PreSet sets[kPreViews];
+    Ctx::PreSet* setp[kPreViews];
+    DevBuf bucket, key, idx, dropped, args;
+    for (int v = 0; v < nv; ++v) {
+        const int rc = ensure_pre_set(c, sets[v], n);
+        if (rc) return rc;
+        setp[v] = &sets[v];
+        // sentinel: what the pass does not write stays 0xFF bytes
+        GSX_HIP(c, hipMemsetAsync(sets[v].depth.p, 0xFF, n4, c->stream));
+        GSX_HIP(c, hipMemsetAsync(sets[v].rect.p, 0xFF, n4, c->stream));
+        GSX_HIP(c, hipMemsetAsync(sets[v].rec.p, 0xFF, 48 * (size_t)n, c->stream));
+    }
+    GSX_HIP(c, bucket.ensure(n4));
+    GSX_HIP(c, key.ensure(n4));
+    GSX_HIP(c, idx.ensure(n4));
+    GSX_HIP(c, dropped.ensure(sizeof(int)));
+    PreMultiArgs a;  // (lives until the synchronisation below)
+    int rc = GSX_OK;
+    if (multi) {
+        GSX_HIP(c, args.ensure(sizeof(PreMultiArgs)));
+        rc = launch_pre_multi(c, nv, cams, W, H, setp, a, args.as<PreMultiArgs>());
+    } else {
+        for (int v = 0; v < nv && rc == GSX_OK; ++v) {
+            const ViewUniforms u = view_uniforms(cams + v, W, H);
+            rc = launch_pre(c, cams + v, u, sets[v].depth.as<int>(), sets[v].pre.as<int>(), sets[v].rec.as<float4>(), sets[v].rect.as<uint32_t>());
+        }
+        if (rc == GSX_OK) GSX_HIP(c, hipGetLastError());
+    }
+    for (int v = 0; v < nv && rc == GSX_OK; ++v) {
+        const gsx_debug_pre_view& o = out[v];
+        Ctx::PreSet& ps = sets[v];
+        if (o.depth) GSX_HIP(c, hipMemcpyAsync(o.depth, ps.depth.p, n4, hipMemcpyDeviceToHost, c->stream));
+        if (o.rect) GSX_HIP(c, hipMemcpyAsync(o.rect, ps.rect.p, n4, hipMemcpyDeviceToHost, c->stream));
+        if (o.rec) GSX_HIP(c, hipMemcpyAsync(o.rec, ps.rec.p, 48 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (o.pre) GSX_HIP(c, hipMemcpyAsync(o.pre, ps.pre.p, 16, hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(c, hipMemsetAsync(dropped.p, 0, sizeof(int), c->stream));
+        launch_bucket(c, ps.depth.as<int>(), ps.pre.as<int>(), bucket.as<uint32_t>(), key.as<uint32_t>(), idx.as<uint32_t>(), ps.rect.as<uint32_t>(),
+                      dropped.as<int>(), compact);
+        GSX_HIP(c, hipGetLastError());
+        if (o.bucket) GSX_HIP(c, hipMemcpyAsync(o.bucket, bucket.p, n4, hipMemcpyDeviceToHost, c->stream));
+        if (o.key) GSX_HIP(c, hipMemcpyAsync(o.key, key.p, n4, hipMemcpyDeviceToHost, c->stream));
+        if (o.rect_bucket) GSX_HIP(c, hipMemcpyAsync(o.rect_bucket, ps.rect.p, n4, hipMemcpyDeviceToHost, c->stream));
+        if (o.dropped) GSX_HIP(c, hipMemcpyAsync(o.dropped, dropped.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(c, hipStreamSynchronize(c->stream));  // (a view's outputs are on the host before the next view reuses bucket / key / dropped)
+    }
+    GSX_HIP(c, hipStreamSynchronize(c->stream));  // nothing of this call is in flight when its buffers are freed
+    return rc;
 }
 
 }  // namespace gsx

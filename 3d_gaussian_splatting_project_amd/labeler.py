@@ -512,6 +512,23 @@ class Context:
                                          bk.ctypes.data if buckets else None), self.h)
         return (buf, order, tex, bk) if buckets else (buf, order, tex)
 
+    def debug_render_pre(self, cameras, width, height, multi=False, compact=True):
+        """The rasterizer's per-splat pre pass and depth-bucket kernel for 1..6 cameras (test hook, gsx_debug_render_pre; multi:
+        one launch of the several-view kernel instead of one launch per view) -> per view a dict: depth (n,) i32, rect (n,) u32,
+        rec (n,12) f32 (0xFF bytes where no record was written), pre (4,) i32, bucket, key, rect_bucket (n,) u32, dropped int."""
+        n, nv = self.n_splats, len(cameras)
+        cams = (Camera * nv)(*[c if isinstance(c, Camera) else Camera.from_dict(c) for c in cameras])
+        outs = [dict(depth=np.empty(n, np.int32), rect=np.empty(n, np.uint32), rec=np.empty((n, 12), np.float32),
+                     pre=np.empty(4, np.int32), bucket=np.empty(n, np.uint32), key=np.empty(n, np.uint32),
+                     rect_bucket=np.empty(n, np.uint32), dropped=np.empty(1, np.int32)) for _ in range(nv)]
+        fields = ("depth", "rect", "rec", "pre", "bucket", "key", "rect_bucket", "dropped")
+        ptrs = (C.c_void_p * (len(fields) * nv))(*[o[f].ctypes.data for o in outs for f in fields])
+        check(self._lib.gsx_debug_render_pre(self.h, nv, cams, int(width), int(height), 1 if multi else 0, 1 if compact else 0, ptrs),
+              self.h)
+        for o in outs:
+            o["dropped"] = int(o["dropped"][0])
+        return outs
+
     def export_splat(self, path):
         """Write the uploaded splats as a `.splat` file: the viewer's 32-byte rows (position f32x3, exp(scale)
         f32x3, rgba u8x4, quaternion u8x4; gs.js:237, 539-542) in importance order.  The reference viewer takes

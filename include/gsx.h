@@ -474,6 +474,29 @@ int64_t gsx_render_num_hidden(const gsx_ctx* ctx);
  * depth buckets (65536 = dropped by the JS counting sort, gs.js:443-457) */
 int gsx_render_debug(gsx_ctx* ctx, uint8_t* buffer_out, uint32_t* order_out, uint32_t* texdata_out,
                      uint32_t* bucket_out);
+/* test hook: the rasterizer's per-splat pre pass (depth keys, vertex shader, colours, tile rectangles) and the depth-bucket
+ * kernel, run on the uploaded scene with the current SH and edit state for num_views cameras (1..6) of one frame size, and what
+ * they wrote, per view.  multi = 0: one pre-kernel launch per view, as gsx_render_view issues it; multi = 1: ONE launch of the
+ * several-view kernel for all of them, as gsx_render_views issues it per group of frames - in both cases through the launch
+ * code of those entry points (grid, arguments, initial depth range).  compact: the option "render_compact" as the bucket kernel
+ * sees it.  The pass runs in buffers of the call's own, filled with 0xFF bytes beforehand (a splat without a tile rectangle
+ * writes no record: its 48 bytes stay 0xFF); frames rendered afterwards are not affected.  Any pointer may be NULL.
+ *   depth   n int32      depth keys, gs.js:436-441           rect         n u32  tx0 | tx1 << 8 | ty0 << 16 | ty1 << 24, 1 = no tile
+ *   rec     n x 12 f32   (cx, cy, g0, g1, rgba, 0, 0)        pre          4 int32: min key, max key, splat 0's rect, unused
+ *   bucket  n u32        16-bit bucket, 65536 = dropped      key          n u32  level-1 sort key
+ *   rect_bucket n u32    rect after the bucket kernel (dropped splats cleared)      dropped  1 int32: splats dropped */
+typedef struct gsx_debug_pre_view {
+    int32_t* depth;
+    uint32_t* rect;
+    float* rec;
+    int32_t* pre;
+    uint32_t* bucket;
+    uint32_t* key;
+    uint32_t* rect_bucket;
+    int32_t* dropped;
+} gsx_debug_pre_view;
+int gsx_debug_render_pre(gsx_ctx* ctx, int32_t num_views, const gsx_camera* cams, int32_t width, int32_t height, int32_t multi,
+                         int32_t compact, const gsx_debug_pre_view* out);
 
 /* ---------------------------------------------------------------------------------------------
  * PLY files — replaces the plyfile calls of the reference: PlyData.read (dls.py:29, ply_handler.py:

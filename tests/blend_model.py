@@ -15,6 +15,7 @@ closed form from a prefix product and a suffix recursion, no second render."""
 import numpy as np
 
 import oracle
+import vertex_model
 
 TILE = 16
 NEAR = 1e-4          # |q - 4| below which fp32 and fp64 may decide `discard` differently
@@ -51,23 +52,9 @@ class Records:
         self.box = self._boxes()
 
     def _boxes(self):
-        """Pixels whose CENTRE lies in the bounding box of the ellipse with half-axes major, minor (+ 1/64 px), clipped to the
-        frame: (x0, x1, r0, r1) inclusive, image rows; x1 < x0 where the splat reaches no pixel centre.  float32, as a binner
-        that works on the vertex shader's outputs sees them."""
-        f = np.float32
-        W, H = f(self.W), f(self.H)
-        ex = np.sqrt(self.major[:, 0] * self.major[:, 0] + self.minor[:, 0] * self.minor[:, 0]) + f(0.015625)
-        ey = np.sqrt(self.major[:, 1] * self.major[:, 1] + self.minor[:, 1] * self.minor[:, 1]) + f(0.015625)
-        cx, top = self.c[:, 0], H - self.c[:, 1]
-        clampx = lambda v: np.minimum(np.maximum(v, f(-1.0)), W)
-        clampy = lambda v: np.minimum(np.maximum(v, f(-1.0)), H)
-        x0 = np.maximum(np.ceil(clampx(cx - ex - f(0.5))).astype(np.int64), 0)
-        x1 = np.minimum(np.floor(clampx(cx + ex - f(0.5))).astype(np.int64), self.W - 1)
-        r0 = np.maximum(np.ceil(clampy(top - ey - f(0.5))).astype(np.int64), 0)
-        r1 = np.minimum(np.floor(clampy(top + ey - f(0.5))).astype(np.int64), self.H - 1)
-        box = np.stack([x0, x1, r0, r1], 1)
-        box[~self.drawn | (x1 < x0) | (r1 < r0)] = (1, 0, 1, 0)
-        return box
+        """(x0, x1, r0, r1) inclusive per splat, x1 < x0 where it reaches no pixel centre: vertex_model.pixel_box, the binner's
+        box on the vertex shader's float32 outputs"""
+        return vertex_model.pixel_box(self.c[:, 0], self.c[:, 1], self.major, self.minor, self.drawn, self.W, self.H)
 
 
 class BlendModel:
