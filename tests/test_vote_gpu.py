@@ -1,6 +1,7 @@
 """GPU parity tests: the HIP labeler (libgsx.so through its C ABI) against the committed golden
 vectors (recorded from the reference) and against the CPU oracle on seeded synthetic scenes.
-Integer work: every comparison is bit-exact."""
+Integer work: every comparison is bit-exact.
+The kernels' structural edges (chunk, mask word, batch, record, bin rows, wave, workgroup, map cells) are met on purpose in test_vote_edges_gpu.py."""
 import importlib
 import os
 
