@@ -5,6 +5,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -43,53 +44,81 @@ MapLayout map_layout(int w, int h, bool tiled, bool coarse) {
 // ---- worker pool ---------------------------------------------------------------------------------------------------
 // Fork-join whose cost is a handful of cache-line transfers (a 1080p map is packed in ~30 us, 200 times per run: round 2's
 // first pool spent 3.5-4.4 us per call forking and joining, 10 % of the hand-over):
-//   fork   the caller writes the job (one line) and bumps `generation` (the one line the idle workers poll).  Nothing per
-//          worker is written: thread t owns the contiguous parts [parts*t/T, parts*(t+1)/T) and every thread derives any
+//   fork   the caller writes the job (one line) and publishes `generation` (the one line the idle workers poll): the run's number
+//          and its number of parts in ONE word, so that a worker never pairs one run's number with another run's parts.  Nothing
+//          per worker is written: thread t owns the contiguous parts [parts*t/T, parts*(t+1)/T) and every thread derives any
 //          thread's bounds itself.
-//   claim  a thread's next unclaimed part lives in a 64-bit word on the thread's own line, tagged with the generation:
-//          (generation << 32) | next.  A stale tag means "nothing claimed yet in this run", so nobody has to reset the
-//          words; owner and helpers claim with the same compare-and-swap.  A thread works through its own share first, then
-//          helps the others (a thread that shares its core, reads remote memory or was descheduled would otherwise hold the
-//          whole call up).
-//   join   every worker decrements one counter (a line of its own, touched once per worker and run) when it has nothing
-//          left to claim; the caller spins on that line only.
+//   claim  a thread's next unclaimed part lives in a 64-bit word on the thread's own line, tagged with the run's number:
+//          (run << 24) | next (40 bits of run number: seven months of back-to-back 36-us runs).  Tags are ORDERED: an older tag
+//          means "nothing claimed yet in this run" (nobody has to reset the words), a newer one "this run is over".  Owner and
+//          helpers claim with the same compare-and-swap.  A thread works through its own share first, then helps the others (a
+//          thread that shares its core, reads remote memory or was descheduled would otherwise hold the whole call up).
+//   join   by PARTS, not by workers: a thread adds the number of parts it has run to one counter (a line of its own, touched once per
+//          thread and share it worked on: its own, and any it helped with) BEFORE it looks at the other threads' claim words, and
+//          run() returns when the counter reaches `parts`.  The job's `fin` hook runs just before that report.  A
+//          worker that slept through a run, or wakes in the middle of a later one, is nobody's business: run() does not wait for
+//          it.  Such a worker must be harmless, so it reads the job's function and argument (jobs live on the caller's stack)
+//          only AFTER it has claimed a part: the claim can only succeed while the run it belongs to is unfinished, and until that
+//          part is reported run() does not return and the job is not rewritten.
 // (One shared `next part` counter next to the flag the idle workers poll cost 0.3 ms per call on a 2-socket EPYC: every
 // fetch_add fought the pollers for the line.)  Placement: see below.
 struct alignas(64) Slot {
-    std::atomic<uint64_t> claim{0};  // (generation << 32) | next unclaimed part of this thread's share
+    std::atomic<uint64_t> claim{0};  // (run << 24) | next unclaimed part of this thread's share
 };
+constexpr int kPartBits = 24;  // a run has fewer than 2^24 parts (run() takes more on the calling thread alone)
+constexpr uint64_t kPartMask = ((uint64_t)1 << kPartBits) - 1;
 
 struct Workers::Impl {
     std::vector<std::thread> threads;
     std::mutex m;
     std::condition_variable cv;
-    alignas(64) std::atomic<uint64_t> generation{0};  // bumped once per run(); its own line: polled by every idle worker
-    alignas(64) int parts = 0;                        // the job: written before the bump, read after it
-    void (*fn)(void*, int) = nullptr;
-    void* arg = nullptr;
-    alignas(64) std::atomic<int> remaining{0};        // workers that have not finished the current run
+    alignas(64) std::atomic<uint64_t> generation{0};  // (run << 24) | parts, published once per run(); its own line: polled by every idle worker
+    // the job: written before the run is published, read after a claim (atomics: a late worker may look while the next is written)
+    alignas(64) std::atomic<void (*)(void*, int)> fn{nullptr};
+    std::atomic<void (*)(void*)> fin{nullptr};
+    std::atomic<void*> arg{nullptr};
+    alignas(64) std::atomic<int> done{0};             // parts of the current run that have been executed (and flushed)
     alignas(64) int nthreads = 1;
     std::atomic<bool> stop{false};
     Slot* slots = nullptr;
 
-    // claims one part of thread v's share in run g; -1 when the share is exhausted
-    int claim(int v, uint32_t g, int nparts) {
+    // claims one part of thread v's share in run g; -1 when the share is exhausted or the run is over
+    int claim(int v, uint64_t g, int nparts) {
         const int lo = (int)((long long)nparts * v / nthreads), hi = (int)((long long)nparts * (v + 1) / nthreads);
+        if (lo >= hi) return -1;
         std::atomic<uint64_t>& w = slots[v].claim;
         uint64_t cur = w.load(std::memory_order_relaxed);
         for (;;) {
-            const int idx = (uint32_t)(cur >> 32) == g ? (int)(uint32_t)cur : lo;
+            const int64_t age = (int64_t)(((cur >> kPartBits) - g) << kPartBits);  // < 0: a tag of an earlier run, > 0: of a later one
+            if (age > 0) return -1;
+            const int idx = age == 0 ? (int)(cur & kPartMask) : lo;
             if (idx >= hi) return -1;
-            if (w.compare_exchange_weak(cur, ((uint64_t)g << 32) | (uint32_t)(idx + 1), std::memory_order_relaxed)) return idx;
+            if (w.compare_exchange_weak(cur, (g << kPartBits) | (uint64_t)(idx + 1), std::memory_order_acquire, std::memory_order_relaxed))
+                return idx;
         }
     }
-    void share(int t, uint32_t g) {
-        const int nparts = parts;
-        void (*const f)(void*, int) = fn;
-        void* const a = arg;
+    // runs the parts of share v that are still unclaimed, flushes, reports them; returns true when that completed the run
+    bool work(int v, uint64_t g, int nparts) {
+        int p = claim(v, g, nparts);
+        if (p < 0) return false;
+        // a part of run g is ours: the run is unfinished, the job is run g's and stays until the part is reported
+        void (*const f)(void*, int) = fn.load(std::memory_order_relaxed);
+        void (*const e)(void*) = fin.load(std::memory_order_relaxed);
+        void* const a = arg.load(std::memory_order_relaxed);
+        int n = 0;
+        do {
+            f(a, p);
+            ++n;
+        } while ((p = claim(v, g, nparts)) >= 0);
+        if (e) e(a);
+        return done.fetch_add(n, std::memory_order_acq_rel) + n == nparts;
+    }
+    void share(int t, uint64_t word) {
+        const uint64_t g = word >> kPartBits;
+        const int nparts = (int)(word & kPartMask);
         for (int k = 0; k < nthreads; ++k) {  // own share first, then the others' leftovers
             const int v = t + k < nthreads ? t + k : t + k - nthreads;
-            for (int p; (p = claim(v, g, nparts)) >= 0;) f(a, p);
+            if (work(v, g, nparts)) return;
         }
     }
     void loop(int t) {
@@ -108,8 +137,7 @@ struct Workers::Impl {
             }
             if (stop.load()) return;
             seen = g;
-            share(t, (uint32_t)g);
-            remaining.fetch_sub(1, std::memory_order_release);
+            share(t, g);
         }
     }
 };
@@ -268,26 +296,27 @@ Workers::~Workers() {
     delete impl_;
 }
 
-void Workers::run(int parts, void (*fn)(void*, int), void* arg) {
+void Workers::run(int parts, void (*fn)(void*, int), void* arg, void (*fin)(void*)) {
     if (parts <= 0) return;
-    if (nthreads_ == 1 || parts == 1) {
+    if (nthreads_ == 1 || parts == 1 || parts > (int)kPartMask) {
         for (int p = 0; p < parts; ++p) fn(arg, p);
+        if (fin) fin(arg);
         return;
     }
     Impl& s = *impl_;
-    // every worker has finished the previous run (run() waited for it), so nobody reads the job while it changes
-    s.parts = parts;
-    s.fn = fn;
-    s.arg = arg;
-    s.remaining.store(nthreads_ - 1, std::memory_order_relaxed);
-    uint64_t g;
+    // the previous run is complete: a worker that still looks at it can claim nothing, and reads the job only after a claim
+    s.fn.store(fn, std::memory_order_relaxed);
+    s.fin.store(fin, std::memory_order_relaxed);
+    s.arg.store(arg, std::memory_order_relaxed);
+    s.done.store(0, std::memory_order_relaxed);
+    const uint64_t word = (((s.generation.load(std::memory_order_relaxed) >> kPartBits) + 1) << kPartBits) | (uint64_t)parts;
     {
         std::lock_guard<std::mutex> lk(s.m);  // pairs with the sleepers' predicate check
-        g = s.generation.fetch_add(1, std::memory_order_release) + 1;
+        s.generation.store(word, std::memory_order_release);
     }
     s.cv.notify_all();
-    s.share(0, (uint32_t)g);
-    while (s.remaining.load(std::memory_order_acquire) != 0) cpu_relax();
+    s.share(0, word);
+    while (s.done.load(std::memory_order_acquire) != parts) cpu_relax();
 }
 
 // CPUs' worth of time the cgroup of this process may use per scheduler period (cgroup v2 cpu.max, v1 cfs quota), 0 = unlimited
@@ -548,8 +577,8 @@ struct PackJob {
     // compact form only
     uint32_t* table = nullptr;
     uint8_t* stream = nullptr;
-    // written by the workers: on lines of their own (every band reads the fields above; a counter next to them would pull
-    // that line out of sixteen caches 135 times per map)
+    // written by the workers: on lines of their own (every part reads the fields above; a counter next to them would pull
+    // that line out of sixteen caches again and again)
     alignas(64) std::atomic<unsigned> bad{0};
     alignas(64) std::atomic<uint32_t> blocks{0};
     char pad_[60] = {};
@@ -583,15 +612,8 @@ static void pack_band_tiled(PackJob* j, int part) {
         }
         continues_at = end;
     }
-    // Compact form: nothing reads the strips behind this function (the coarse bytes and the mixed cells' blocks are all that
-    // leaves), so the band's lines need not live in a map-sized scratch whose every line is a fresh miss - they go to a buffer
-    // of this thread that the next band reuses: `strips` lines of 128 bytes, in the first-level cache for good.
-    const bool local = j->stream != nullptr;
-    static thread_local std::vector<uint8_t> lines_tl;
-    if (local && lines_tl.size() < (size_t)strips * 128 + 64) lines_tl.resize((size_t)strips * 128 + 64);
-    uint8_t* const lbase = local ? lines_tl.data() + ((64 - (reinterpret_cast<uintptr_t>(lines_tl.data()) & 63)) & 63) : nullptr;
-    const size_t spitch = local ? (size_t)128 : (size_t)L.strip_bytes;             // from one strip's line to the next strip's
-    uint8_t* const band0 = local ? lbase : dst + (size_t)band * 128;               // the band's line of strip 0
+    const size_t spitch = (size_t)L.strip_bytes;         // from one strip's line to the next strip's
+    uint8_t* const band0 = dst + (size_t)band * 128;     // the band's line of strip 0
     for (int y = y0; y < y1; ++y) {
         const T* row = seg + (size_t)y * L.w;
         uint8_t* o = band0 + (size_t)(y - r0) * 16;  // row y of strip 0
@@ -646,53 +668,142 @@ static void pack_band_tiled(PackJob* j, int part) {
         }
     }
     if (bad) j->bad.fetch_or(1u, std::memory_order_relaxed);
-    if (j->stream) {
-        // compact form: the mixed cells (coarse byte 255) of this band's two cell rows go to the stream as 16-byte blocks, cell
-        // row by cell row and inside a row by cell column; uniform cells are their coarse byte.  The strips' lines were
-        // written a moment ago: they are in this core's cache.  Cost ~ the number of mixed cells: a row of 16 cells is one
-        // compare + movemask.  table[2 * band + c] = where cell row c's blocks start.
-        constexpr int kMaxCs = 1024;  // coarse strips of a 65535-pixel row
-        uint16_t masks[2][kMaxCs];
-        const int ncs = (L.cw + 15) >> 4;
-        uint32_t n[2] = {0, 0};
-        for (int cyl = c0; cyl < c1; ++cyl) {
-            const int cy = band * 2 + cyl;
-            if (cy >= L.ch) break;
-            if (L.cw & 15)  // the cells past the map's last cell column: defined bytes (the level goes into the pool as it is)
-                std::memset(j->coarse + (size_t)(L.cw >> 4) * L.cstrip_bytes + (size_t)cy * 16 + (L.cw & 15), 0, (size_t)(16 - (L.cw & 15)));
-            for (int cs = 0; cs < ncs; ++cs) {
-                const uint8_t* co = j->coarse + (size_t)cs * L.cstrip_bytes + (size_t)cy * 16;
-                unsigned m;
-#if defined(__x86_64__)
-                m = (unsigned)_mm_movemask_epi8(_mm_cmpeq_epi8(_mm_loadu_si128(reinterpret_cast<const __m128i*>(co)), _mm_set1_epi8((char)255)));
-#else
-                m = 0;
-                for (int k = 0; k < 16; ++k) m |= (unsigned)(co[k] == 255) << k;
-#endif
-                masks[cyl][cs] = (uint16_t)m;  // padding cells are 0, never 255
-                n[cyl] += (unsigned)__builtin_popcount(m);
-            }
+}
+
+// Compact form: one CELL ROW (4 pixel rows, fewer for a ragged last one) per part.  Nothing reads the strips behind the packer (the
+// coarse bytes and the mixed cells' blocks are all that leaves), so a work unit is not tied to the 128-B line that 8 rows of a strip
+// share: the rows' 16-byte pieces go to a buffer of this thread, 64 bytes per strip, in the first-level cache for good, and the coarse
+// bytes, the mixed-cell masks, the table entry and the blocks are all made per cell row.  A 1080p map is then 270 units: shares of 17
+// or 16 on 16 threads (8.5 band-times against the 9 of whole bands), each still one contiguous piece of the map.
+struct CompactTL {
+    const void* continues_at = nullptr;  // where this thread's stream through the map stands
+    std::vector<uint8_t> lines;          // the cell row being packed: 64 B per strip
+    // The mixed cells' blocks of the cell rows this thread has packed in the current call wait here, and compact_flush() moves them
+    // into the stream after ONE reservation: the stream's counter is a line all threads write, and a reservation per band was 135
+    // locked read-modify-writes on it per 1080p map.
+    std::vector<uint8_t> blocks;
+    std::vector<uint32_t> rows;  // pairs: cell row, its first block in `blocks`
+    uint32_t nblocks = 0;
+};
+static thread_local CompactTL compact_tl;
+
+template <typename T, unsigned ADD>
+static void pack_cell_row(void* arg, int cy) {
+    PackJob* j = static_cast<PackJob*>(arg);
+    const MapLayout L = j->L;  // by value: the u8 stores below may alias anything reached through a pointer
+    const unsigned bins = j->bins;
+    const T* seg = static_cast<const T*>(j->seg);
+    const int r0 = cy * 4, r1 = r0 + 4;          // pixel rows of this cell row ...
+    const int y1 = r1 < L.h ? r1 : L.h;          // ... that exist (r0 < h: cy < ch)
+    const int strips = (L.w + 15) / 16, full = L.w / 16;
+    CompactTL& tl = compact_tl;
+    {
+        // a cell row that does not continue this thread's stream starts cold: ask for a whole prefetch distance at once (see
+        // pack_band_tiled)
+        const char* first = reinterpret_cast<const char*>(seg + (size_t)r0 * L.w);
+        const char* end = reinterpret_cast<const char*>(seg + (size_t)y1 * L.w);
+        if (first != tl.continues_at && g_prefetch_burst) {
+            const char* stop = first + g_prefetch_bytes < end ? first + g_prefetch_bytes : end;
+            for (const char* q = first; q < stop; q += 64) prefetch_map(q);
         }
-        const uint32_t total = n[0] + n[1];
-        uint32_t first = total ? j->blocks.fetch_add(total, std::memory_order_relaxed) : 0u;
-        for (int cyl = c0; cyl < c1; ++cyl) {
-            j->table[2 * band + cyl] = first;
-            uint8_t* out = j->stream + (size_t)first * 16;
-            first += n[cyl];
-            if (!n[cyl]) continue;
-            const uint8_t* rows = band0 + (size_t)(cyl * 4) * 16;  // row 4*cyl of the band in strip 0
-            for (int cs = 0; cs < ncs; ++cs) {
-                for (unsigned m = masks[cyl][cs]; m; m &= m - 1) {
-                    const int cx = cs * 16 + __builtin_ctz(m);
-                    const uint8_t* q = rows + (size_t)(cx >> 2) * spitch + (cx & 3) * 4;  // rows 16 bytes apart
-                    uint32_t r[4];
-                    std::memcpy(&r[0], q, 4), std::memcpy(&r[1], q + 16, 4), std::memcpy(&r[2], q + 32, 4), std::memcpy(&r[3], q + 48, 4);
-                    std::memcpy(out, r, 16);
-                    out += 16;
+        tl.continues_at = end;
+    }
+    if (tl.lines.size() < (size_t)strips * 64 + 64) tl.lines.resize((size_t)strips * 64 + 64);
+    uint8_t* const lbase = tl.lines.data() + ((64 - (reinterpret_cast<uintptr_t>(tl.lines.data()) & 63)) & 63);
+    unsigned bad = 0;
+    for (int y = r0; y < y1; ++y) {
+        const T* row = seg + (size_t)y * L.w;
+        uint8_t* o = lbase + (size_t)(y - r0) * 16;  // row y of strip 0
+        if (full) bad |= rows16<T, ADD>(row, 16, full, bins, o, 64);
+        if (full < strips) {  // ragged last strip: columns past the map hold bin 0
+            uint8_t* e = o + (size_t)full * 64;
+            std::memset(e, 0, 16);
+            bad |= narrow_n<T, ADD>(row + (size_t)full * 16, L.w - full * 16, bins, e);
+        }
+    }
+    if (bad) j->bad.fetch_or(1u, std::memory_order_relaxed);
+    // coarse bytes: a cell holds the bin its 16 pixels share, else 255 (cells that stick out of the map are "mixed": the vote then reads
+    // the exact pixel).  A cell row inside the map: four strips at a time; the strips that are left (and every strip of a ragged cell
+    // row, or without AVX2) take the general loop.
+    const bool whole = y1 == r1;
+    int s_fast = 0;
+    if (g_avx2 && whole) {
+        s_fast = (full / 4) * 4;
+        if (s_fast) coarse_row_avx2(lbase, 64, s_fast / 4, j->coarse + (size_t)cy * 16, (size_t)L.cstrip_bytes);
+    }
+    for (int s = s_fast; s < strips; ++s) {
+        const int x0 = s * 16;
+        const int cnt = L.w - x0 >= 16 ? 16 : L.w - x0;
+        uint8_t* line = lbase + (size_t)s * 64;
+        if (!whole) std::memset(line + (size_t)(y1 - r0) * 16, 0, (size_t)(r1 - y1) * 16);  // rows past the map: defined bytes
+        uint32_t word = 0xffffffffu;
+        if (whole) {
+            if (g_avx2 && cnt == 16) {
+                word = coarse_word_avx2(line);
+            } else {
+                uint32_t r[4][4];
+                std::memcpy(r, line, 64);
+                word = 0;
+                for (int c = 0; c < 4; ++c) {
+                    const uint32_t same = (r[0][c] & 0xffu) * 0x01010101u;
+                    const bool uniform = x0 + 4 * c + 4 <= L.w && r[0][c] == same && r[1][c] == same && r[2][c] == same && r[3][c] == same;
+                    word |= (uniform ? (r[0][c] & 0xffu) : 255u) << (8 * c);
                 }
             }
         }
+        const int cx0 = s * 4;  // first cell of the strip
+        const int ncell = L.cw - cx0 >= 4 ? 4 : L.cw - cx0;
+        uint8_t* co = j->coarse + (size_t)(cx0 >> 4) * L.cstrip_bytes + (cx0 & 15) + (size_t)cy * 16;
+        if (ncell == 4) std::memcpy(co, &word, 4);
+        else std::memcpy(co, &word, (size_t)ncell);
     }
+    if (L.cw & 15)  // the cells past the map's last cell column: defined bytes (the level goes into the pool as it is)
+        std::memset(j->coarse + (size_t)(L.cw >> 4) * L.cstrip_bytes + (size_t)cy * 16 + (L.cw & 15), 0, (size_t)(16 - (L.cw & 15)));
+    // the mixed cells (coarse byte 255) go to the stream as 16-byte blocks, by cell column; uniform cells are their coarse byte.  Cost ~
+    // the number of mixed cells: 16 cells are one compare + movemask.  table[cy] = where the cell row's blocks start.
+    constexpr int kMaxCs = 1024;  // coarse strips of a 65535-pixel row
+    uint16_t masks[kMaxCs];
+    const int ncs = (L.cw + 15) >> 4;
+    uint32_t n = 0;
+    for (int cs = 0; cs < ncs; ++cs) {
+        const uint8_t* co = j->coarse + (size_t)cs * L.cstrip_bytes + (size_t)cy * 16;
+        unsigned m;
+#if defined(__x86_64__)
+        m = (unsigned)_mm_movemask_epi8(_mm_cmpeq_epi8(_mm_loadu_si128(reinterpret_cast<const __m128i*>(co)), _mm_set1_epi8((char)255)));
+#else
+        m = 0;
+        for (int k = 0; k < 16; ++k) m |= (unsigned)(co[k] == 255) << k;
+#endif
+        masks[cs] = (uint16_t)m;  // padding cells are 0, never 255
+        n += (unsigned)__builtin_popcount(m);
+    }
+    if (tl.blocks.size() < ((size_t)tl.nblocks + n) * 16) tl.blocks.resize(std::max(tl.blocks.size() * 2, ((size_t)tl.nblocks + n) * 16));
+    tl.rows.push_back((uint32_t)cy);
+    tl.rows.push_back(tl.nblocks);
+    uint8_t* out = tl.blocks.data() + (size_t)tl.nblocks * 16;
+    tl.nblocks += n;
+    for (int cs = 0; cs < ncs && n; ++cs) {
+        for (unsigned m = masks[cs]; m; m &= m - 1) {
+            const int cx = cs * 16 + __builtin_ctz(m);
+            const uint8_t* q = lbase + (size_t)(cx >> 2) * 64 + (cx & 3) * 4;  // the cell's rows, 16 bytes apart
+            uint32_t r[4];
+            std::memcpy(&r[0], q, 4), std::memcpy(&r[1], q + 16, 4), std::memcpy(&r[2], q + 32, 4), std::memcpy(&r[3], q + 48, 4);
+            std::memcpy(out, r, 16);
+            out += 16;
+        }
+    }
+}
+
+// end of a thread's part in one call: room in the stream for all its blocks at once, and the table entries of its cell rows
+static void compact_flush(void* arg) {
+    PackJob* j = static_cast<PackJob*>(arg);
+    CompactTL& tl = compact_tl;
+    if (tl.rows.empty()) return;
+    const uint32_t first = tl.nblocks ? j->blocks.fetch_add(tl.nblocks, std::memory_order_relaxed) : 0u;
+    if (tl.nblocks) std::memcpy(j->stream + (size_t)first * 16, tl.blocks.data(), (size_t)tl.nblocks * 16);
+    for (size_t i = 0; i < tl.rows.size(); i += 2) j->table[tl.rows[i]] = first + tl.rows[i + 1];
+    tl.rows.clear();
+    tl.nblocks = 0;
 }
 
 template <typename T, unsigned ADD>
@@ -720,6 +831,12 @@ static void pack_part(void* arg, int part) {
 // segments (270 parts per 1080p map: +12 %), several bands per part (+0..12 %), and the bands that do not divide evenly
 // (135 = 16 x 8 + 7) handed out as single cell rows so that no thread idles at the end (+6.5 %: a part that does not continue a
 // thread's stream starts cold, 8 KB of prefetch distance behind).
+// The compact form (host_pack_map_compact) is cut into cell rows instead, 270 parts per 1080p map, still in contiguous shares (17 or
+// 16 per thread against 9 or 8 bands), with ONE reservation of stream room per thread and run of cell rows.  Measured step by step on
+// the GPU box (profiles/handover_shares_ab.md, ms per run of 200 maps against the step before): cell rows alone +0.7 (a locked add
+// per cell row on the stream's counter), one reservation per thread -0.7, the pool's join by parts on top 0 to -0.7 (bench.py, all
+// three against the parent: -0.54); bands with one reservation under the same pool are 0.3 slower than cell rows.  Removed again: a look at the join counter before helping (+0.4)
+// and keeping the workers awake through the vote's tail (nothing).  The pool form keeps bands: its strips are written in place.
 int host_pack_map(Workers* pool, const void* seg, int seg_dtype, const MapLayout& L, int bins, uint8_t* dst) {
     PackJob j;
     j.seg = seg;
@@ -764,19 +881,23 @@ int host_pack_map_compact(Workers* pool, const void* seg, int seg_dtype, const M
     j.coarse = rec + C.table_bytes;
     j.table = reinterpret_cast<uint32_t*>(rec);
     j.stream = rec + C.stream_off;
-    void (*fn)(void*, int) = seg_dtype == 0   ? pack_part<int32_t, 1u>
-                             : seg_dtype == 1 ? pack_part<int64_t, 1u>
-                             : seg_dtype == 2 ? pack_part<uint8_t, 0u>
-                                              : pack_part<uint8_t, 1u>;
-    std::memset(rec + (size_t)C.bands * 8, 0, C.table_bytes - (size_t)C.bands * 8);
+    void (*fn)(void*, int) = seg_dtype == 0   ? pack_cell_row<int32_t, 1u>
+                             : seg_dtype == 1 ? pack_cell_row<int64_t, 1u>
+                             : seg_dtype == 2 ? pack_cell_row<uint8_t, 0u>
+                                              : pack_cell_row<uint8_t, 1u>;
+    // the table's entries past the map's last cell row (an odd number of cell rows leaves one) and its padding: defined bytes
+    std::memset(rec + (size_t)L.ch * 4, 0, C.table_bytes - (size_t)L.ch * 4);
     // cell rows past the map (a coarse strip has room for a multiple of 8): defined bytes, like the cell columns past the
-    // map that the bands clear - the level goes into the pool as it is
+    // map that the cell rows clear - the level goes into the pool as it is
     const size_t row_room = (size_t)L.cstrip_bytes / 16;
     for (int cs = 0; cs * 16 < L.cw && row_room > (size_t)L.ch; ++cs)
         std::memset(j.coarse + (size_t)cs * L.cstrip_bytes + (size_t)L.ch * 16, 0, (row_room - (size_t)L.ch) * 16);
-    if (pool) pool->run(C.bands, fn, &j);
-    else
-        for (int b = 0; b < C.bands; ++b) fn(&j, b);
+    if (pool) {
+        pool->run(L.ch, fn, &j, compact_flush);
+    } else {
+        for (int cy = 0; cy < L.ch; ++cy) fn(&j, cy);
+        compact_flush(&j);
+    }
     *blocks = j.blocks.load();
     return j.bad.load() ? 1 : 0;
 }

@@ -34,7 +34,9 @@ public:
     Workers(const Workers&) = delete;
     Workers& operator=(const Workers&) = delete;
     int threads() const { return nthreads_; }
-    void run(int parts, void (*fn)(void*, int), void* arg);
+    // fin (optional): called with arg by every thread that ran parts, after the last part of each share it worked on (its own, one it
+    // helped with) and before those parts count as done: the place to publish what the parts collected per thread
+    void run(int parts, void (*fn)(void*, int), void* arg, void (*fin)(void*) = nullptr);
 
 private:
     struct Impl;
@@ -54,7 +56,8 @@ int host_pack_map(Workers* pool, const void* seg, int seg_dtype, const MapLayout
 //   [table_bytes, +coarse_bytes)         the coarse level exactly as it sits in the pool (padding zeroed)
 //   [stream_off, stream_off + 16*blocks) one 16-byte block (4 rows x 4 pixels, u8 bins) per MIXED 4x4 cell (coarse byte 255:
 //                                        the cell's pixels differ, or it sticks out of the map); inside a cell row by cell
-//                                        column, the cell rows in the order their workers reserved room (an atomic counter:
+//                                        column; a packer thread's cell rows follow each other, the threads' pieces lie in the
+//                                        order they reserved room (one atomic add per thread and contiguous run of cell rows:
 //                                        the order differs from run to run, the table says where)
 // Uniform cells travel as their coarse byte alone; the GPU rebuilds the full-resolution level (seg_expand_kernel).
 struct CompactLayout {
