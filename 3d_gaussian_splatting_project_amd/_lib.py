@@ -161,6 +161,9 @@ _SIGS = {
                                              C.c_void_p]),
     "gsx_debug_exclusive_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "gsx_debug_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "gsx_debug_bin": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]),
     "gsx_debug_spatial_order": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gsx_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "gsx_profile_reset": (C.c_int, [C.c_void_p]),

@@ -817,6 +817,95 @@ int gsx_debug_ranges(gsx_ctx* ctx, const uint32_t* sorted_keys, int64_t capacity
     return GSX_OK;
 }
 
+// Everything comes from the caller and is checked here, on the host, before a kernel sees it: the kernels trust the pre pass and
+// the level-1 sort for in-range indices and rectangles, a test's arrays get no such trust.
+int gsx_debug_bin(gsx_ctx* ctx, int64_t n, const uint32_t* tile_rect, const float* rec, const uint32_t* by_depth, int64_t len,
+                  int64_t nvis, int64_t div0, int64_t div1, int64_t m_cap, int32_t height, int32_t tiles_x, int32_t tiles_y,
+                  int32_t bin32, int32_t exact, const uint8_t* sat, int64_t pair_cap, uint32_t* count_out, uint64_t* total_out,
+                  uint32_t* keys_out, uint32_t* vals_out) {
+    CTX_OR_FAIL(ctx);
+    if (n < 1 || n > ((int64_t)1 << 28) || !tile_rect || !by_depth || len < 0 || len > ((int64_t)1 << 31) || nvis < 0 || nvis > len ||
+        !count_out || !total_out || !keys_out || !vals_out)
+        return gsx::fail(c, GSX_E_INVALID, "debug_bin: bad arguments (n, len, nvis <= len, NULL array)");
+    if (tiles_x < 1 || tiles_x > 256 || tiles_y < 1 || tiles_y > 256 || height < 1)
+        return gsx::fail(c, GSX_E_INVALID, "debug_bin: %d x %d tiles, height %d: 1..256 tiles per side", tiles_x, tiles_y, height);
+    if (div0 < 0 || div1 < 1) return gsx::fail(c, GSX_E_INVALID, "debug_bin: div0 %lld < 0 or div1 %lld < 1", (long long)div0, (long long)div1);
+    const int64_t phase_len = nvis / div1 - (div0 ? nvis / div0 : 0);
+    if (m_cap < 1 || m_cap > ((int64_t)1 << 31) || m_cap < phase_len)
+        return gsx::fail(c, GSX_E_INVALID, "debug_bin: m_cap %lld does not cover the phase's %lld splats", (long long)m_cap, (long long)phase_len);
+    if (pair_cap < 1 || pair_cap > 0x7fffffff) return gsx::fail(c, GSX_E_INVALID, "debug_bin: pair_cap %lld outside [1, 2^31 - 1]", (long long)pair_cap);
+    if (bin32 && exact) return gsx::fail(c, GSX_E_INVALID, "debug_bin: bin32 with exact is never launched");
+    if (exact && !rec) return gsx::fail(c, GSX_E_INVALID, "debug_bin: exact needs rec");
+    for (int64_t j = 0; j < nvis; ++j)
+        if ((int64_t)by_depth[j] >= n) return gsx::fail(c, GSX_E_INVALID, "debug_bin: by_depth[%lld] = %u >= n", (long long)j, by_depth[j]);
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t r = tile_rect[i], tx0 = r & 255u, tx1 = (r >> 8) & 255u, ty0 = (r >> 16) & 255u, ty1 = r >> 24;
+        if (tx1 >= tx0 && ty1 >= ty0 && ((int)tx1 >= tiles_x || (int)ty1 >= tiles_y))
+            return gsx::fail(c, GSX_E_INVALID, "debug_bin: rectangle %lld (%u..%u, %u..%u) outside the frame's tiles", (long long)i, tx0, tx1, ty0, ty1);
+    }
+    GSX_HIP(c, hipSetDevice(c->device));
+    const int lists = bin32 ? ((tiles_x + 1) / 2) * ((tiles_y + 1) / 2) : tiles_x * tiles_y;
+    const size_t sat_bytes = bin32 ? 4 * (size_t)lists : (size_t)lists;
+    const size_t nb = sizeof(uint32_t) * (size_t)n, lb = sizeof(uint32_t) * (size_t)(len > 0 ? len : 1);
+    const size_t mb = sizeof(uint32_t) * (size_t)m_cap, pb = sizeof(uint32_t) * (size_t)pair_cap;
+    gsx::DevBuf drect, drec, dorder, dsat, dcount, doffset, dseq, dkeys, dvals, dsmall;
+    GSX_HIP(c, drect.ensure(nb));
+    if (rec) GSX_HIP(c, drec.ensure(12 * sizeof(float) * (size_t)n));
+    GSX_HIP(c, dorder.ensure(lb));
+    if (sat) GSX_HIP(c, dsat.ensure(sat_bytes));
+    GSX_HIP(c, dcount.ensure(mb));
+    GSX_HIP(c, doffset.ensure(mb));
+    GSX_HIP(c, dseq.ensure(mb));
+    GSX_HIP(c, dkeys.ensure(pb));
+    GSX_HIP(c, dvals.ensure(pb));
+    GSX_HIP(c, dsmall.ensure(16));  // u64 nvis, u64 pair total
+    const unsigned long long nvis_host = (unsigned long long)nvis;
+    GSX_HIP(c, hipMemcpyAsync(drect.p, tile_rect, nb, hipMemcpyHostToDevice, c->stream));
+    if (rec) GSX_HIP(c, hipMemcpyAsync(drec.p, rec, 12 * sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (len > 0) GSX_HIP(c, hipMemcpyAsync(dorder.p, by_depth, sizeof(uint32_t) * (size_t)len, hipMemcpyHostToDevice, c->stream));
+    if (sat) GSX_HIP(c, hipMemcpyAsync(dsat.p, sat, sat_bytes, hipMemcpyHostToDevice, c->stream));
+    GSX_HIP(c, hipMemsetAsync(dcount.p, 0xff, mb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(doffset.p, 0xff, mb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(dseq.p, 0xff, mb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(dkeys.p, 0xff, pb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(dvals.p, 0xff, pb, c->stream));
+    GSX_HIP(c, hipMemsetAsync(dsmall.p, 0xff, 16, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(dsmall.p, &nvis_host, 8, hipMemcpyHostToDevice, c->stream));
+    gsx::DebugBinArgs a;
+    a.nvis_dev = dsmall.as<unsigned long long>();
+    a.div0 = div0;
+    a.div1 = div1;
+    a.m_cap = m_cap;
+    a.by_depth = dorder.as<uint32_t>();
+    a.tile_rect = drect.as<uint32_t>();
+    a.rec = rec ? drec.as<float4>() : nullptr;
+    a.H = height;
+    a.tiles_x = tiles_x;
+    a.bin32 = bin32 ? 1 : 0;
+    a.exact = exact ? 1 : 0;
+    a.sat = sat ? dsat.as<uint8_t>() : nullptr;
+    a.count = dcount.as<uint32_t>();
+    a.offset = doffset.as<uint32_t>();
+    a.rect_seq = dseq.as<uint32_t>();
+    a.keys = dkeys.as<uint32_t>();
+    a.vals = dvals.as<uint32_t>();
+    a.total_dev = dsmall.as<unsigned long long>() + 1;
+    a.pair_cap = (unsigned long long)pair_cap;
+    int rc = gsx::debug_bin(c, a);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // nvis_host and the buffers go away
+        return rc;
+    }
+    unsigned long long total = 0;
+    GSX_HIP(c, hipMemcpyAsync(count_out, dcount.p, mb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(&total, a.total_dev, 8, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(keys_out, dkeys.p, pb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(vals_out, dvals.p, pb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    *total_out = (uint64_t)total;
+    return GSX_OK;
+}
+
 int gsx_debug_spatial_order(gsx_ctx* ctx, uint32_t* perm_out) {
     CTX_OR_FAIL(ctx);
     if (!perm_out) return gsx::fail(c, GSX_E_INVALID, "debug_spatial_order: perm_out is NULL");

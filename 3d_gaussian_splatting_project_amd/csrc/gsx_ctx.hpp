@@ -394,6 +394,20 @@ int render_debug(Ctx* c, uint8_t* buffer_out, uint32_t* order_out, uint32_t* tex
 int debug_render_pre(Ctx* c, int nv, const gsx_camera* cams, int W, int H, int multi, int compact, const gsx_debug_pre_view* out);
 int debug_exclusive_scan(Ctx* c, const uint32_t* in, uint32_t* out, long long n, unsigned long long* grand_dev);  // test hook: exclusive_scan_u32
 int debug_ranges(Ctx* c, const uint32_t* keys, const unsigned long long* total_dev, long long cap, int nlists, int2* ranges);  // test hook: ranges_kernel as a frame launches it
+// test hook: bin_kernel COUNT -> exclusive_scan_u32 -> bin_kernel EMIT of one depth phase as a frame launches them (device pointers)
+struct DebugBinArgs {
+    const unsigned long long* nvis_dev;
+    long long div0, div1, m_cap;
+    const uint32_t* by_depth;
+    const uint32_t* tile_rect;
+    const float4* rec;
+    int H, tiles_x, bin32, exact;
+    const uint8_t* sat;
+    uint32_t *count, *offset, *rect_seq, *keys, *vals;
+    unsigned long long* total_dev;
+    unsigned long long pair_cap;
+};
+int debug_bin(Ctx* c, const DebugBinArgs& a);
 void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, int img_w, int img_h);
 
 }  // namespace gsx

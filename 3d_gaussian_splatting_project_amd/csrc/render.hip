@@ -968,6 +968,27 @@ int debug_ranges(Ctx* c, const uint32_t* keys, const unsigned long long* total_d
     return GSX_OK;
 }
 
+// test hook (gsx_debug_bin): one depth phase's COUNT -> scan -> EMIT with render_view's grids and arguments, in the caller's buffers
+int debug_bin(Ctx* c, const DebugBinArgs& a) {
+    const int lists_x = a.bin32 ? (a.tiles_x + 1) / 2 : a.tiles_x;
+    const auto count_k = a.bin32 ? bin_kernel<false, true> : bin_kernel<false, false>;
+    const auto emit_k = a.bin32 ? bin_kernel<true, true> : bin_kernel<true, false>;
+    const long long m = a.m_cap;
+    hipLaunchKernelGGL(count_k, dim3(grid_for(m)), dim3(kRB), 0, c->stream,
+                       a.nvis_dev, a.div0, a.div1, m, a.by_depth, a.tile_rect, a.rec, (float)a.H, lists_x,
+                       a.exact, a.sat, a.count, (const uint32_t*)nullptr,
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, (const unsigned long long*)nullptr, 0ull, a.rect_seq);
+    GSX_HIP(c, hipGetLastError());
+    const int rc = exclusive_scan_u32(c, a.count, a.offset, m, a.total_dev);
+    if (rc) return rc;
+    hipLaunchKernelGGL(emit_k, dim3(grid_for(m)), dim3(kRB), 0, c->stream,
+                       a.nvis_dev, a.div0, a.div1, m, a.by_depth, a.tile_rect, a.rec, (float)a.H, lists_x,
+                       a.exact, a.sat, (uint32_t*)nullptr, a.offset,
+                       a.keys, a.vals, a.total_dev, a.pair_cap, a.rect_seq);
+    GSX_HIP(c, hipGetLastError());
+    return GSX_OK;
+}
+
 int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const float* rot, const float* opacity,
                   const float* f_dc, const int32_t* labels) {
     GSX_HIP(c, hipSetDevice(c->device));

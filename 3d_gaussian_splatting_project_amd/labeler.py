@@ -589,6 +589,28 @@ class Context:
         check(self._lib.gsx_debug_ranges(self.h, k.ctypes.data, len(k), int(total), int(nlists), out.ctypes.data), self.h)
         return out
 
+    def debug_bin(self, tile_rect, rec, by_depth, nvis, div0, div1, m_cap, H, tiles_x, tiles_y, bin32=False, exact=False, sat=None,
+                  pair_cap=1):
+        """One depth phase's binning as a frame runs it, on the caller's arrays alone (test hook, gsx_debug_bin): tile_rect (n,) u32,
+        rec (n,12) f32 or None, by_depth (len,) u32, sat None or u8 -> (count (m_cap,) u32, pair total as a Python int, keys
+        (pair_cap,) u32, vals (pair_cap,) u32); what the kernels did not write is 0xFF bytes."""
+        rect = np.ascontiguousarray(tile_rect, dtype=np.uint32)
+        order = np.ascontiguousarray(by_depth, dtype=np.uint32)
+        r = None if rec is None else np.ascontiguousarray(rec, dtype=np.float32)
+        s = None if sat is None else np.ascontiguousarray(sat, dtype=np.uint8)
+        lists = ((tiles_x + 1) // 2) * ((tiles_y + 1) // 2) * 4 if bin32 else tiles_x * tiles_y
+        if (r is not None and r.size != 12 * len(rect)) or (s is not None and s.size != lists):
+            raise ValueError("debug_bin: rec must hold 12 floats per splat, sat one byte per tile (bin32: four per bin)")
+        count = np.empty(max(int(m_cap), 0), np.uint32)
+        keys = np.empty(max(int(pair_cap), 0), np.uint32)
+        vals = np.empty(max(int(pair_cap), 0), np.uint32)
+        total = C.c_uint64(0)
+        check(self._lib.gsx_debug_bin(self.h, len(rect), rect.ctypes.data, None if r is None else r.ctypes.data, order.ctypes.data,
+                                      len(order), int(nvis), int(div0), int(div1), int(m_cap), int(H), int(tiles_x), int(tiles_y),
+                                      1 if bin32 else 0, 1 if exact else 0, None if s is None else s.ctypes.data, int(pair_cap),
+                                      count.ctypes.data, C.byref(total), keys.ctypes.data, vals.ctypes.data), self.h)
+        return count, int(total.value), keys, vals
+
     def spatial_order(self):
         """The Morton order of the last upload_positions: perm[i] = uploaded index of slot i (test hook, gsx_debug_spatial_order)."""
         perm = np.empty(int(self._lib.gsx_num_gaussians(self.h)), np.uint32)

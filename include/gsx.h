@@ -557,6 +557,28 @@ int gsx_debug_exclusive_scan(gsx_ctx* ctx, const uint32_t* in, int64_t n, uint32
  * ranges_out (nlists x 2 int32): [first, last + 1) slot of every key that occurs below nlists, (0, 0) for the others */
 int gsx_debug_ranges(gsx_ctx* ctx, const uint32_t* sorted_keys, int64_t capacity, int64_t total, int32_t nlists,
                      int32_t* ranges_out);
+/* test hook: one depth phase's binning as a frame runs it (csrc/render.hip: bin_kernel COUNT -> exclusive_scan_u32 -> bin_kernel
+ * EMIT, the grids and arguments of gsx_render_view) on the caller's arrays alone - no uploaded scene is needed and none of the
+ * context's frame buffers or counters is touched.
+ *   tile_rect  n u32            tx0 | tx1 << 8 | ty0 << 16 | ty1 << 24 (tx1 < tx0 or ty1 < ty0: no tile)
+ *   rec        n x 12 f32       the pre pass's records (cx, cy, g0, g1, ..); NULL allowed when exact == 0
+ *   by_depth   len u32          the depth order; its first nvis entries are the splats the level-1 sort kept.  nvis goes to the
+ *                               device as the u64 the kernel reads; the phase is [nvis / div0, nvis / div1) of the order (div0 = 0:
+ *                               from the start), the launches cover m_cap slots
+ *   height, tiles_x, tiles_y    the frame's height in pixels and its size in 16x16 tiles; bin32 != 0: the candidates are 32x32 bins
+ *                               (the kernels then see (tiles_x + 1) / 2 lists per row); exact: the option "exact_cull"
+ *   sat        NULL, or tiles_x * tiles_y bytes; with bin32 four bytes per bin, (tiles_x + 1) / 2 * ((tiles_y + 1) / 2) bins
+ *   pair_cap                    capacity of the pair arrays
+ * Outputs, all preset to 0xFF bytes: count_out m_cap u32 (pairs per slot of the phase), *total_out (64 bits), keys_out and
+ * vals_out pair_cap u32 each (written only when the total fits pair_cap).
+ * GSX_E_INVALID, before any launch, for whatever could make a kernel index outside these arrays: an entry of by_depth[0, nvis)
+ * >= n, nvis > len, a non-empty rectangle outside tiles_x x tiles_y, tiles_x or tiles_y outside [1, 256], div1 < 1, div0 < 0,
+ * m_cap < 1 or below the phase's length, pair_cap outside [1, 2^31 - 1], bin32 together with exact (gsx_render_view never
+ * launches that pair), exact without rec, a NULL array */
+int gsx_debug_bin(gsx_ctx* ctx, int64_t n, const uint32_t* tile_rect, const float* rec, const uint32_t* by_depth, int64_t len,
+                  int64_t nvis, int64_t div0, int64_t div1, int64_t m_cap, int32_t height, int32_t tiles_x, int32_t tiles_y,
+                  int32_t bin32, int32_t exact, const uint8_t* sat, int64_t pair_cap, uint32_t* count_out, uint64_t* total_out,
+                  uint32_t* keys_out, uint32_t* vals_out);
 /* test hook: the Morton order of the last upload with the option "spatial_sort" on - perm_out[i] (gsx_num_gaussians
  * entries) = the uploaded index of the position in slot i.  GSX_E_INVALID when the context holds no sorted order (fewer
  * than two positions, or the option was off) */
