@@ -147,6 +147,7 @@ void gsx_destroy(gsx_ctx* ctx) {
         b->release();
     gsx::render_release_twin(c);
     gsx::vote_release_host(c);
+    gsx::iou_release(c);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -167,6 +168,7 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
     const std::string k(name);
     if (k == "spatial_sort") c->opt_spatial_sort = value != 0;
     else if (k == "nn_brute") c->opt_nn_brute = value != 0;
+    else if (k == "iou_table_lds") c->opt_iou_table_lds = value != 0;
     else if (k == "xcd_swizzle") {
         if (value < 0 || value > 65536) return gsx::fail(c, GSX_E_INVALID, "set_option: xcd_swizzle must be in [0,65536]");
         c->opt_xcd_swizzle = (int)value;
@@ -627,6 +629,42 @@ int gsx_region_growing(gsx_ctx* ctx, int64_t n, const float* points, int64_t k_n
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::region_growing(c, n, points, k_normals, k, residual_threshold, angle_threshold, labels_out,
                                normals_out, residuals_out, n_regions_out); });
+}
+
+int gsx_iou_masks(gsx_ctx* ctx, int32_t n_masks, const void* const* masks, int32_t mask_dtype, int32_t n_gt, const void* const* gts,
+                  int32_t gt_dtype, int32_t h, int32_t w, int64_t* inter_out, int64_t* area_masks_out, int64_t* area_gt_out, double* iou_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::iou_masks(c, false, n_masks, masks, mask_dtype, n_gt, gts, gt_dtype, h, w, inter_out,
+                                                               area_masks_out, area_gt_out, iou_out); });
+}
+int gsx_iou_masks_device(gsx_ctx* ctx, int32_t n_masks, const void* const* masks_dev, int32_t mask_dtype, int32_t n_gt,
+                         const void* const* gts_dev, int32_t gt_dtype, int32_t h, int32_t w, int64_t* inter_out, int64_t* area_masks_out,
+                         int64_t* area_gt_out, double* iou_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::iou_masks(c, true, n_masks, masks_dev, mask_dtype, n_gt, gts_dev, gt_dtype, h, w, inter_out,
+                                                               area_masks_out, area_gt_out, iou_out); });
+}
+int gsx_iou_label_maps(gsx_ctx* ctx, int32_t n_pairs, const void* const* pred, int32_t pred_dtype, int32_t n_pred_classes,
+                       const void* const* gt, int32_t gt_dtype, int32_t n_gt_classes, int32_t h, int32_t w, int64_t* table_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::iou_label_maps(c, false, n_pairs, pred, pred_dtype, n_pred_classes, gt, gt_dtype,
+                                                                    n_gt_classes, h, w, table_out); });
+}
+int gsx_iou_label_maps_device(gsx_ctx* ctx, int32_t n_pairs, const void* const* pred_dev, int32_t pred_dtype, int32_t n_pred_classes,
+                              const void* const* gt_dev, int32_t gt_dtype, int32_t n_gt_classes, int32_t h, int32_t w, int64_t* table_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::iou_label_maps(c, true, n_pairs, pred_dev, pred_dtype, n_pred_classes, gt_dev, gt_dtype,
+                                                                    n_gt_classes, h, w, table_out); });
+}
+int gsx_masks_top_index(gsx_ctx* ctx, int32_t n_masks, const void* const* masks, int32_t mask_dtype, int32_t h, int32_t w,
+                        int32_t* index_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::masks_top_index(c, n_masks, masks, mask_dtype, h, w, index_out); });
+}
+int gsx_debug_iou_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_iou_constants: NULL argument");
+    gsx::iou_constants(out);
+    return GSX_OK;
 }
 
 int gsx_vote_culled(gsx_ctx* ctx, int64_t* wave_views, int32_t reset) {

@@ -306,6 +306,20 @@ struct Ctx {
     DevBuf nn_pts, nn_cs;                // float4[n] (x, y, z, index) in cell order; u32[cells + 1]
     DevBuf nn_out, nn_flag;              // double normals[3n] | residuals[n] | moments[9n] (before the search: the raw points of the finite check); int
 
+    // IoU evaluation (iou.hip): buffers only grow
+    int opt_iou_table_lds = 1;           // label-map tables of up to 40000 entries are counted in LDS per workgroup (0: on the global table)
+    DevBuf iou_planes;                   // u64 [masks + ground truths][ceil(h w / 64)]: the bit planes
+    DevBuf iou_cnt;                      // u64: areas of the masks, of the ground truths, then inter[m][g]
+    DevBuf iou_ptrs;                     // the device copy of a call's pointer arrays
+    DevBuf iou_table;                    // u64 [pair][P + 1][G + 1], then u32 [pair]: lowest flat index out of range
+    DevBuf iou_top;                      // int32 [h w]
+    DevBuf iou_raw[2];                   // host inputs: the two raw masks (or pairs of label maps) in flight ...
+    void* iou_pin[2] = {nullptr, nullptr};  // ... and the pinned staging pair they come through
+    size_t iou_pin_cap[2] = {0, 0};
+    hipEvent_t iou_ev[2] = {nullptr, nullptr};  // recorded behind a slot's H2D copy
+    bool iou_ev_pending[2] = {false, false};
+    int iou_slot = 0;
+
     // profiling
     bool prof_on = false;
     std::vector<std::string> prof_names;
@@ -408,6 +422,14 @@ struct DebugBinArgs {
     unsigned long long pair_cap;
 };
 int debug_bin(Ctx* c, const DebugBinArgs& a);
+// iou.hip
+int iou_masks(Ctx* c, bool device, int n_masks, const void* const* masks, int mask_dtype, int n_gt, const void* const* gts, int gt_dtype,
+              int h, int w, int64_t* inter_out, int64_t* area_masks_out, int64_t* area_gt_out, double* iou_out);
+int iou_label_maps(Ctx* c, bool device, int n_pairs, const void* const* pred, int pred_dtype, int n_pred_classes, const void* const* gt,
+                   int gt_dtype, int n_gt_classes, int h, int w, int64_t* table_out);
+int masks_top_index(Ctx* c, int n_masks, const void* const* masks, int mask_dtype, int h, int w, int32_t* index_out);
+void iou_release(Ctx* c);  // pinned staging pair and its events (gsx_destroy)
+void iou_constants(int32_t out[8]);
 void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, int img_w, int img_h);
 
 }  // namespace gsx

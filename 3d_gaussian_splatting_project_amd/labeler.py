@@ -617,6 +617,56 @@ class Context:
         check(self._lib.gsx_debug_spatial_order(self.h, perm.ctypes.data), self.h)
         return perm
 
+    # -- IoU evaluation (Image_Segmentation/evaluation.py; csrc/iou.hip, csrc/iou_host.cpp) -------------------------------------
+    def _iou_call(self, host_fn, dev_fn, lists, rest):
+        """lists: [(device, items, dtype), ...] of one kind (all host or all device); rest(ptr arrays and dtypes) -> arguments"""
+        device = lists[0][0]
+        arrs = [(C.c_void_p * len(items))(*[t.data_ptr() if device else t.ctypes.data for t in items]) for _, items, _ in lists]
+        if device:   # ONE fence for the whole call: the ctx stream is not torch's, and the call waits for its own results anyway
+            import torch
+            torch.cuda.current_stream().synchronize()
+        check((dev_fn if device else host_fn)(self.h, *rest(arrs)), self.h)
+
+    def iou_masks(self, masks, ground_truths):
+        """IoU (evaluation.py:24-35) of every mask with every ground truth.  masks / ground_truths: lists of 2-D arrays (numpy, or
+        torch tensors on this GPU) or one 3-D array each; a pixel is set iff value != 0.  Inputs are not written.
+        Returns (iou float64 (M, G), inter int64 (M, G), area_masks int64 (M,), area_gt int64 (G,)); iou is NaN where both are empty."""
+        m, g = _iou_same_side(_iou_list(masks, "masks"), _iou_list(ground_truths, "ground_truths"))
+        (h, w), M, G = _iou_shape(m[1] + g[1]), len(m[1]), len(g[1])
+        iou, inter = np.empty((M, G), np.float64), np.empty((M, G), np.int64)
+        am, ag = np.empty(M, np.int64), np.empty(G, np.int64)
+        self._iou_call(self._lib.gsx_iou_masks, self._lib.gsx_iou_masks_device, [m, g],
+                       lambda a: (M, a[0], m[2], G, a[1], g[2], h, w, inter.ctypes.data, am.ctypes.data, ag.ctypes.data, iou.ctypes.data))
+        return iou, inter, am, ag
+
+    def best_ious(self, masks, ground_truths):
+        """get_ious_from_masks (evaluation.py:38-56): [(max_iou, gt_idx), ...], one per mask; (0, 0) for a mask without a positive IoU."""
+        best, idx = iou_best(self.iou_masks(masks, ground_truths)[0])
+        return [(0, 0) if b == 0 else (b, int(i)) for b, i in zip(best, idx)]
+
+    def label_map_tables(self, preds, gts, n_pred_classes, n_gt_classes, packed_u8=False):
+        """Contingency tables of pairs of label maps (labels -1 .. n-1; any integer dtype; numpy or torch tensors on this GPU):
+        int64 (n_pairs, P + 1, G + 1), entry [a, b] = pixels with pred label a - 1 and gt label b - 1.  packed_u8: uint8 maps hold
+        label + 1.  A label out of range raises ValueError naming the pair and the lowest flat pixel index."""
+        p, g = _iou_same_side(_iou_list(preds, "preds", seg=True, packed_u8=packed_u8), _iou_list(gts, "gts", seg=True, packed_u8=packed_u8))
+        if len(p[1]) != len(g[1]):
+            raise ValueError(f"label_map_tables: {len(p[1])} preds for {len(g[1])} gts")
+        (h, w), n = _iou_shape(p[1] + g[1]), len(p[1])
+        P, G = int(n_pred_classes), int(n_gt_classes)
+        table = np.empty((n, max(P, 0) + 1, max(G, 0) + 1), np.int64)
+        self._iou_call(self._lib.gsx_iou_label_maps, self._lib.gsx_iou_label_maps_device, [p, g],
+                       lambda a: (n, a[0], p[2], P, a[1], g[2], G, h, w, table.ctypes.data))
+        return table
+
+    def masks_top_index(self, masks):
+        """int32 (H, W): the highest list index whose mask is set at the pixel, or -1 - who owns the pixel in
+        generate_segmentation_map (evaluation.py:65-67)."""
+        m = _iou_list(masks, "masks", to_host=True)
+        h, w = _iou_shape(m[1])
+        out = np.empty((h, w), np.int32)
+        self._iou_call(self._lib.gsx_masks_top_index, None, [m], lambda a: (len(m[1]), a[0], m[2], h, w, out.ctypes.data))
+        return out
+
     def synchronize(self):
         check(self._lib.gsx_synchronize(self.h), self.h)
         self._keep_alive.clear()
@@ -741,3 +791,134 @@ def region_grow(normals, residuals, knn, residual_threshold=0.1, angle_threshold
     check(_lib.lib().gsx_region_grow(len(nrm), nrm.ctypes.data, res.ctypes.data, nb.ctypes.data, nb.shape[1], float(residual_threshold),
                                      float(angle_threshold), labels.ctypes.data, C.byref(nreg)))
     return labels, int(nreg.value)
+
+
+# -- IoU evaluation: input normalisation and the host-only helpers --------------------------------------------------------------------
+_MASK_NP = {"u1": _lib.GSX_MASK_U8, "i4": _lib.GSX_MASK_I32, "i8": _lib.GSX_MASK_I64, "f4": _lib.GSX_MASK_F32, "f8": _lib.GSX_MASK_F64}
+_MASK_NP_AS = {"b1": ("view", np.uint8), "i1": ("view", np.uint8), "i2": ("to", np.int32), "u2": ("to", np.int32), "u4": ("view", np.int32),
+               "u8": ("view", np.int64), "f2": ("to", np.float32)}   # same width: the bits decide "!= 0"; narrower: widened exactly
+
+
+def _iou_mask_np(a):
+    a = np.ascontiguousarray(a)
+    key = a.dtype.str[1:] if a.dtype.kind in "buif" else ""
+    how = _MASK_NP_AS.get(key)
+    if how:
+        a = a.view(how[1]) if how[0] == "view" else a.astype(how[1])
+    elif key not in _MASK_NP:
+        a = (a != 0).view(np.uint8)
+    return a, _MASK_NP[a.dtype.str[1:]]
+
+
+def _iou_mask_torch(t):
+    import torch
+    t = t.contiguous()
+    if t.dtype in (torch.bool, torch.int8):
+        t = t.view(torch.uint8)
+    elif t.dtype == torch.int16:
+        t = t.to(torch.int32)
+    elif t.dtype in (torch.float16, torch.bfloat16):
+        t = t.to(torch.float32)
+    code = {torch.uint8: _lib.GSX_MASK_U8, torch.int32: _lib.GSX_MASK_I32, torch.int64: _lib.GSX_MASK_I64,
+            torch.float32: _lib.GSX_MASK_F32, torch.float64: _lib.GSX_MASK_F64}.get(t.dtype)
+    if code is None:
+        t, code = (t != 0).view(torch.uint8), _lib.GSX_MASK_U8
+    return t, code
+
+
+def _iou_list(x, what, seg=False, packed_u8=False, to_host=False):
+    """-> (device, [2-D contiguous arrays or tensors of ONE supported dtype], dtype code)"""
+    if hasattr(x, "data_ptr") or isinstance(x, np.ndarray):
+        if x.ndim not in (2, 3):
+            raise ValueError(f"{what}: expected a list of 2-D arrays or one 3-D array")
+        x = [x] if x.ndim == 2 else list(x)
+    x = list(x)
+    if not x:
+        raise ValueError(f"{what}: empty list")
+    device = all(hasattr(t, "data_ptr") and t.is_cuda for t in x) and not to_host
+    if not device:
+        x = [t.detach().cpu().numpy() if hasattr(t, "data_ptr") else np.asarray(t) for t in x]
+    if any(t.ndim != 2 for t in x):
+        raise ValueError(f"{what}: every entry must be 2-D")
+    if seg:
+        out, codes = [], []
+        for t in x:
+            if device:
+                t = t.contiguous()
+                code = Context._TORCH_DT.get(str(t.dtype))
+                if code is None:
+                    import torch
+                    t, code = t.to(torch.int32), _lib.GSX_SEG_I32
+            else:
+                code = Context._NP_DT.get(t.dtype)
+                if code is None:
+                    t, code = t.astype(np.int32), _lib.GSX_SEG_I32
+                t = np.ascontiguousarray(t)
+            if packed_u8 and code == _lib.GSX_SEG_U8_LABELS:
+                code = _lib.GSX_SEG_U8
+            out.append(t)
+            codes.append(code)
+        if len(set(codes)) > 1:   # mixed dtypes: int64 holds them all (a packed uint8 map is unpacked on the way)
+            wide = [t.long() if device else t.astype(np.int64) for t in out]
+            out = [t - 1 if c == _lib.GSX_SEG_U8 else t for t, c in zip(wide, codes)]
+            codes = [_lib.GSX_SEG_I64]
+        return device, out, codes[0]
+    pairs = [(_iou_mask_torch if device else _iou_mask_np)(t) for t in x]
+    if len({c for _, c in pairs}) > 1:   # mixed dtypes: every non-zero value stays non-zero as a double, and -0.0 stays -0.0
+        pairs = [((t.double() if device else t.astype(np.float64)), _lib.GSX_MASK_F64) for t, _ in pairs]
+    return device, [t for t, _ in pairs], pairs[0][1]
+
+
+def _iou_same_side(a, b):
+    """both lists on the host or both on the device: a device list next to a host list comes down"""
+    if a[0] == b[0]:
+        return a, b
+    down = lambda l: (False, [np.ascontiguousarray(t.cpu().numpy()) for t in l[1]], l[2]) if l[0] else l
+    return down(a), down(b)
+
+
+def _iou_shape(items):
+    shape = tuple(items[0].shape)
+    for t in items:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"all masks / maps of a call must share one shape: {tuple(t.shape)} next to {shape}")
+    return shape
+
+
+def iou_from_counts(inter, area_a, area_b):
+    """inter / (area_a + area_b - inter) as the reference divides (evaluation.py:35), elementwise over int64 arrays of one
+    shape; NaN where the union is empty.  Host only."""
+    inter = np.ascontiguousarray(inter, np.int64)
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(area_a, np.int64), inter.shape))
+    b = np.ascontiguousarray(np.broadcast_to(np.asarray(area_b, np.int64), inter.shape))
+    out = np.empty(inter.shape, np.float64)
+    check(_lib.lib().gsx_iou_from_counts(inter.size, inter.ctypes.data, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+    return out
+
+
+def iou_from_table(table):
+    """float64 (..., P + 1, G + 1) from contingency tables: entry [a, b] = n_ab / (row_a + col_b - n_ab), which is exactly
+    IoU(pred == a - 1, gt == b - 1) of the reference (evaluation.py:24-35); NaN where neither label occurs.  Host only."""
+    t = np.asarray(table, np.int64)
+    if t.ndim < 2:
+        raise ValueError("iou_from_table: a table has at least two axes")
+    return iou_from_counts(t, t.sum(axis=-1, keepdims=True), t.sum(axis=-2, keepdims=True))
+
+
+def iou_best(iou):
+    """The best match of get_ious_from_masks (evaluation.py:44-54) over iou (M, G): (best float64 (M,), gt_idx int32 (M,)).
+    Strict '>' from (0, gt 0): the first of equal maxima wins, NaN never wins, no positive IoU gives (0, 0).  Host only."""
+    iou = np.ascontiguousarray(iou, np.float64)
+    if iou.ndim != 2:
+        raise ValueError("iou_best: iou must be 2-D (masks, ground truths)")
+    best, idx = np.empty(iou.shape[0], np.float64), np.empty(iou.shape[0], np.int32)
+    check(_lib.lib().gsx_iou_best(iou.shape[0], iou.shape[1], iou.ctypes.data, best.ctypes.data, idx.ctypes.data))
+    return best, idx
+
+
+def iou_constants():
+    """Test hook, host only: the units the IoU kernels are built on (gsx_debug_iou_constants)."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_iou_constants(out.ctypes.data))
+    names = ("load_bytes", "word_bits", "wave_tile", "block_tile", "pair_tile", "pair_chunk_words", "table_lds_max", "table_run")
+    return dict(zip(names, (int(v) for v in out)))

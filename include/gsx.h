@@ -56,6 +56,17 @@ typedef enum gsx_seg_dtype {
                         * as an 8-bit image; it cannot express -1)                          */
 } gsx_seg_dtype;
 
+/* element type of a binary mask handed to gsx_iou_masks* / gsx_masks_top_index (ev.py = Image_Segmentation/evaluation.py).
+ * A pixel is SET iff value != 0 (ev.py:29-30), compared on the whole element: NaN, infinities, denormals, 256 and 2^32 are
+ * set, -0.0 is not. */
+typedef enum gsx_mask_dtype {
+    GSX_MASK_U8 = 0,  /* uint8, also numpy / torch bool */
+    GSX_MASK_I32 = 1,
+    GSX_MASK_I64 = 2,
+    GSX_MASK_F32 = 3,
+    GSX_MASK_F64 = 4
+} gsx_mask_dtype;
+
 /* ---------------------------------------------------------------------------------------------
  * context
  * ------------------------------------------------------------------------------------------- */
@@ -171,7 +182,10 @@ int gsx_synchronize(gsx_ctx* ctx);
  *                               its 16 pixels share, or 255) and look a vote up there first; only lanes that hit a
  *                               mixed cell read the full-resolution map.  Same labels; a wave then touches ~3 cache
  *                               lines per view instead of ~16 (HBM traffic per launch 5.2 GB -> 0.5 GB).  Needs
- *                               n_classes <= 254, unit scale and "seg_tiled"; otherwise the one-level path runs */
+ *                               n_classes <= 254, unit scale and "seg_tiled"; otherwise the one-level path runs
+ *   "iou_table_lds" (default 1) gsx_iou_label_maps*: a table of up to 40000 entries is counted in a u32 copy in LDS per
+ *                               workgroup and flushed once; 0 = every add goes to the global u64 table (the path of larger
+ *                               tables).  Same tables */
 int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value);
 /* the current value of an option that other code overrides for a while and has to put back: "early_vote", "early_vote_at",
  * "early_replay", "seg_tiled", "seg_coarse"; GSX_E_INVALID for any other name */
@@ -680,6 +694,56 @@ int gsx_region_growing(gsx_ctx* ctx, int64_t n, const float* points, int64_t k_n
                        int32_t* n_regions_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * IoU evaluation of 2-D segmentations: Image_Segmentation/evaluation.py ("ev.py").  Everything is counted in
+ * integers on the GPU and divided once on the host, so the results equal the reference's exactly.  Inputs are never written
+ * (the reference's IoU overwrites the set pixels of both arguments with 1, ev.py:29-30; the Python front-end restates that).
+ * Errors: GSX_E_INVALID (before anything is read) for a NULL pointer, h, w or a count <= 0, an unknown dtype, a device pointer
+ * not aligned to its element; GSX_E_UNSUPPORTED for h * w >= 2^31, more than 65535 masks / ground truths / pairs, more than
+ * 1 GiB of bit planes or tables.
+ * ------------------------------------------------------------------------------------------- */
+/* IoU (ev.py:24-35) of every mask with every ground truth - the body of the double loop of get_ious_from_masks (ev.py:46-50).
+ * masks[n_masks], gts[n_gt]: HOST pointers to row-major h x w arrays of gsx_mask_dtype mask_dtype / gt_dtype.
+ *   inter_out      int64 [n_masks][n_gt]   |mask & gt|                       np.sum(intersection), ev.py:32,35
+ *   area_masks_out int64 [n_masks], area_gt_out int64 [n_gt]                 set pixels
+ *   iou_out        double [n_masks][n_gt]  inter / (area_m + area_g - inter)  ev.py:35; NaN where the union is empty
+ * Any output may be NULL.  The masks are copied up one at a time through a pinned staging pair and packed into bit planes
+ * (one bit per pixel); only the planes and two raw masks are resident. */
+int gsx_iou_masks(gsx_ctx* ctx, int32_t n_masks, const void* const* masks, int32_t mask_dtype, int32_t n_gt, const void* const* gts,
+                  int32_t gt_dtype, int32_t h, int32_t w, int64_t* inter_out, int64_t* area_masks_out, int64_t* area_gt_out,
+                  double* iou_out);
+/* same, the arrays hold DEVICE pointers (instance masks of a model on this GPU); a pointer needs the alignment of its element
+ * only (a view into a larger tensor).  Runs on the ctx stream, which the caller orders behind the producers of the masks; the
+ * call returns after the counts have arrived on the host. */
+int gsx_iou_masks_device(gsx_ctx* ctx, int32_t n_masks, const void* const* masks_dev, int32_t mask_dtype, int32_t n_gt,
+                         const void* const* gts_dev, int32_t gt_dtype, int32_t h, int32_t w, int64_t* inter_out,
+                         int64_t* area_masks_out, int64_t* area_gt_out, double* iou_out);
+/* contingency tables of n_pairs pairs of label maps (gsx_seg_dtype, labels -1 .. n-1 as in gsx_vote_view; both class counts in
+ * 1 .. 255): table_out int64 [n_pairs][n_pred_classes + 1][n_gt_classes + 1], entry [a][b] = pixels whose pred bin is a and
+ * whose gt bin is b, bin = label + 1.  IoU(pred == a - 1, gt == b - 1) (ev.py:24-35) is n_ab / (row_a + col_b - n_ab).
+ * A label out of range fails the call with GSX_E_RANGE; the text names the pair and the lowest flat pixel index at fault. */
+int gsx_iou_label_maps(gsx_ctx* ctx, int32_t n_pairs, const void* const* pred, int32_t pred_dtype, int32_t n_pred_classes,
+                       const void* const* gt, int32_t gt_dtype, int32_t n_gt_classes, int32_t h, int32_t w, int64_t* table_out);
+int gsx_iou_label_maps_device(gsx_ctx* ctx, int32_t n_pairs, const void* const* pred_dev, int32_t pred_dtype, int32_t n_pred_classes,
+                              const void* const* gt_dev, int32_t gt_dtype, int32_t n_gt_classes, int32_t h, int32_t w,
+                              int64_t* table_out);
+/* generate_segmentation_map (ev.py:59-69) without the colours: index_out int32 [h][w] = the highest list index whose mask is set
+ * at the pixel (the last mask drawn owns it, ev.py:65-67), or -1.  Host pointers. */
+int gsx_masks_top_index(gsx_ctx* ctx, int32_t n_masks, const void* const* masks, int32_t mask_dtype, int32_t h, int32_t w,
+                        int32_t* index_out);
+/* host only (no ctx, no GPU; errors: gsx_last_error(NULL)): iou_out[i] = (double)inter[i] / (double)(area_a[i] + area_b[i] -
+ * inter[i]), ev.py:35 - one IEEE division, NaN for 0 / 0 */
+int gsx_iou_from_counts(int64_t n, const int64_t* inter, const int64_t* area_a, const int64_t* area_b, double* iou_out);
+/* host only: the best match of get_ious_from_masks (ev.py:44-54) over iou [n_masks][n_gt]: per mask start from (0, gt 0) and
+ * move to gt i only if iou > best - the first of equal maxima wins, NaN never wins, no positive IoU reports (0, 0).
+ * best_iou_out double [n_masks], best_gt_out int32 [n_masks]. */
+int gsx_iou_best(int32_t n_masks, int32_t n_gt, const double* iou, double* best_iou_out, int32_t* best_gt_out);
+/* test hook, host only: the units the IoU kernels are built on, out[8] = bytes of a lane's load in the pack kernel, pixels per
+ * plane word, per wave and per workgroup of the pack kernel, the pair kernel's tile edge and the words per chunk of a slice
+ * (small problems get slices of exactly one chunk), the table entries up to which the LDS path runs, the pixels a lane of the
+ * table kernel run-length-merges */
+int gsx_debug_iou_constants(int32_t* out);
+
+/* ---------------------------------------------------------------------------------------------
  * profiling hooks (HIP events on the ctx stream around each kernel launch)
  * ------------------------------------------------------------------------------------------- */
 int gsx_profile_enable(gsx_ctx* ctx, int on);
@@ -690,7 +754,7 @@ const char* gsx_profile_name(gsx_ctx* ctx, int32_t index);
 int gsx_host_threads(gsx_ctx* ctx);
 /* the pool size a context would choose on its own in this process right now (no context, no GPU needed) */
 int gsx_default_host_threads(void);
-/* name: "vote_fused_labels", "seg_pack", ...; returns launches and total milliseconds since reset */
+/* name: "vote_fused_labels", "seg_pack", "iou_pack", "iou_pairs", "iou_table", "iou_top_index", ...; returns launches and total milliseconds since reset */
 int gsx_profile_get(gsx_ctx* ctx, const char* name, int64_t* launches, double* total_ms);
 
 #ifdef __cplusplus
