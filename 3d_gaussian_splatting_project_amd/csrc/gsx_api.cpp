@@ -616,6 +616,10 @@ int gsx_debug_normals_moments(gsx_ctx* ctx, int64_t n, const float* points, int6
     if (!moments_out) return gsx::fail(c, GSX_E_INVALID, "debug_normals_moments: moments_out is NULL");
     return gsx::guard(c, __func__, [&] { return gsx::normals(c, n, points, k, nullptr, nullptr, moments_out); });
 }
+int gsx_debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, double origin_out[3], double* h_out, int32_t dims_out[3],
+                      uint32_t* cell_start_out, int32_t* order_out) {
+    return gsx::guard(nullptr, __func__, [&] { return gsx::debug_nn_grid(n, points, k, brute, origin_out, h_out, dims_out, cell_start_out, order_out); });
+}
 int gsx_knn(gsx_ctx* ctx, int64_t n, const float* points, int32_t k, int32_t* index_out) {
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::knn(c, n, points, k, index_out); });

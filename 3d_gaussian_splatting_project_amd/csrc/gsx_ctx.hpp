@@ -393,6 +393,8 @@ void debug_cull_planes(const gsx_camera* cam, double* out);
 int normals(Ctx* c, int64_t n, const float* points, int64_t k, double* normals_out, double* residuals_out, double* moments_out = nullptr,
             bool checked = false);
 int knn(Ctx* c, int64_t n, const float* points, int k, int32_t* index_out, bool checked = false);
+int debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, double* origin_out, double* h_out, int32_t* dims_out,
+                  uint32_t* cell_start_out, int32_t* order_out);  // test hook: the grid and the counting sort, host only
 int region_growing(Ctx* c, int64_t n, const float* points, int64_t k_normals, int k, double residual_threshold, double angle_threshold,
                    int32_t* labels_out, double* normals_out, double* residuals_out, int32_t* n_regions_out);
 // render.hip

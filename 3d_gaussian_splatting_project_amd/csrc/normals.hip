@@ -386,28 +386,11 @@ struct NnScene {
     NnGrid G;
 };
 
-// the buffers live in the context (nn_*), as every other path's do: nothing is allocated once they have grown.
-// checked: the caller has already had these points through the finite check (the second search of gsx_region_growing)
-static int nn_prepare(Ctx* c, const char* who, int64_t n, const float* points, int64_t k, NnScene& S, bool checked = false) {
-    GSX_HIP(c, hipSetDevice(c->device));
-    // non-finite coordinates are found on the device, before anything is derived from them
-    if (!checked) {
-        DevBuf& raw = c->nn_out;  // the output buffer is free until the search has run
-        DevBuf& flag = c->nn_flag;
-        GSX_HIP(c, raw.ensure(sizeof(float) * 3 * (size_t)n));
-        GSX_HIP(c, flag.ensure(sizeof(int)));
-        GSX_HIP(c, hipMemcpyAsync(raw.p, points, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        GSX_HIP(c, hipMemsetAsync(flag.p, 0, sizeof(int), c->stream));
-        const long long n3 = 3 * (long long)n;
-        hipLaunchKernelGGL(nn_finite_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, c->stream, raw.as<float>(), n3, flag.as<int>());
-        GSX_HIP(c, hipGetLastError());
-        int bad = 0;
-        GSX_HIP(c, hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        GSX_HIP(c, hipStreamSynchronize(c->stream));
-        if (bad) return fail(c, GSX_E_INVALID, "%s: a coordinate is not finite", who);
-    }
+// grid sizing and counting sort: host arithmetic only, no context and no HIP call (gsx_debug_nn_grid shows it to the tests).
+// start: cells + 1 offsets into sorted, cells in x-fastest order; sorted: (x, y, z, bits of the original index)
+static void nn_grid_sort(int64_t n, const float* points, int64_t k, bool brute, NnGrid& G, std::vector<uint32_t>& start,
+                         std::vector<float4>& sorted) {
     // robust bounding box
-    NnGrid& G = S.G;
     double ext[3];
     for (int a = 0; a < 3; ++a) {
         double lo, hi;
@@ -439,7 +422,7 @@ static int nn_prepare(Ctx* c, const char* who, int64_t n, const float* points, i
         }
     G.g[0] = G.g[1] = G.g[2] = 1;
     G.h = 1.0;
-    if (dims > 0 && !c->opt_nn_brute) {
+    if (dims > 0 && !brute) {
         // about 3 cells of ring radius for k neighbours: k = (4 pi / 3) 27 occupancy
         const double occupancy = std::max(2.0, (double)k / 113.0);
         const double cells = std::max(1.0, (double)n / occupancy);
@@ -461,7 +444,8 @@ static int nn_prepare(Ctx* c, const char* who, int64_t n, const float* points, i
     G.inv_h = 1.0 / G.h;
     const size_t ncells = (size_t)G.g[0] * G.g[1] * G.g[2];
     // counting sort by cell, x fastest; stable, so a cell's points stay in index order
-    std::vector<uint32_t> cell((size_t)n), start(ncells + 1, 0);
+    std::vector<uint32_t> cell((size_t)n);
+    start.assign(ncells + 1, 0);
     for (int64_t i = 0; i < n; ++i) {
         size_t id = 0;
         for (int a = 2; a >= 0; --a) {
@@ -473,7 +457,7 @@ static int nn_prepare(Ctx* c, const char* who, int64_t n, const float* points, i
         ++start[id + 1];
     }
     for (size_t j = 0; j < ncells; ++j) start[j + 1] += start[j];
-    std::vector<float4> sorted((size_t)n);
+    sorted.resize((size_t)n);
     {
         std::vector<uint32_t> at(start.begin(), start.end() - 1);
         for (int64_t i = 0; i < n; ++i) {
@@ -486,6 +470,32 @@ static int nn_prepare(Ctx* c, const char* who, int64_t n, const float* points, i
             sorted[at[cell[(size_t)i]]++] = v;
         }
     }
+}
+
+// the buffers live in the context (nn_*), as every other path's do: nothing is allocated once they have grown.
+// checked: the caller has already had these points through the finite check (the second search of gsx_region_growing)
+static int nn_prepare(Ctx* c, const char* who, int64_t n, const float* points, int64_t k, NnScene& S, bool checked = false) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    // non-finite coordinates are found on the device, before anything is derived from them
+    if (!checked) {
+        DevBuf& raw = c->nn_out;  // the output buffer is free until the search has run
+        DevBuf& flag = c->nn_flag;
+        GSX_HIP(c, raw.ensure(sizeof(float) * 3 * (size_t)n));
+        GSX_HIP(c, flag.ensure(sizeof(int)));
+        GSX_HIP(c, hipMemcpyAsync(raw.p, points, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        GSX_HIP(c, hipMemsetAsync(flag.p, 0, sizeof(int), c->stream));
+        const long long n3 = 3 * (long long)n;
+        hipLaunchKernelGGL(nn_finite_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, c->stream, raw.as<float>(), n3, flag.as<int>());
+        GSX_HIP(c, hipGetLastError());
+        int bad = 0;
+        GSX_HIP(c, hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(c, hipStreamSynchronize(c->stream));
+        if (bad) return fail(c, GSX_E_INVALID, "%s: a coordinate is not finite", who);
+    }
+    std::vector<uint32_t> start;
+    std::vector<float4> sorted;
+    nn_grid_sort(n, points, k, c->opt_nn_brute != 0, S.G, start, sorted);
+    const size_t ncells = start.size() - 1;
     GSX_HIP(c, c->nn_pts.ensure(sizeof(float4) * (size_t)n));
     GSX_HIP(c, c->nn_cs.ensure(sizeof(uint32_t) * (ncells + 1)));
     GSX_HIP(c, hipMemcpyAsync(c->nn_pts.p, sorted.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, c->stream));
@@ -563,6 +573,32 @@ int region_growing(Ctx* c, int64_t n, const float* points, int64_t k_normals, in
     if (rc) return rc;
     rc = gsx_region_grow(n, normals_out, residuals_out, nb.data(), k, residual_threshold, angle_threshold, labels_out, n_regions_out);
     if (rc) return fail(c, rc, "region_growing: %s", gsx_last_error(nullptr));
+    return GSX_OK;
+}
+
+int debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, double* origin_out, double* h_out, int32_t* dims_out,
+                  uint32_t* cell_start_out, int32_t* order_out) {
+    if (!points || n < 1 || k < 1) return fail(nullptr, GSX_E_INVALID, "debug_nn_grid: points is NULL, n < 1 or k < 1");
+    if (n > ((int64_t)1 << 31) - 1) return fail(nullptr, GSX_E_UNSUPPORTED, "debug_nn_grid: n > 2^31-1");
+    if (!origin_out || !h_out || !dims_out) return fail(nullptr, GSX_E_INVALID, "debug_nn_grid: origin_out, h_out or dims_out is NULL");
+    for (int64_t i = 0; i < 3 * n; ++i)  // the product finds these on the device (nn_finite_kernel)
+        if (!std::isfinite(points[i])) return fail(nullptr, GSX_E_INVALID, "debug_nn_grid: a coordinate is not finite");
+    NnGrid G;
+    std::vector<uint32_t> start;
+    std::vector<float4> sorted;
+    nn_grid_sort(n, points, k, brute != 0, G, start, sorted);
+    for (int a = 0; a < 3; ++a) {
+        origin_out[a] = G.o[a];
+        dims_out[a] = G.g[a];
+    }
+    *h_out = G.h;
+    if (cell_start_out) std::memcpy(cell_start_out, start.data(), sizeof(uint32_t) * start.size());
+    if (order_out)
+        for (int64_t j = 0; j < n; ++j) {
+            uint32_t u;
+            std::memcpy(&u, &sorted[(size_t)j].w, 4);
+            order_out[j] = (int32_t)u;
+        }
     return GSX_OK;
 }
 

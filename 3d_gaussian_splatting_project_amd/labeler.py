@@ -793,6 +793,21 @@ def region_grow(normals, residuals, knn, residual_threshold=0.1, angle_threshold
     return labels, int(nreg.value)
 
 
+def debug_nn_grid(points, k, brute=False):
+    """Test hook, no context and no GPU: the search grid gsx_normals / gsx_knn build for these points and this k.
+    Returns (origin float64 (3,), cell edge h, dims int32 (3,), cell_start uint32 (cells + 1,), order int32 (n,): the
+    original index at each position of the cell-sorted points; cells are numbered x fastest)."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    origin, h, dims = np.empty(3, np.float64), C.c_double(), np.empty(3, np.int32)
+    L = _lib.lib()
+    check(L.gsx_debug_nn_grid(len(pts), pts.ctypes.data, int(k), int(bool(brute)), origin.ctypes.data, C.byref(h), dims.ctypes.data, None, None))
+    start = np.empty(int(np.prod(dims.astype(np.int64))) + 1, np.uint32)
+    order = np.empty(len(pts), np.int32)
+    check(L.gsx_debug_nn_grid(len(pts), pts.ctypes.data, int(k), int(bool(brute)), origin.ctypes.data, C.byref(h), dims.ctypes.data,
+                              start.ctypes.data, order.ctypes.data))
+    return origin, float(h.value), dims, start, order
+
+
 # -- IoU evaluation: input normalisation and the host-only helpers --------------------------------------------------------------------
 _MASK_NP = {"u1": _lib.GSX_MASK_U8, "i4": _lib.GSX_MASK_I32, "i8": _lib.GSX_MASK_I64, "f4": _lib.GSX_MASK_F32, "f8": _lib.GSX_MASK_F64}
 _MASK_NP_AS = {"b1": ("view", np.uint8), "i1": ("view", np.uint8), "i2": ("to", np.int32), "u2": ("to", np.int32), "u4": ("view", np.int32),

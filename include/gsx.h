@@ -668,6 +668,15 @@ int gsx_normals(gsx_ctx* ctx, int64_t n, const float* points, int64_t k, double*
 /* test hook: the moments gsx_normals takes its normal from - moments_out double[n][9] = centroid x y z (the mean of the
  * k nearest points, rg.py:103), then the upper triangle xx xy xz yy yz zz of centered^T centered (rg.py:109) */
 int gsx_debug_normals_moments(gsx_ctx* ctx, int64_t n, const float* points, int64_t k, double* moments_out);
+/* test hook, needs no ctx and no GPU (errors: gsx_last_error(NULL)): the search grid gsx_normals / gsx_knn build for these
+ * points and this k - the very host code they run (brute != 0: as under option "nn_brute").  origin_out[3], *h_out,
+ * dims_out[3]: corner, cell edge and cells per axis; cell c = floor((double(p) - origin) * (1 / h)) clamped to [0, dims - 1]
+ * per axis, cells numbered x fastest.  cell_start_out uint32[cells + 1]: the sorted positions [start[j], start[j + 1]) hold
+ * cell j; order_out int32[n]: the original index at each sorted position.  Either may be NULL: ask for dims_out first.
+ * GSX_E_INVALID: NULL points or a NULL origin_out / h_out / dims_out, n < 1, k < 1, a non-finite coordinate (found on the
+ * host here); GSX_E_UNSUPPORTED: n > 2^31-1, as gsx_normals and gsx_knn. */
+int gsx_debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, double origin_out[3], double* h_out, int32_t dims_out[3],
+                      uint32_t* cell_start_out, int32_t* order_out);
 /* kd_tree.query(points[i], k)[1] for every i (rg.py:205): index_out int32[n][k], ascending distance (the point itself
  * first unless a duplicate with a lower index precedes it).  2 <= k <= min(64, n).  index_out may be NULL: the lists
  * stay on the device. */

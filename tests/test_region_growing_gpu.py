@@ -21,6 +21,7 @@ import pytest
 
 import region_growing_model as model
 from conftest import GOLDEN, ROOT
+from region_growing_checks import angles, check_against_model, check_lists, check_moments
 
 pytestmark = pytest.mark.gpu
 
@@ -30,54 +31,6 @@ CASES = [str(c) for c in Z["cases"]]
 
 def case(name):
     return {k.split("/", 1)[1]: Z[k] for k in Z.files if k.startswith(name + "/")}
-
-
-def angles(a, b, sign_free=None):
-    cosang = np.einsum("ij,ij->i", a, b)
-    if sign_free is not None:
-        cosang = np.where(sign_free, np.abs(cosang), cosang)
-    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=1), cosang)
-
-
-def check_against_model(pts, k, nrm, res, queries=None, what=""):
-    """normals / residuals of the GPU against the model on `queries` (default: all)"""
-    q = np.arange(len(pts)) if queries is None else queries
-    nbr, _ = model.knn(pts, k, q)
-    m_nrm, m_res, m_dot, gap = model.normals_from_neighbours(pts, nbr, q)
-    ok = gap > 1e-3
-    assert (~ok).mean() < 0.01, f"{what}: {(~ok).mean():.2%} of the points have a degenerate eigen-gap: not a scene for this test"
-    P = pts.astype(np.float64)
-    vnorm = np.linalg.norm(P[q] - P[nbr].mean(axis=1), axis=1)
-    ang = angles(nrm[q], m_nrm, sign_free=np.abs(m_dot) < 1e-12 * vnorm)
-    rel = np.abs(res[q] - m_res) / np.maximum(m_res, 1e-300)
-    print(f"{what}: GPU vs model over {ok.sum()} points: max angle {ang[ok].max():.3e} rad, max relative residual error {rel[ok].max():.3e}")
-    assert np.isfinite(nrm).all() and np.allclose(np.linalg.norm(nrm, axis=1), 1.0, atol=1e-12)
-    assert ang[ok].max() <= 1e-9 and rel[ok].max() <= 1e-9, what
-    return nbr
-
-
-def check_moments(ctx, pts, k, nbr, queries=None, what=""):
-    """the neighbour SET of a large k, through the centroid and the covariance gsx_normals forms (bounds: module docstring)"""
-    q = np.arange(len(pts)) if queries is None else queries
-    cen, cov = ctx.debug_normals_moments(pts, k)
-    m_cen, m_cov, r2 = model.moments(pts, nbr, q)
-    u, S = 2.0 ** -53, float(np.abs(pts).max())
-    dc = np.abs(cen[q] - m_cen).max(axis=1)
-    dv = np.abs(cov[q] - m_cov).max(axis=(1, 2))
-    print(f"{what}: moments: centroid off by {dc.max():.3e} (bound {4 * k * u * S:.3e}), covariance by {(dv / (k * r2)).max():.3e} of k R2 "
-          f"(bound {8 * k * u:.3e})")
-    assert dc.max() <= 4 * k * u * S and (dv <= 8 * k * u * k * r2).all(), what
-
-
-def check_lists(pts, nbr):
-    """every row of a k-NN result on its own: the point itself is there, (d2, index) ascends strictly"""
-    P = pts.astype(np.float64)
-    d = P[nbr] - P[:, None, :]
-    d2 = (d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2]
-    assert (nbr == np.arange(len(pts))[:, None]).any(axis=1).all()
-    step = np.diff(d2, axis=1)
-    assert ((step > 0) | ((step == 0) & (np.diff(nbr, axis=1) > 0))).all()
-    return d2
 
 
 def planes_and_blob(rng, n):
