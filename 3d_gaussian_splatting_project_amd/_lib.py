@@ -202,7 +202,7 @@ def lib():
     """Load libgsx.so.  Raises if it has not been built: the HIP library IS the product."""
     global _lib
     if _lib is None:
-        path = os.environ.get("GSX_LIBRARY") or SO_PATH   # GSX_LIBRARY: another build of the same C ABI (tools/ablate.sh)
+        path = os.environ.get("GSX_LIBRARY") or SO_PATH   # GSX_LIBRARY: another build of the same C ABI (tools/ab.sh, the experiments library)
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `make -C {CSRC}` "
                               "(or __graft_entry__.build()); there is no CPU fallback")

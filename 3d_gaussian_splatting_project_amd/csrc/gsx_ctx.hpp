@@ -91,13 +91,12 @@ struct alignas(64) ViewDesc {
     double half_w, half_h;  // width/2, height/2                                    (dls.py:76-77)
     double width, height;   // bounds of the visibility test                        (dls.py:80)
     int seg_w, seg_h;
-    int cam_w, cam_h;   // camera width / height as integers (visibility test of the certified path)
+    int cam_w, cam_h;   // camera width / height as integers (visibility test of the filtered projection)
     int coarse_row_bytes;   // bytes per strip of 16 coarse cells (0: this view has no coarse level)
     unsigned coarse_delta;  // byte offset of the coarse level from the map's own start
     float hw32, hh32;       // half_w, half_h as floats (exact: the frame is <= 65535 pixels a side): the fp32 filter of the projection
     // ---- cold part: only read on the scale + clamp path (dls.py:270-286) ----
     double wscale, hscale;  // seg_w/img_w, seg_h/img_h                             (dls.py:270-271)
-    float xf[12];           // experiments (GSX_ABLATE & 64, timing only): fx R0, fy R1, R2 rows and fx t0, fy t1, t2 as floats
 };
 static_assert(sizeof(ViewDesc) == 256 && offsetof(ViewDesc, wscale) == 192, "ViewDesc layout");
 
@@ -140,12 +139,10 @@ struct Ctx {
     int opt_vote_unroll = 8;   // views whose seg gathers are in flight together: 1, 2, 4 or 8
     int opt_slabs = 1;         // see Ctx::slabs (takes effect at the next vote_begin)
     int opt_local_codes = 0;   // see Ctx::local_codes
-    int opt_lds_batch = 0;     // read a chunk's LDS counters in one round trip (repeats resolved in registers)
     int opt_blend_pk2 = 2;     // rasterizer: 0 = one pixel per thread, 1 = two (packed fp32), 2 = four, one wave per tile (default since round 3)
     int opt_exact_cull = 0;    // rasterizer: keep only the tiles the splat's ellipse really reaches (pairs -23 %; the test costs more than the sort saves)
     int opt_tile_lpt = 0;      // rasterizer: launch the tiles with the longest lists first (blend -3 %, but net 0)
     int opt_seg_tiled = 1;     // store seg maps as 16x8-pixel tiles of 128 B
-    int opt_fast_div = 0;      // certified single-reciprocal projection with exact fallback (bit-identical, not faster)
     int opt_batched_counts = 1; // > 255 views on one GPU: per-batch count planes + sparse tie pass instead of 16-bit planes
     int opt_seg_coarse = 1;    // keep a 4x4-coarsened level of every tiled map (views staged after the call)
     int opt_flat_project = 1;  // branchless projection block (exact divisions, one predicate at the end)

@@ -42,13 +42,6 @@
 
 #include <type_traits>
 
-#ifndef GSX_ABLATE
-#define GSX_ABLATE 0  // product build; tools/ablate.sh builds timing-only variants (results invalid)
-#endif
-#if GSX_ABLATE && !defined(GSX_EXPERIMENTS)
-#error "GSX_ABLATE variants are experiments: build them with -DGSX_EXPERIMENTS (make experiments), never into libgsx.so"
-#endif
-
 #include "gsx_ctx.hpp"
 
 namespace gsx {
@@ -145,13 +138,7 @@ __device__ __forceinline__ double row_dot(const double* Rr, double v0, double v1
 // project_gaussian (dls.py:43-82).  Returns false where the reference returns None (:72-73, :80-82).
 //
 // DIV == kDivExact: the two IEEE-754 divisions of dls.py:76-77, operation for operation.
-// DIV == kDivCertified: the same results from ONE reciprocal.  r ~ 1/pc2 (v_rcp_f64 + two Newton steps,
-//   relative error <= 2^-48), s^ = (f*pc)*r + half is within 2^-30 of the reference's px = fl(fl(f*pc/pc2) + half)
-//   whenever |px| <= 2^18, and far outside the frame (<= 2^16 pixels) otherwise.  If s^ is at least 2^-20 away
-//   from every integer, floor(px) == floor(s^) is CERTAIN, and so are `0 <= px < width` (integer width) and the
-//   truncation int(px).  A lane that is closer than that to an integer (~4e-6 of them), or whose arithmetic left
-//   the finite range, or whose depth lies outside [2^-200, 2^200] (reciprocal not safely normal), falls through to
-//   the exact divisions.  11 fewer fp64 instructions per visible pair.
+// (A certified form, the same results from ONE reciprocal, option "fast_div", was measured and removed: DESIGN.md.)
 // DIV == kDivFlat: the exact divisions again, but as ONE straight-line block: all three rows and both quotients are
 //   evaluated unconditionally and the reference's tests (:72, :80) become a single predicate at the end.  The
 //   branchy form serialises ~45 dependent fp64 instructions behind three divergent branches; here the three rows
@@ -161,8 +148,7 @@ __device__ __forceinline__ double row_dot(const double* Rr, double v0, double v1
 //   two wave-uniform tests per view disappear from the instruction stream.
 // DIV == kDivFlatCoarse: kDivFlatSimple for a batch whose maps all carry a coarse level (see gather_chunk).
 // DIV == kDivFiltCoarse: kDivFlatCoarse with the fp32 filter of project_filtered() in front of the two divisions.
-enum { kDivExact = 0, kDivCertified = 1, kDivFlat = 2, kDivFlatSimple = 3, kDivFlatCoarse = 4, kDivFiltCoarse = 5 };
-static constexpr int kDivModes = 6;
+enum { kDivExact = 0, kDivFlat = 1, kDivFlatSimple = 2, kDivFlatCoarse = 3, kDivFiltCoarse = 4 };
 
 // Two IEEE-754 divisions by the same denominator, bit-identical to `ax / b` and `ay / b`.
 // hipcc expands an fp64 division into div_scale(den), rcp, two Newton steps, div_scale(num), mul, fma, div_fmas,
@@ -216,23 +202,6 @@ __device__ __forceinline__ bool project(const ViewRegs& vd, double X, double Y, 
     const double pc0 = row_dot(vd.R + 0, X, Y, Z) + vd.t[0];
     const double pc1 = row_dot(vd.R + 3, X, Y, Z) + vd.t[1];
     const double ax = vd.fx * pc0, ay = vd.fy * pc1;
-    // the certificate below assumes a normal reciprocal: 2^-200 <= pc2 <= 2^200 (exponent field 823..1223)
-    if (DIV == kDivCertified && (unsigned)(((__double2hiint(pc2) >> 20) & 0x7ff) - 823) <= 400u) {
-        double r = __builtin_amdgcn_rcp(pc2);
-        r = __builtin_fma(__builtin_fma(-pc2, r, 1.0), r, r);
-        r = __builtin_fma(__builtin_fma(-pc2, r, 1.0), r, r);
-        const double sx = ax * r + vd.half_w, sy = ay * r + vd.half_h;
-        const double flx = floor(sx), fly = floor(sy);
-        const double frx = sx - flx, fry = sy - fly;
-        const double lo = 9.5367431640625e-07, hi = 1.0 - 9.5367431640625e-07;  // 2^-20
-        if ((frx >= lo) & (frx <= hi) & (fry >= lo) & (fry <= hi)) {  // false for NaN / infinity
-            const int kx = (int)flx, ky = (int)fly;                    // saturating conversions
-            if (((unsigned)kx >= (unsigned)vd.cam_w) | ((unsigned)ky >= (unsigned)vd.cam_h)) return false;
-            xi = kx;
-            yi = ky;
-            return true;
-        }
-    }
     const double px = ax / pc2 + vd.half_w;  // dls.py:76
     const double py = ay / pc2 + vd.half_h;  // dls.py:77
     if (!((0.0 <= px) && (px < vd.width) && (0.0 <= py) && (py < vd.height))) return false;  // :80
@@ -324,10 +293,6 @@ __device__ __forceinline__ int seg_bin_regs(const ViewRegs& vd, const ViewDesc* 
             xi = xs > (double)(vd.seg_w - 1) ? vd.seg_w - 1 : (int)xs;  // :285 (xs >= 0 always)
             yi = ys > (double)(seg_h - 1) ? seg_h - 1 : (int)ys;        // :286
         }
-#if GSX_ABLATE & 32  // timing experiment only: the footprint of a 4x4-coarsened map (upper bound for a coarse level)
-        xi >>= 2;
-        yi >>= 2;
-#endif
         unsigned off;
         if (kSimple || vd.seg_row_bytes) {
             // strips of 16 pixel columns, rows of a strip back to back (16 B each): any 8 consecutive rows of a strip
@@ -340,15 +305,7 @@ __device__ __forceinline__ int seg_bin_regs(const ViewRegs& vd, const ViewDesc* 
         // the device copy of the descriptor holds the map's absolute address; say "global" explicitly, a pointer made
         // from an integer would otherwise be a FLAT one (flat loads also count in lgkmcnt and stall the scalar waits)
         typedef const __attribute__((address_space(1))) uint8_t* global_u8;
-#if GSX_ABLATE & 2  // timing experiment only (tools/ablate.sh): no gather, a bin made from the offset
-        bin = (int)(off & 127u);
-#elif GSX_ABLATE & 8  // timing experiment only: every gather falls into the first KiB of the map (always cached)
-        bin = ((global_u8)(unsigned long long)vd.seg_off)[off & 1023u];
-#elif GSX_ABLATE & 16  // timing experiment only: the first 64 KiB of the map (L2-resident, rarely in L1)
-        bin = ((global_u8)(unsigned long long)vd.seg_off)[off & 65535u];
-#else
         bin = ((global_u8)(unsigned long long)vd.seg_off)[off];
-#endif
     }
     return bin;
 }
@@ -642,44 +599,6 @@ __device__ __forceinline__ unsigned cull_bits(const CullMasks& k, int done) {
     return (unsigned)(word >> (done & 63)) & ((1u << U) - 1u);
 }
 
-#if GSX_ABLATE & 64
-// TIMING EXPERIMENT ONLY (results invalid): what an all-fp32 filter would cost - the camera-space point from twelve floats
-// (one s_load_dwordx16 instead of 176 bytes of fp64 descriptor), the exact path (full descriptor, fp64) only for the waves
-// with a lane near a pixel boundary.  Without the per-wave base point such a filter would need, its error bound is missing.
-struct ViewF32 {
-    float r0[3], r1[3], r2[3], t0, t1, t2, hw, hh;
-    int cam_w, cam_h, coarse_row_bytes;
-    unsigned coarse_delta;
-    long long seg_off;
-};
-__device__ __forceinline__ ViewF32 load_view_f32(const ViewDesc* __restrict__ vp) {
-    const char* q = reinterpret_cast<const char*>(vp);
-    v16i a = *reinterpret_cast<const v16i*>(q + 192);
-    v8i d = *reinterpret_cast<const v8i*>(q + 160);
-    v2i so = *reinterpret_cast<const v2i*>(q + 112);
-    asm volatile("" : "+s"(a), "+s"(d), "+s"(so));
-    ViewF32 r;
-    int w[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k] = a[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        r.r0[k] = __builtin_bit_cast(float, w[4 + k]);
-        r.r1[k] = __builtin_bit_cast(float, w[7 + k]);
-        r.r2[k] = __builtin_bit_cast(float, w[10 + k]);
-    }
-    r.t0 = __builtin_bit_cast(float, w[13]);
-    r.t1 = __builtin_bit_cast(float, w[14]);
-    r.t2 = __builtin_bit_cast(float, w[15]);
-    const int d2 = d[2], d3 = d[3], d4 = d[4], d5 = d[5], d6 = d[6], d7 = d[7];
-    r.cam_w = d2, r.cam_h = d3, r.coarse_row_bytes = d4, r.coarse_delta = (unsigned)d5;
-    r.hw = __builtin_bit_cast(float, d6);
-    r.hh = __builtin_bit_cast(float, d7);
-    r.seg_off = __builtin_bit_cast(long long, so);
-    return r;
-}
-#endif
-
 // One chunk of U views (vb-1, vb-2, ..): bin[u] = the vote of this lane's Gaussian in view vb-1-u, or -1.
 // FULL: all U views exist (no index test).  culled: bit u set = the whole wave provably misses view vb-1-u.
 typedef const __attribute__((address_space(1))) uint8_t* global_u8_ptr;
@@ -700,37 +619,6 @@ __device__ __forceinline__ void gather_chunk(const ViewDesc* __restrict__ views,
             const int v = vb - 1 - u;
             bin[u] = -1;  // (pixel[u] is only read where bin[u] == 255, i.e. where it was set below)
             if (((culled >> u) & 1u) || !(FULL || v >= 0)) continue;  // wave-uniform
-#if GSX_ABLATE & 64  // timing experiment only, see load_view_f32
-            if (DIV == kDivFiltCoarse) {
-                const ViewF32 f = load_view_f32(views + v);
-                const float Xf = (float)X, Yf = (float)Y, Zf = (float)Z;
-                const float zf = __builtin_fmaf(Xf, f.r2[0], __builtin_fmaf(Yf, f.r2[1], __builtin_fmaf(Zf, f.r2[2], f.t2)));
-                const bool pos = zf > 0.f;
-                if (__builtin_amdgcn_ballot_w64(pos) == 0) continue;
-                const float a0 = __builtin_fmaf(Xf, f.r0[0], __builtin_fmaf(Yf, f.r0[1], __builtin_fmaf(Zf, f.r0[2], f.t0)));
-                const float a1 = __builtin_fmaf(Xf, f.r1[0], __builtin_fmaf(Yf, f.r1[1], __builtin_fmaf(Zf, f.r1[2], f.t1)));
-                const float r = __builtin_amdgcn_rcpf(zf);
-                const float pxf = __builtin_fmaf(a0, r, f.hw), pyf = __builtin_fmaf(a1, r, f.hh);
-                const float dx = __builtin_amdgcn_fractf(pxf) - 0.5f, dy = __builtin_amdgcn_fractf(pyf) - 0.5f;
-                const bool cert = (zf >= 1e-12f) & (__builtin_fabsf(dx) <= filt_h) & (__builtin_fabsf(dy) <= filt_h);
-                int xi = cvt_floor_i32(pxf), yi = cvt_floor_i32(pyf);
-                bool vis = cert & ((unsigned)xi < (unsigned)f.cam_w) & ((unsigned)yi < (unsigned)f.cam_h);
-                long long seg_off = f.seg_off;
-                unsigned cdelta = f.coarse_delta;
-                int crb = f.coarse_row_bytes;
-                if (__builtin_amdgcn_ballot_w64(pos & !cert) != 0) {  // the exact path for the whole wave, full descriptor
-                    const ViewRegs vd = load_view(views + v);
-                    vis = project<kDivFlatSimple>(vd, X, Y, Z, xi, yi);
-                }
-                if (vis) {
-                    pixel[u] = (unsigned)xi | ((unsigned)yi << 16);
-                    const unsigned cx = (unsigned)xi >> 2, cy = (unsigned)yi >> 2;
-                    const unsigned coff = __umul24(cx >> 4, (unsigned)crb) + (cx & 15u) + (cy << 4);
-                    bin[u] = ((global_u8_ptr)((unsigned long long)seg_off + cdelta))[coff];
-                }
-                continue;
-            }
-#endif
             const ViewRegs vd = load_view(views + v);
             int xi, yi;
             if (DIV == kDivFiltCoarse ? project_filtered(vd, filt_h, X, Y, Z, xi, yi) : project<kDivFlatSimple>(vd, X, Y, Z, xi, yi)) {
@@ -759,20 +647,13 @@ __device__ __forceinline__ void gather_chunk(const ViewDesc* __restrict__ views,
             bin[u] = -1;
             continue;
         }
-#if GSX_ABLATE & 4  // timing experiment only: ONE descriptor for all views (no scalar loads in the loop; NOTE: every
-                    // view then votes the same pixel, so the gathers become free as well); the view-dependent
-                    // perturbation (it rounds away) keeps the arithmetic inside the loop
-        const ViewRegs vd0 = load_view(views);
-        bin[u] = (FULL || v >= 0) ? seg_bin_regs<DIV>(vd0, views, pool, __builtin_fma((double)v, 1e-300, X), Y, Z) : -1;
-#else
         bin[u] = (FULL || v >= 0) ? seg_bin<DIV>(views + v, pool, X, Y, Z) : -1;
-#endif
     }
 }
 
 // (The last stage's LDS layout - a wave's histograms as [bin][64 lanes] bytes - was measured here too, round 3: 1.052 ms against
 // 1.036-1.043 for the row per thread, profiles/r03/lds_layout_and_replay_ab.txt; removed again.)
-template <int U, int DIV, bool LDS_BATCH>
+template <int U, int DIV>
 __global__ __launch_bounds__(kBlock) void vote_fused_labels_kernel(FusedParams p, const ViewDesc* __restrict__ views,
                                                                    int* __restrict__ labels) {
     extern __shared__ uint32_t lds[];
@@ -796,40 +677,14 @@ __global__ __launch_bounds__(kBlock) void vote_fused_labels_kernel(FusedParams p
         constexpr bool kFull = decltype(full)::value;
         int bin[U];
         gather_chunk<U, DIV, kFull>(views, pool, vb, X, Y, Z, cull_bits<U>(cmask, p.nviews - vb), bin, p.filt_h);
-#if GSX_ABLATE & 1  // timing experiment only: no LDS histogram, the bins are just consumed
 #pragma unroll
-        for (int u = 0; u < U; ++u) best += bin[u];
-        if (false)
-#endif
-        if (LDS_BATCH) {
-            // one LDS round trip for the whole chunk: read the U counters first, resolve repeats of a bin
-            // inside the chunk in registers, then apply the votes in (reverse view) order
-            int old[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) old[u] = bin[u] >= 0 ? (int)h[bin[u]] : 0;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (bin[u] >= 0) {
-                    int c = old[u] + 1;  // dls.py:295
-#pragma unroll
-                    for (int w = 0; w < u; ++w) c += (bin[w] == bin[u]) ? 1 : 0;
-                    h[bin[u]] = (uint8_t)c;  // LDS stores of one wave retire in order: the last repeat wins
-                    if (c >= bestc) {  // reverse-order tie rule == first-inserted wins (dls.py:303)
-                        bestc = c;
-                        best = bin[u];
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (bin[u] >= 0) {
-                    const int c = h[bin[u]] + 1;  // dls.py:295
-                    h[bin[u]] = (uint8_t)c;
-                    if (c >= bestc) {  // reverse-order tie rule == first-inserted wins (dls.py:303)
-                        bestc = c;
-                        best = bin[u];
-                    }
+        for (int u = 0; u < U; ++u) {
+            if (bin[u] >= 0) {
+                const int c = h[bin[u]] + 1;  // dls.py:295
+                h[bin[u]] = (uint8_t)c;
+                if (c >= bestc) {  // reverse-order tie rule == first-inserted wins (dls.py:303)
+                    bestc = c;
+                    best = bin[u];
                 }
             }
         }
@@ -1466,14 +1321,6 @@ void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, i
     vd.cam_h = cam->height;
     vd.hw32 = (float)vd.half_w;  // exact for frames up to 2^24 pixels a side
     vd.hh32 = (float)vd.half_h;
-    for (int k = 0; k < 3; ++k) {
-        vd.xf[k] = (float)(vd.fx * vd.R[k]);
-        vd.xf[3 + k] = (float)(vd.fy * vd.R[3 + k]);
-        vd.xf[6 + k] = (float)vd.R[6 + k];
-    }
-    vd.xf[9] = (float)(vd.fx * vd.t[0]);
-    vd.xf[10] = (float)(vd.fy * vd.t[1]);
-    vd.xf[11] = (float)vd.t[2];
     vd.wscale = (double)seg_w / (double)img_w;
     vd.hscale = (double)seg_h / (double)img_h;
     vd.seg_w = seg_w;
@@ -1482,11 +1329,28 @@ void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, i
     vd.unit_scale = (vd.wscale == 1.0 && vd.hscale == 1.0 && cam->width <= seg_w && cam->height <= seg_h) ? 1 : 0;
 }
 
+// The branchless projection variant a set of views allows under this context's options.  simple: every view has unit scale and
+// a tiled map; coarse: ... and a coarse level.
+static inline int flat_div_mode(const Ctx* c, bool simple, bool coarse) {
+    if (!simple) return kDivFlat;
+    return coarse && c->opt_seg_coarse ? (c->opt_filter_project ? kDivFiltCoarse : kDivFlatCoarse) : kDivFlatSimple;
+}
 // call after sync_views(): views_simple describes the staged batch
 static inline int div_mode(const Ctx* c) {
-    if (!c->opt_flat_project) return c->opt_fast_div ? kDivCertified : kDivExact;
-    if (!c->views_simple) return kDivFlat;
-    return c->views_coarse && c->opt_seg_coarse ? (c->opt_filter_project ? kDivFiltCoarse : kDivFlatCoarse) : kDivFlatSimple;
+    return c->opt_flat_project ? flat_div_mode(c, c->views_simple, c->views_coarse) : kDivExact;
+}
+// Kernel selection: calls f(std::integral_constant<int, DIV>{}) for the projection variant dm and returns what it returns
+// (the same type for every DIV: a kernel pointer).  FLAT_ONLY: f is instantiated for the four branchless variants only -
+// the early-vote kernels exist for no other, and their stages never run without "flat_project".
+template <bool FLAT_ONLY = false, class F>
+static inline auto with_div(int dm, F&& f) {
+    switch (dm) {
+        case kDivFiltCoarse: return f(std::integral_constant<int, kDivFiltCoarse>{});
+        case kDivFlatCoarse: return f(std::integral_constant<int, kDivFlatCoarse>{});
+        case kDivFlatSimple: return f(std::integral_constant<int, kDivFlatSimple>{});
+        case kDivFlat: return f(std::integral_constant<int, kDivFlat>{});
+        default: return f(std::integral_constant<int, FLAT_ONLY ? kDivFlat : kDivExact>{});
+    }
 }
 // 0.5 - E of project_filtered() for the staged views (E grows with the frame: the largest one decides)
 static float filter_half_width(const Ctx* c) {
@@ -1518,9 +1382,6 @@ int project_all(Ctx* c, const gsx_camera* cam, const float* dx, const float* dy,
                                dvd.as<ViewDesc>(), perm, ox.as<int>(), oy.as<int>(), filt_h);
         else if (c->opt_flat_project)
             hipLaunchKernelGGL(project_kernel<kDivFlat>, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n,
-                               dvd.as<ViewDesc>(), perm, ox.as<int>(), oy.as<int>(), 0.f);
-        else if (c->opt_fast_div)
-            hipLaunchKernelGGL(project_kernel<kDivCertified>, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n,
                                dvd.as<ViewDesc>(), perm, ox.as<int>(), oy.as<int>(), 0.f);
         else
             hipLaunchKernelGGL(project_kernel<kDivExact>, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n,
@@ -2342,7 +2203,7 @@ static int early_upload(Ctx* c, int lo, int hi, int block, int blocks, hipStream
         cull_planes(v, pl);
         for (int k = 0; k < kCullStride * kCullPlanes; ++k) planes[(size_t)k * kEarlyPitch + (i - lo)] = pl[k];
     }
-    *dm = !simple ? kDivFlat : (coarse && c->opt_seg_coarse ? (c->opt_filter_project ? kDivFiltCoarse : kDivFlatCoarse) : kDivFlatSimple);
+    *dm = flat_div_mode(c, simple, coarse);
     if (hi > lo) GSX_HIP(c, hipMemcpyAsync(c->e_views.as<ViewDesc>() + lo, hv, sizeof(ViewDesc) * (size_t)(hi - lo), hipMemcpyHostToDevice, st));
     GSX_HIP(c, hipMemcpyAsync(c->e_cull.as<double>() + (size_t)block * kEarlyCullDoubles, planes, cbytes, hipMemcpyHostToDevice, st));
     GSX_HIP(c, hipEventRecord(c->early_up_ev, st));
@@ -2427,10 +2288,7 @@ static int early_vote_stage(Ctx* c) {
     if ((rc = early_upload(c, 0, at, 0, 2, c->stream2, &dm))) return rc;
     if (c->opt_early_replay) {  // record only: the last stage replays it
         FusedParams p = early_params(c, 0, at, 0, 1);
-        auto kr = dm == kDivFiltCoarse ? vote_record_kernel<kUnroll, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_record_kernel<kUnroll, kDivFlatCoarse>
-                  : dm == kDivFlatSimple ? vote_record_kernel<kUnroll, kDivFlatSimple>
-                                         : vote_record_kernel<kUnroll, kDivFlat>;
+        auto kr = with_div<true>(dm, [](auto d) { return vote_record_kernel<kUnroll, decltype(d)::value>; });
         {
             ProfScope ps(c, "vote_early_record", c->stream2);
             hipLaunchKernelGGL(kr, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream2, p, p.views, c->erec.as<uint8_t>());
@@ -2446,10 +2304,7 @@ static int early_vote_stage(Ctx* c) {
     c->early_replayed = false;
     FusedParams p = early_params(c, 0, at, 0, 2);
     const size_t lds = (size_t)kBlock * p.stride_dw * 4;
-    auto k = dm == kDivFiltCoarse ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivFlatCoarse>
-             : dm == kDivFlatSimple ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivFlatSimple>
-                                    : vote_fused_planes_kernel<kUnroll, uint8_t, kDivFlat>;
+    auto k = with_div<true>(dm, [](auto d) { return vote_fused_planes_kernel<kUnroll, uint8_t, decltype(d)::value>; });
     if ((rc = set_lds(c, k, lds))) return rc;
     {
         ProfScope ps(c, "vote_early_planes", c->stream2);
@@ -2485,10 +2340,7 @@ static int early_batch_stage(Ctx* c) {
     if ((rc = early_upload(c, lo, hi, s, S, c->stream2, &dm))) return rc;
     FusedParams p = early_params(c, lo, hi, s, 1);
     const size_t lds = (size_t)kBlock * p.stride_dw * 4;
-    auto k = dm == kDivFiltCoarse ? vote_fused_counts_kernel<kUnroll, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_fused_counts_kernel<kUnroll, kDivFlatCoarse>
-             : dm == kDivFlatSimple ? vote_fused_counts_kernel<kUnroll, kDivFlatSimple>
-                                    : vote_fused_counts_kernel<kUnroll, kDivFlat>;
+    auto k = with_div<true>(dm, [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
     if ((rc = set_lds(c, k, lds))) return rc;
     {
         ProfScope ps(c, "vote_early_counts", c->stream2);
@@ -2513,10 +2365,7 @@ static int early_vote_finish(Ctx* c) {
     if (c->early_replayed) {
         FusedParams pr = early_params(c, c->early_done, nv, 1, 1);
         const size_t ldsr = (size_t)kBlock * pr.stride_dw * 4;
-        auto kr = dm == kDivFiltCoarse ? vote_fused_replay_kernel<kUnroll, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_fused_replay_kernel<kUnroll, kDivFlatCoarse>
-                  : dm == kDivFlatSimple ? vote_fused_replay_kernel<kUnroll, kDivFlatSimple>
-                                         : vote_fused_replay_kernel<kUnroll, kDivFlat>;
+        auto kr = with_div<true>(dm, [](auto d) { return vote_fused_replay_kernel<kUnroll, decltype(d)::value>; });
         if ((rc = set_lds(c, kr, ldsr))) return rc;
         if ((rc = early_join(c))) return rc;
         if ((c->opt_ablate >> 4) & 2) pr.nviews = 0;  // timing experiment (tools/early_probe.py)
@@ -2530,10 +2379,10 @@ static int early_vote_finish(Ctx* c) {
     const size_t lds = (size_t)(kBlock / 64) * ((c->bins + 3) / 4) * 256;  // per wave: [bin][64] bytes, rows padded to a multiple of four
     constexpr int kRegRows = 38;  // bins <= 152 (the 150 ADE20K classes + unlabelled): the first-view rows wait in registers
     const bool regs = c->bins <= 4 * kRegRows;
-    auto k = dm == kDivFiltCoarse ? (regs ? vote_fused_final_kernel<kUnroll, kDivFiltCoarse, kRegRows> : vote_fused_final_kernel<kUnroll, kDivFiltCoarse, 0>)
-                 : dm == kDivFlatCoarse ? (regs ? vote_fused_final_kernel<kUnroll, kDivFlatCoarse, kRegRows> : vote_fused_final_kernel<kUnroll, kDivFlatCoarse, 0>)
-             : dm == kDivFlatSimple ? (regs ? vote_fused_final_kernel<kUnroll, kDivFlatSimple, kRegRows> : vote_fused_final_kernel<kUnroll, kDivFlatSimple, 0>)
-                                    : (regs ? vote_fused_final_kernel<kUnroll, kDivFlat, kRegRows> : vote_fused_final_kernel<kUnroll, kDivFlat, 0>);
+    auto k = with_div<true>(dm, [&](auto d) {
+        constexpr int kDiv = decltype(d)::value;
+        return regs ? vote_fused_final_kernel<kUnroll, kDiv, kRegRows> : vote_fused_final_kernel<kUnroll, kDiv, 0>;
+    });
     if ((rc = set_lds(c, k, lds))) return rc;
     if ((rc = early_join(c))) return rc;
     // timing experiments (results invalid), option "ablate": 16 every wave reads the planes of wave 0; 32 no views behind the
@@ -2585,24 +2434,12 @@ int vote_flush(Ctx* c) {
         const int fresh = (c->planes_zero || c->planes_stale) ? 1 : 0;
         ProfScope ps(c, "vote_fused_planes");
         if (c->wide) {
-            const int dm = div_mode(c);
-            auto k = dm == kDivFiltCoarse ? vote_fused_planes_kernel<kUnroll, uint16_t, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_fused_planes_kernel<kUnroll, uint16_t, kDivFlatCoarse>
-                     : dm == kDivFlatSimple ? vote_fused_planes_kernel<kUnroll, uint16_t, kDivFlatSimple>
-                     : dm == kDivFlat     ? vote_fused_planes_kernel<kUnroll, uint16_t, kDivFlat>
-                     : dm == kDivCertified ? vote_fused_planes_kernel<kUnroll, uint16_t, kDivCertified>
-                                           : vote_fused_planes_kernel<kUnroll, uint16_t, kDivExact>;
+            auto k = with_div(div_mode(c), [](auto d) { return vote_fused_planes_kernel<kUnroll, uint16_t, decltype(d)::value>; });
             if ((rc = set_lds(c, k, lds))) return rc;
             hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->cnt.as<uint16_t>(),
                                c->fv.as<uint16_t>(), (long long)c->sn, view_base, fresh, 0, (uint8_t*)nullptr);
         } else {
-            const int dm = div_mode(c);
-            auto k = dm == kDivFiltCoarse ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivFlatCoarse>
-                     : dm == kDivFlatSimple ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivFlatSimple>
-                     : dm == kDivFlat     ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivFlat>
-                     : dm == kDivCertified ? vote_fused_planes_kernel<kUnroll, uint8_t, kDivCertified>
-                                           : vote_fused_planes_kernel<kUnroll, uint8_t, kDivExact>;
+            auto k = with_div(div_mode(c), [](auto d) { return vote_fused_planes_kernel<kUnroll, uint8_t, decltype(d)::value>; });
             if ((rc = set_lds(c, k, lds))) return rc;
             hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->cnt.as<uint8_t>(),
                                c->fv.as<uint8_t>(), (long long)c->sn, view_base, fresh, c->local_codes ? 1 : 0, (uint8_t*)nullptr);
@@ -2757,19 +2594,14 @@ static int labels_one_batch(Ctx* c, const VoteRange& r, const uint32_t* perm, in
     FusedParams p = range_params(c, r, 1);
     p.perm = perm ? perm + r.i0 : nullptr;
     const size_t lds = (size_t)kBlock * p.stride_dw * 4;
-    // kernel variants: unroll U in {2,4,8} x division mode x batched LDS reads
+    // kernel variants: unroll U in {2,4,8} x division mode
     using K = void (*)(FusedParams, const ViewDesc*, int*);
     const int ui = c->opt_vote_unroll == 2 ? 0 : c->opt_vote_unroll == 4 ? 1 : 2;
-#define GSX_ROW(U_) \
-    {{vote_fused_labels_kernel<U_, kDivExact, false>, vote_fused_labels_kernel<U_, kDivExact, true>},         \
-     {vote_fused_labels_kernel<U_, kDivCertified, false>, vote_fused_labels_kernel<U_, kDivCertified, true>}, \
-     {vote_fused_labels_kernel<U_, kDivFlat, false>, vote_fused_labels_kernel<U_, kDivFlat, true>},           \
-     {vote_fused_labels_kernel<U_, kDivFlatSimple, false>, vote_fused_labels_kernel<U_, kDivFlatSimple, true>}, \
-     {vote_fused_labels_kernel<U_, kDivFlatCoarse, false>, vote_fused_labels_kernel<U_, kDivFlatCoarse, true>},   \
-     {vote_fused_labels_kernel<U_, kDivFiltCoarse, false>, vote_fused_labels_kernel<U_, kDivFiltCoarse, true>}}
-    static const K table[3][kDivModes][2] = {GSX_ROW(2), GSX_ROW(4), GSX_ROW(8)};
-#undef GSX_ROW
-    K k = table[ui][div_mode(c)][c->opt_lds_batch ? 1 : 0];
+    K k = with_div(div_mode(c), [ui](auto d) {
+        constexpr int kDiv = decltype(d)::value;
+        static const K by_unroll[3] = {vote_fused_labels_kernel<2, kDiv>, vote_fused_labels_kernel<4, kDiv>, vote_fused_labels_kernel<8, kDiv>};
+        return by_unroll[ui];
+    });
     int rc = set_lds(c, k, lds);
     if (rc) return rc;
     ProfScope ps(c, "vote_fused_labels");
@@ -2799,13 +2631,7 @@ static int labels_batched(Ctx* c, const VoteRange& r) {
     GSX_HIP(c, c->cand.ensure(sizeof(uint32_t) * kCandWords * (size_t)npad));
     GSX_HIP(c, c->bcodes.ensure(sizeof(uint16_t) * (size_t)npad * S));
     if (r.n <= 0) return GSX_OK;
-    const int dm = div_mode(c);
-    auto k = dm == kDivFiltCoarse ? vote_fused_counts_kernel<kUnroll, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_fused_counts_kernel<kUnroll, kDivFlatCoarse>
-             : dm == kDivFlatSimple ? vote_fused_counts_kernel<kUnroll, kDivFlatSimple>
-             : dm == kDivFlat     ? vote_fused_counts_kernel<kUnroll, kDivFlat>
-             : dm == kDivCertified ? vote_fused_counts_kernel<kUnroll, kDivCertified>
-                                   : vote_fused_counts_kernel<kUnroll, kDivExact>;
+    auto k = with_div(div_mode(c), [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
     FusedParams base = range_params(c, r, 1);
     const size_t lds = (size_t)kBlock * base.stride_dw * 4;
     int rc = set_lds(c, k, lds);
@@ -3124,13 +2950,7 @@ int vote_flush_counts(Ctx* c) {
     if (c->n > 0) {
         FusedParams p = fused_params(c, 1);
         const size_t lds = (size_t)kBlock * p.stride_dw * 4;
-        const int dm = div_mode(c);
-        auto k = dm == kDivFiltCoarse ? vote_fused_counts_kernel<kUnroll, kDivFiltCoarse>
-                 : dm == kDivFlatCoarse ? vote_fused_counts_kernel<kUnroll, kDivFlatCoarse>
-                 : dm == kDivFlatSimple ? vote_fused_counts_kernel<kUnroll, kDivFlatSimple>
-                 : dm == kDivFlat     ? vote_fused_counts_kernel<kUnroll, kDivFlat>
-                 : dm == kDivCertified ? vote_fused_counts_kernel<kUnroll, kDivCertified>
-                                       : vote_fused_counts_kernel<kUnroll, kDivExact>;
+        auto k = with_div(div_mode(c), [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
         if ((rc = set_lds(c, k, lds))) return rc;
         ProfScope ps(c, "vote_fused_counts");
         hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->cnt.as<uint8_t>(),

@@ -98,12 +98,6 @@ int gsx_synchronize(gsx_ctx* ctx);
  *                               33 % of the (wave, view) pairs of the benchmark scene, bit-identical results.  On its
  *                               own it measured 3-5 % slower (the kernel waited on seg-map gathers, which invisible
  *                               pairs never issued); together with "seg_coarse" it is worth 12 %
- *   "lds_batch"    (default 0)  read the LDS counters of a whole chunk of views in one round trip and
- *                               resolve repeated bins in registers (measured 2.6 % slower: VALU-bound)
- *   "fast_div"     (default 0)  projection through ONE reciprocal with a certified margin; lanes within 2^-20 of a
- *                               pixel boundary (and any non-finite case) take the exact IEEE divisions.  Bit-identical
- *                               (tested on 7e7 pairs and at pixel boundaries) but measured 1 % SLOWER: 15 fewer fp64
- *                               instructions per visible pair, yet both axes are evaluated before the first early-out
  *   "filter_project" (default 1) the two IEEE divisions of the projection are preceded by an fp32 filter (one v_rcp_f32, two
  *                               v_fma_f32) with a proven error bound: a wave whose lanes are all farther than the bound from
  *                               every pixel boundary takes floor() of the filter's result, any other wave the exact

@@ -30,7 +30,8 @@ with gsx.Context(0) as c:
         C = int(rng.choice([3, 20, 150, 254, 255]))
         opts = {"spatial_sort": int(rng.random() < 0.8), "seg_tiled": int(rng.random() < 0.9), "vote_unroll": int(rng.choice([2, 4, 8])),
                 "flat_project": int(rng.random() < 0.85), "wave_cull": int(rng.random() < 0.8), "seg_coarse": int(rng.random() < 0.8),
-                "xcd_swizzle": int(rng.choice([0, 1, 4, 32])), "fast_div": int(rng.random() < 0.3), "lds_batch": int(rng.random() < 0.2)}
+                "xcd_swizzle": int(rng.choice([0, 1, 4, 32]))}
+        rng.random(), rng.random()   # the draws of two retired options: a seed's trials stay the ones they were
         opts["filter_project"] = int(rng.random() < 0.8)
         opts["host_threads"] = int(rng.choice([1, 3, 16]))
         opts["labels_u8"] = int(rng.random() < 0.8)
@@ -126,7 +127,7 @@ with gsx.Context(0) as c:
                 bad = np.nonzero(got_slabs != want)[0]
                 print("DIAG slab votes differ:", len(bad), "of", n, "first", bad[:10], "got", got_slabs[bad[:10]], "want", want[bad[:10]],
                       "uniform import" if uniform_used else "blob import", "parts", parts, "world", world, flush=True)
-                for k, v in (("filter_project", 0), ("wave_cull", 0), ("lds_batch", 0), ("vote_unroll", 8), ("seg_coarse", 0), ("xcd_swizzle", 0)):
+                for k, v in (("filter_project", 0), ("wave_cull", 0), ("vote_unroll", 8), ("seg_coarse", 0), ("xcd_swizzle", 0)):
                     c.set_option(k, v)
                     sl = []
                     for r_ in range(world):

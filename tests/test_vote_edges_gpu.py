@@ -16,8 +16,8 @@ import vote_cases as vc
 
 pytestmark = pytest.mark.gpu
 
-OPTION_SETS = [{}, {"vote_unroll": 2}, {"vote_unroll": 4, "lds_batch": 1}, {"filter_project": 0}, {"seg_coarse": 0}, {"seg_tiled": 0},
-               {"flat_project": 0, "fast_div": 0}, {"flat_project": 0, "fast_div": 1}, {"wave_cull": 0}, {"spatial_sort": 0},
+OPTION_SETS = [{}, {"vote_unroll": 2}, {"vote_unroll": 4}, {"filter_project": 0}, {"seg_coarse": 0}, {"seg_tiled": 0},
+               {"flat_project": 0}, {"wave_cull": 0}, {"spatial_sort": 0},
                {"labels_u8": 0}]
 MAP_OPTION_SETS = [{"seg_tiled": t, "seg_coarse": c, "host_pack": h} for t in (0, 1) for c in (0, 1) for h in (0, 1)]
 

@@ -107,9 +107,9 @@ def test_results_do_not_depend_on_tuning_options(gsx):
     pos, cams, segs = scene.make_scene(n, 9, 480, 270, config_id=12, convention="w2c")
     sizes = [(480, 270)] * 9
     want = oracle.assign_labels(pos, cams, segs, sizes, threads=0)
-    for opts in ({"spatial_sort": 0, "xcd_swizzle": 0, "vote_unroll": 2, "seg_tiled": 0, "lds_batch": 0}, {"spatial_sort": 1, "xcd_swizzle": 0, "vote_unroll": 2},
-                 {"spatial_sort": 0, "xcd_swizzle": 1, "vote_unroll": 8, "fast_div": 0}, {"spatial_sort": 1, "xcd_swizzle": 1, "vote_unroll": 4, "seg_tiled": 0},
-                 {"flat_project": 0}, {"flat_project": 0, "vote_unroll": 2, "spatial_sort": 0, "fast_div": 1}, {"filter_project": 0},
+    for opts in ({"spatial_sort": 0, "xcd_swizzle": 0, "vote_unroll": 2, "seg_tiled": 0}, {"spatial_sort": 1, "xcd_swizzle": 0, "vote_unroll": 2},
+                 {"spatial_sort": 0, "xcd_swizzle": 1, "vote_unroll": 8}, {"spatial_sort": 1, "xcd_swizzle": 1, "vote_unroll": 4, "seg_tiled": 0},
+                 {"flat_project": 0}, {"flat_project": 0, "vote_unroll": 2, "spatial_sort": 0}, {"filter_project": 0},
                  {"flat_project": 1, "vote_unroll": 4, "seg_tiled": 0, "xcd_swizzle": 0}, {"wave_cull": 0}, {"seg_coarse": 0}, {"labels_u8": 0}, {"host_compact": 0}, {"host_compact": 0, "host_threads": 3}, {"host_pack": 0}, {"host_pack": 0, "seg_tiled": 0, "host_threads": 2}, {"seg_coarse": 1, "wave_cull": 1, "vote_unroll": 2},
                  {"wave_cull": 1, "vote_unroll": 2, "spatial_sort": 0}, {"wave_cull": 1, "vote_unroll": 4, "flat_project": 0}):
         with gsx.Context(0) as c:
@@ -147,7 +147,8 @@ def test_project_extreme_exponents(gsx):
     # fraction 0.5) although the true quotient is 0.5 and 1.0
     cams.append({"fx": 0.5, "fy": 1.0, "width": 1921, "height": 1081, "rotation": R, "position": [-1e308, -1e308, -1e308]})
     cams.append({"fx": 0.5, "fy": 1.0, "width": 1921, "height": 1081, "rotation": R, "position": [-4e307, -8e307, -1.6e308]})
-    for shared in (("fast_div", 1), ("fast_div", 0), ("flat_project", 1), ("filter_project", 0)):
+    # the branchy exact kernel, the default (filtered) one, the branchless one without the filter
+    for shared in (("flat_project", 0), ("flat_project", 1), ("filter_project", 0)):
         with gsx.Context(0) as c:
             c.set_option(*shared)
             c.upload_positions(pos)
@@ -157,29 +158,23 @@ def test_project_extreme_exponents(gsx):
                 assert np.array_equal(x, ox) and np.array_equal(y, oy), (shared, cam["fx"], cam["fy"])
 
 
-def test_certified_projection_equals_exact_divisions(gsx):
-    """The single-reciprocal path (fast_div=1) and the branchless block (flat_project=1) must give the very same
-    pixels as the branchy two-division form:
+def test_flat_projection_equals_exact_divisions_and_oracle(gsx):
+    """The branchless block (flat_project=1, behind its fp32 filter) must give the very same pixels as the branchy
+    two-division form:
     3 M Gaussians x 24 views GPU-vs-GPU, and points sitting ON and within a few ulps of pixel boundaries
-    (where the certified margin must hand over to the exact path) against the oracle."""
+    (where the filter's margin must hand over to the exact divisions) against the oracle."""
     n = 3_000_000
     pos = scene.make_positions(n, scene.BASE_SEED + 3)
     cams = scene.make_cameras(200, 1920, 1080, convention="w2c")[::9][:24]
-    with gsx.Context(0) as fast, gsx.Context(0) as exact, gsx.Context(0) as flat:
-        exact.set_option("fast_div", 0)
+    with gsx.Context(0) as exact, gsx.Context(0) as flat:
         exact.set_option("flat_project", 0)
-        fast.set_option("fast_div", 1)
-        fast.set_option("flat_project", 0)
         flat.set_option("flat_project", 1)
-        fast.upload_positions(pos)
         exact.upload_positions(pos)
         flat.upload_positions(pos)
         vis = 0
         for cam in cams:
-            xf, yf = fast.project_all(cam)
             xe, ye = exact.project_all(cam)
             xl, yl = flat.project_all(cam)
-            assert np.array_equal(xf, xe) and np.array_equal(yf, ye)
             assert np.array_equal(xl, xe) and np.array_equal(yl, ye)
             vis += int((xe >= 0).sum())
         assert vis > 0.4 * n * len(cams)
@@ -198,7 +193,7 @@ def test_certified_projection_equals_exact_divisions(gsx):
                 q[:, 0] = np.nextafter(q[:, 0], np.float32(np.inf if sh > 0 else -np.inf)) if abs(sh) == 1 else \
                     np.nextafter(np.nextafter(q[:, 0], np.float32(np.inf if sh > 0 else -np.inf)), np.float32(np.inf if sh > 0 else -np.inf))
             ox, oy = oracle.project_many(q, cam)
-            for c in (fast, exact, flat):
+            for c in (exact, flat):
                 c.upload_positions(q)
                 x, y = c.project_all(cam)
                 assert np.array_equal(x, ox) and np.array_equal(y, oy)
@@ -1063,6 +1058,13 @@ def test_empty_and_degenerate(ctx):
         assert ctx.vote_finalize()[0] == first
 
 
+def test_retired_options_are_unknown(ctx):
+    """fast_div and lds_batch (measured, rejected, removed: DESIGN.md) are refused like any key the library never had."""
+    for key in ("fast_div", "lds_batch"):
+        with pytest.raises(ValueError, match="unknown option"):
+            ctx.set_option(key, 1)
+
+
 def test_errors(ctx, gsx):
     cam = scene.make_cameras(1, 64, 48, convention="w2c")[0]
     ctx.upload_positions(np.zeros((10, 3), np.float32))
@@ -1238,8 +1240,7 @@ def test_randomised_small_configurations(gsx):
             c.set_option("spatial_sort", int(rng.integers(0, 2)))
             c.set_option("seg_tiled", int(rng.integers(0, 2)))
             c.set_option("vote_unroll", int(rng.choice([2, 4, 8])))
-            c.set_option("lds_batch", int(rng.integers(0, 2)))
-            c.set_option("fast_div", int(rng.integers(0, 2)))
+            rng.integers(0, 2), rng.integers(0, 2)   # the draws of two retired options: the 40 configurations stay the ones they were
             c.set_option("flat_project", int(rng.integers(0, 2)))
             c.set_option("wave_cull", int(rng.integers(0, 2)))
             c.set_option("seg_coarse", int(rng.integers(0, 2)))

@@ -3,7 +3,7 @@
 #   tools/ab.sh <tag> "<bench args of run 1>" "<bench args of run 2>" ...
 # e.g. tools/ab.sh filter "--opt filter_project=1" "--opt filter_project=0" "--opt filter_project=1" "--opt filter_project=0"
 #      tools/ab.sh shapes "--gaussians 500000 --views 16 --width 1280 --height 720" "--gaussians 10000000 --views 125 --width 3840 --height 2160"
-#      GSX_LIBRARY=tools/ablate/libgsx_2.so tools/ab.sh ablate ""        (a timing-only build of tools/ablate.sh)
+#      tools/ab.sh build "GSX_LIBRARY=/path/to/parent/libgsx.so" "" "GSX_LIBRARY=/path/to/parent/libgsx.so" ""   (another build of the same C ABI)
 #      AB_STEPS=20 AB_WARMUP=5 tools/ab.sh affinity "GSX_HOST_AFFINITY=l3" "GSX_HOST_AFFINITY=node" "GSX_HOST_AFFINITY=0"   (per-run environment)
 # Replaces round 1-2's one-off scripts (gpt_ab, occ_ab, mem_ab, views_ab, configs_ab, ablate_run, render_ab, sort_ab, ...).
 set -o pipefail
