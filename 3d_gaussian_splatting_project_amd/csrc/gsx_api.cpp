@@ -591,6 +591,10 @@ int gsx_render_debug(gsx_ctx* ctx, uint8_t* buffer_out, uint32_t* order_out, uin
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::render_debug(c, buffer_out, order_out, texdata_out, bucket_out); });
 }
+int gsx_debug_render_scene(gsx_ctx* ctx, int32_t* labels_out, float* sh_out, int32_t* sh_degree_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::debug_render_scene(c, labels_out, sh_out, sh_degree_out); });
+}
 int gsx_debug_render_pre(gsx_ctx* ctx, int32_t num_views, const gsx_camera* cams, int32_t width, int32_t height, int32_t multi,
                          int32_t compact, const gsx_debug_pre_view* out) {
     CTX_OR_FAIL(ctx);

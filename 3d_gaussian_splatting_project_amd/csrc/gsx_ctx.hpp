@@ -404,6 +404,7 @@ int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* con
 void render_release_twin(Ctx* c);
 int hit_test(Ctx* c, const gsx_camera* cam, int W, int H, double x, double y, int32_t* label_out, int64_t* index_out);
 int render_debug(Ctx* c, uint8_t* buffer_out, uint32_t* order_out, uint32_t* tex_out, uint32_t* bucket_out);
+int debug_render_scene(Ctx* c, int32_t* labels_out, float* sh_out, int32_t* sh_degree_out);
 int debug_render_pre(Ctx* c, int nv, const gsx_camera* cams, int W, int H, int multi, int compact, const gsx_debug_pre_view* out);
 int debug_exclusive_scan(Ctx* c, const uint32_t* in, uint32_t* out, long long n, unsigned long long* grand_dev);  // test hook: exclusive_scan_u32
 int debug_ranges(Ctx* c, const uint32_t* keys, const unsigned long long* total_dev, long long cap, int nlists, int2* ranges);  // test hook: ranges_kernel as a frame launches it

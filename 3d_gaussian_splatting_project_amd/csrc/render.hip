@@ -993,6 +993,7 @@ int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const
                   const float* f_dc, const int32_t* labels) {
     GSX_HIP(c, hipSetDevice(c->device));
     c->rn = 0;
+    c->r_sh_on = false;     // the SH planes were laid out in the order that goes away here, also when n == 0
     c->r_edits_on = false;  // the edit codes were resolved against the labels that go away here
     c->r_edit_hidden_n = 0;
     if (n < 0 || (n > 0 && (!xyz || !f_dc || (scale && (!rot || !opacity)))))
@@ -1047,7 +1048,6 @@ int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const
     GSX_HIP(c, hipGetLastError());
     GSX_HIP(c, hipStreamSynchronize(c->stream));
     c->rn = n;
-    c->r_sh_on = false;
     return GSX_OK;
 }
 
@@ -1753,8 +1753,10 @@ __global__ __launch_bounds__(kRB) void hit_partial_kernel(const uint4* __restric
     if (threadIdx.x == 0) partial[blockIdx.x] = best;
 }
 
+// labels: the exact int32 labels in importance order (labels_pack_kernel), the worker's labelData - not the texture word,
+// which holds the label rounded to fp32
 __global__ __launch_bounds__(kRB) void hit_final_kernel(const HitKey* __restrict__ partial, int m,
-                                                         const uint4* __restrict__ tex, long long* __restrict__ out) {
+                                                         const int* __restrict__ labels, long long* __restrict__ out) {
     __shared__ HitKey sh[4];
     HitKey best{0.0, 0.0, -1};
     for (int t = threadIdx.x; t < m; t += kRB)
@@ -1762,7 +1764,7 @@ __global__ __launch_bounds__(kRB) void hit_final_kernel(const HitKey* __restrict
     best = hit_reduce_block(best, sh);
     if (threadIdx.x == 0) {
         out[0] = best.idx;
-        out[1] = best.idx >= 0 ? (long long)(int)__uint_as_float(tex[2 * best.idx].w) : -999999LL;  // labelData[i]
+        out[1] = best.idx >= 0 ? (long long)labels[best.idx] : -999999LL;  // labelData[i], gs.js:390
     }
 }
 
@@ -1788,7 +1790,7 @@ int hit_test(Ctx* c, const gsx_camera* cam, int W, int H, double x, double y, in
             ProfScope ps(c, "hit_test");
             hipLaunchKernelGGL(hit_partial_kernel, dim3(blocks), dim3(kRB), 0, c->stream, c->r_tex.as<uint4>(), (long long)c->rn, u,
                                partial);
-            hipLaunchKernelGGL(hit_final_kernel, dim3(1), dim3(kRB), 0, c->stream, partial, blocks, c->r_tex.as<uint4>(), out);
+            hipLaunchKernelGGL(hit_final_kernel, dim3(1), dim3(kRB), 0, c->stream, partial, blocks, c->r_labels.as<int>(), out);
         }
         GSX_HIP(c, hipGetLastError());
         GSX_HIP(c, hipMemcpyAsync(res, out, sizeof res, hipMemcpyDeviceToHost, c->stream));
@@ -1809,6 +1811,22 @@ int render_debug(Ctx* c, uint8_t* buffer_out, uint32_t* order_out, uint32_t* tex
     if (bucket_out) {
         if (c->r_bucket.cap < 4 * n) return fail(c, GSX_E_STATE, "render_debug: no view has been rendered yet");
         GSX_HIP(c, hipMemcpyAsync(bucket_out, c->r_bucket.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    }
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    return GSX_OK;
+}
+
+// gsx_debug_render_scene: what labels_pack_kernel and sh_pack_kernel wrote at upload, and the SH state
+int debug_render_scene(Ctx* c, int32_t* labels_out, float* sh_out, int32_t* sh_degree_out) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->rn;
+    const bool sh = n > 0 && c->r_sh_on;
+    if (sh_degree_out) *sh_degree_out = sh ? c->r_sh_deg : -1;
+    if (n == 0) return GSX_OK;
+    if (labels_out) GSX_HIP(c, hipMemcpyAsync(labels_out, c->r_labels.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    if (sh_out && sh) {
+        const size_t K = (size_t)(c->r_sh_deg + 1) * (size_t)(c->r_sh_deg + 1);
+        GSX_HIP(c, hipMemcpyAsync(sh_out, c->r_shc.p, sizeof(float) * 3 * K * n, hipMemcpyDeviceToHost, c->stream));
     }
     GSX_HIP(c, hipStreamSynchronize(c->stream));
     return GSX_OK;

@@ -512,6 +512,17 @@ class Context:
                                          bk.ctypes.data if buckets else None), self.h)
         return (buf, order, tex, bk) if buckets else (buf, order, tex)
 
+    def debug_render_scene(self):
+        """(labels (n,) i32 exact, in importance order; SH planes (K, 3, n) f32 or None while the SH colour is off; degree or
+        -1) — test hook, gsx_debug_render_scene.  The row count is the library's (gsx_num_splats)."""
+        n = self._lib.gsx_num_splats(self.h)
+        deg = C.c_int32(-2)
+        check(self._lib.gsx_debug_render_scene(self.h, None, None, C.byref(deg)), self.h)
+        labels = np.empty(n, np.int32)
+        sh = np.empty(((deg.value + 1) ** 2, 3, n), np.float32) if deg.value >= 0 else None
+        check(self._lib.gsx_debug_render_scene(self.h, labels.ctypes.data, None if sh is None else sh.ctypes.data, None), self.h)
+        return labels, sh, deg.value
+
     def debug_render_pre(self, cameras, width, height, multi=False, compact=True):
         """The rasterizer's per-splat pre pass and depth-bucket kernel for 1..6 cameras (test hook, gsx_debug_render_pre; multi:
         one launch of the several-view kernel instead of one launch per view) -> per view a dict: depth (n,) i32, rect (n,) u32,

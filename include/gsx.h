@@ -381,6 +381,8 @@ int gsx_vote_debug_planes(gsx_ctx* ctx, uint16_t* counts_out, uint16_t* first_ou
  *   xyz n x 3, scale n x 3 (log), rot n x 4 (w first), opacity n (logit), f_dc n x 3, labels n (or NULL).
  *   scale == NULL selects the viewer's fallback (scale 0.01, identity rotation, gs.js:559-563);
  *   opacity == NULL -> alpha 255 (gs.js:576).
+ * Where a splat's importance exp(s0) * exp(s1) * exp(s2) * sigmoid(opacity) is NaN (Infinity * 0) the importance order is
+ * unspecified: the reference's sort comparator returns NaN there (gs.js:527).
  * rgba_out: height x width x 4 floats, row 0 = top row, premultiplied colour exactly as the fragment
  * shader emits it (float, not the canvas's 8-bit quantisation); NULL leaves the image on the device.
  * ------------------------------------------------------------------------------------------- */
@@ -411,7 +413,8 @@ int64_t gsx_render_num_pairs_consumed(const gsx_ctx* ctx);
 /* Selection hit test — performHitTesting, gs.js:361-395: the label of the splat whose projected centre is
  * nearest to (x, y) (canvas pixels, y measured from the BOTTOM as the viewer's click handler does,
  * gs.js:1377-1378) within 10 px, nearer NDC depth breaking exact ties; NO_SELECTION (-999999) if none.
- * *index_out = importance-order row of that splat or -1.  Uses the splats of gsx_upload_splats. */
+ * *index_out = importance-order row of that splat or -1.  Uses the splats of gsx_upload_splats; *label_out is the
+ * exact int32 that gsx_upload_splats was given for that splat (labelData[i], gs.js:390), not the texture's fp32 copy. */
 int gsx_hit_test(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, double x, double y,
                  int32_t* label_out, int64_t* index_out);
 /* Label edits — what the viewer does WITH the labels of gsx_upload_splats: highlight, recolour, hide and displace the
@@ -482,6 +485,11 @@ int64_t gsx_render_num_hidden(const gsx_ctx* ctx);
  * depth buckets (65536 = dropped by the JS counting sort, gs.js:443-457) */
 int gsx_render_debug(gsx_ctx* ctx, uint8_t* buffer_out, uint32_t* order_out, uint32_t* texdata_out,
                      uint32_t* bucket_out);
+/* test hook (any pointer may be NULL): what else an upload left on the device.  labels_out: the n exact int32 labels in
+ * importance order (-999999 each without labels).  sh_out: the 3 * K * n floats of the SH planes as laid out by
+ * gsx_upload_sh, coef[k][c][j] with K = (degree + 1)^2, k = 0 the f_dc plane, c the channel, j the importance-order row;
+ * left alone while the SH colour is off.  *sh_degree_out: the degree 0..3, or -1 while the SH colour is off. */
+int gsx_debug_render_scene(gsx_ctx* ctx, int32_t* labels_out, float* sh_out, int32_t* sh_degree_out);
 /* test hook: the rasterizer's per-splat pre pass (depth keys, vertex shader, colours, tile rectangles) and the depth-bucket
  * kernel, run on the uploaded scene with the current SH and edit state for num_views cameras (1..6) of one frame size, and what
  * they wrote, per view.  multi = 0: one pre-kernel launch per view, as gsx_render_view issues it; multi = 1: ONE launch of the

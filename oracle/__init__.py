@@ -196,6 +196,14 @@ def texture(buffer, labels=None):
     return tex
 
 
+def float_to_half(values):
+    """floatToHalf (gs.js:248-275) of each value, the function oracle.texture packs its halves with -> uint32 array."""
+    f = lib().gsxo_float_to_half
+    f.restype = C.c_uint32
+    f.argtypes = [C.c_double]
+    return np.array([f(float(v)) for v in np.asarray(values, np.float64).reshape(-1)], np.uint32)
+
+
 def view_matrix(cam):
     R = np.ascontiguousarray(cam["rotation"], dtype=np.float64).reshape(9)
     p = np.ascontiguousarray(cam["position"], dtype=np.float64)

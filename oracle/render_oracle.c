@@ -80,6 +80,9 @@ static uint32_t js_float_to_half(double v) {
     return (uint32_t)((sign << 15) | (newExp << 10) | (frac >> 13));
 }
 
+/* floatToHalf alone, for tests that feed it bit patterns no covariance reaches (negative zero, NaN payloads, every exponent) */
+uint32_t gsxo_float_to_half(double v) { return js_float_to_half(v); }
+
 static uint32_t js_pack_half2(double x, double y) { return js_float_to_half(x) | (js_float_to_half(y) << 16); }
 
 /* ------------------------------------------------------------------------------------------------
