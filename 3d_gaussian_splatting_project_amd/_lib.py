@@ -12,6 +12,7 @@ GSX_OK = 0
 GSX_E_INVALID, GSX_E_HIP, GSX_E_STATE, GSX_E_RANGE, GSX_E_UNSUPPORTED, GSX_E_IO = -1, -2, -3, -4, -5, -6
 GSX_SEG_I32, GSX_SEG_I64, GSX_SEG_U8, GSX_SEG_U8_LABELS = 0, 1, 2, 3
 GSX_MASK_U8, GSX_MASK_I32, GSX_MASK_I64, GSX_MASK_F32, GSX_MASK_F64 = 0, 1, 2, 3, 4
+GSX_F32, GSX_F16, GSX_BF16 = 0, 1, 2
 
 
 class GsxError(RuntimeError):
@@ -166,6 +167,11 @@ _SIGS = {
     "gsx_iou_from_counts": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsx_iou_best": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsx_debug_iou_constants": (C.c_int, [C.c_void_p]),
+    "gsx_segmap_from_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p]),
+    "gsx_segmap_from_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p]),
+    "gsx_debug_segmap_constants": (C.c_int, [C.c_void_p]),
     "gsx_vote_culled": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "gsx_debug_filter_check": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gsx_debug_cull_planes": (C.c_int, [C.POINTER(Camera), C.c_void_p]),

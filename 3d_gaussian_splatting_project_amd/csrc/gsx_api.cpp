@@ -673,6 +673,22 @@ int gsx_debug_iou_constants(int32_t* out) {
     return GSX_OK;
 }
 
+int gsx_segmap_from_logits(gsx_ctx* ctx, const void* logits_dev, int32_t dtype, int32_t n, int32_t C, int32_t h, int32_t w, int32_t out_w,
+                           int32_t out_h, int32_t* maps_dev) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::segmap_from_logits(c, logits_dev, dtype, n, C, h, w, out_w, out_h, maps_dev); });
+}
+int gsx_segmap_from_masks(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, int32_t K, int32_t mh, int32_t mw, const float* cls_dev,
+                          const float* conf_dev, int32_t out_w, int32_t out_h, int32_t* map_dev) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::segmap_from_masks(c, masks_dev, dtype, K, mh, mw, cls_dev, conf_dev, out_w, out_h, map_dev); });
+}
+int gsx_debug_segmap_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_segmap_constants: NULL argument");
+    gsx::segmap_constants(out);
+    return GSX_OK;
+}
+
 int gsx_vote_culled(gsx_ctx* ctx, int64_t* wave_views, int32_t reset) {
     CTX_OR_FAIL(ctx);
     if (!wave_views) return gsx::fail(c, GSX_E_INVALID, "vote_culled: NULL argument");

@@ -317,6 +317,9 @@ struct Ctx {
     bool iou_ev_pending[2] = {false, false};
     int iou_slot = 0;
 
+    // class maps from network outputs (segmap.hip)
+    DevBuf seg_low;                      // int32 [n][h w]: the maps at the network's resolution, between the two kernels of a call
+
     // profiling
     bool prof_on = false;
     std::vector<std::string> prof_names;
@@ -430,6 +433,11 @@ int iou_label_maps(Ctx* c, bool device, int n_pairs, const void* const* pred, in
 int masks_top_index(Ctx* c, int n_masks, const void* const* masks, int mask_dtype, int h, int w, int32_t* index_out);
 void iou_release(Ctx* c);  // pinned staging pair and its events (gsx_destroy)
 void iou_constants(int32_t out[8]);
+// segmap.hip
+int segmap_from_logits(Ctx* c, const void* logits, int dtype, int n, int C, int h, int w, int out_w, int out_h, int32_t* maps);
+int segmap_from_masks(Ctx* c, const void* masks, int dtype, int K, int mh, int mw, const float* cls, const float* conf, int out_w, int out_h,
+                      int32_t* map);
+void segmap_constants(int32_t out[8]);
 void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, int img_w, int img_h);
 
 }  // namespace gsx

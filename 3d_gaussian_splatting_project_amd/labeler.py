@@ -46,11 +46,13 @@ class Context:
         self._vote_view_addr = C.cast(self._lib.gsx_vote_view, C.c_void_p).value   # for the CPython fast path
         self.device = int(device)
         self._keep_alive = []   # device maps handed to vote_view until the ctx stream has consumed them
+        self._ext = None        # the ctx stream as torch sees it (segmap_from_*)
 
     def close(self):
         if getattr(self, "h", None):
             self._lib.gsx_destroy(self.h)
             self.h = None
+            self._ext = None
 
     def __del__(self):
         try:
@@ -678,6 +680,86 @@ class Context:
         self._iou_call(self._lib.gsx_masks_top_index, None, [m], lambda a: (len(m[1]), a[0], m[2], h, w, out.ctypes.data))
         return out
 
+    # -- class maps from network outputs (deep_learning_segmentation.py:85-124, 142-144; csrc/segmap.hip) ---------------------------
+    _FLOAT_DT = {"torch.float32": _lib.GSX_F32, "torch.float16": _lib.GSX_F16, "torch.bfloat16": _lib.GSX_BF16}
+
+    def _seg_enter(self):
+        """The ctx stream waits, on the device, for an event on torch's current stream - the producer of the inputs.
+        Returns (ctx stream as torch's, torch's current stream); the caller lets the latter wait for the former once its kernels
+        are queued, which also keeps torch's allocator honest: it hands a freed block only to work on the stream it was
+        allocated on, and that stream is then behind the kernels that read or wrote the block.  (No Tensor.record_stream: it
+        would leave the allocator with events to record on the ctx stream when a tensor dies - after close(), on a stream
+        that no longer exists.)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if self._ext is None:
+            self._ext = torch.cuda.ExternalStream(self.stream, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        self._ext.wait_stream(cur)
+        return self._ext, cur
+
+    def order_after_torch(self):
+        """The ctx stream waits, on the device, for torch's current stream: call it before vote_view on a tensor some torch
+        operation has just written.  (segmap_from_logits / segmap_from_masks do it themselves; their results need none.)"""
+        self._seg_enter()
+
+    def _seg_input(self, t, what, dims):
+        if not hasattr(t, "data_ptr") or not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{what} must be a torch tensor on GPU {self.device}")
+        if t.dim() not in dims:
+            raise ValueError(f"{what} must have {' or '.join(str(d) for d in dims)} dimensions (got {tuple(t.shape)})")
+        dt = self._FLOAT_DT.get(str(t.dtype))
+        if dt is None:
+            raise ValueError(f"{what} must be float32, float16 or bfloat16 (got {t.dtype})")
+        return t.contiguous(), dt
+
+    def segmap_from_logits(self, logits, size):
+        """int32 class map(s) at the image size from a network's logits, on the device: logits (C, h, w) -> (height, width),
+        (n, C, h, w) -> (n, height, width); size = (width, height).  torch.argmax over the channels, then OpenCV's nearest
+        resize (deep_learning_segmentation.py:142-144).  Nothing is synchronised; the result goes straight into vote_view /
+        vote_views_device, and torch's current stream is ordered behind it."""
+        import torch
+        t, dt = self._seg_input(logits, "logits", (3, 4))
+        n, ch, h, w = (1,) + tuple(t.shape) if t.dim() == 3 else tuple(t.shape)
+        W, H = int(size[0]), int(size[1])
+        if W <= 0 or H <= 0:
+            raise ValueError(f"size must be positive (got {W} x {H})")
+        out = torch.empty((H, W) if t.dim() == 3 else (n, H, W), dtype=torch.int32, device=t.device)
+        ext, cur = self._seg_enter()
+        check(self._lib.gsx_segmap_from_logits(self.h, t.data_ptr(), dt, n, ch, h, w, W, H, out.data_ptr()), self.h)
+        cur.wait_stream(ext)
+        return out
+
+    def segmap_from_masks(self, masks, cls, conf, size):
+        """int32 (height, width) class map from instance masks (K, mh, mw), class ids (K,) and confidences (K,), all on the
+        device: the loop of process_yolo_segmentation (deep_learning_segmentation.py:113-124).  -1 where no accepted instance
+        (conf > 0.5) has a mask value > 0.5; later instances overwrite earlier ones.  masks may be None or empty (K = 0).
+        conf is never read on the host: nothing is synchronised."""
+        import torch
+        W, H = int(size[0]), int(size[1])
+        if W <= 0 or H <= 0:
+            raise ValueError(f"size must be positive (got {W} x {H})")
+        dev = torch.device("cuda", self.device)
+        K = 0 if masks is None else int(masks.shape[0])
+        if K == 0:
+            mh, mw = (1, 1) if masks is None or masks.dim() != 3 or 0 in masks.shape[1:] else (int(masks.shape[1]), int(masks.shape[2]))
+            out = torch.empty((H, W), dtype=torch.int32, device=dev)
+            ext, cur = self._seg_enter()
+            check(self._lib.gsx_segmap_from_masks(self.h, None, _lib.GSX_F32, 0, mh, mw, None, None, W, H, out.data_ptr()), self.h)
+            cur.wait_stream(ext)
+            return out
+        t, dt = self._seg_input(masks, "masks", (3,))
+        mh, mw = int(t.shape[1]), int(t.shape[2])
+        cc = [torch.as_tensor(v, device=dev).to(torch.float32).reshape(-1).contiguous() for v in (cls, conf)]
+        if any(v.numel() != K for v in cc):
+            raise ValueError(f"cls and conf must hold one value per mask ({K})")
+        out = torch.empty((H, W), dtype=torch.int32, device=dev)
+        ext, cur = self._seg_enter()
+        check(self._lib.gsx_segmap_from_masks(self.h, t.data_ptr(), dt, K, mh, mw, cc[0].data_ptr(), cc[1].data_ptr(), W, H, out.data_ptr()),
+              self.h)
+        cur.wait_stream(ext)
+        return out
+
     def synchronize(self):
         check(self._lib.gsx_synchronize(self.h), self.h)
         self._keep_alive.clear()
@@ -940,6 +1022,14 @@ def iou_best(iou):
     best, idx = np.empty(iou.shape[0], np.float64), np.empty(iou.shape[0], np.int32)
     check(_lib.lib().gsx_iou_best(iou.shape[0], iou.shape[1], iou.ctypes.data, best.ctypes.data, idx.ctypes.data))
     return best, idx
+
+
+def segmap_constants():
+    """Test hook, host only: the units the class-map kernels are built on (gsx_debug_segmap_constants)."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_segmap_constants(out.ctypes.data))
+    return {"pix_wg": int(out[0]), "slices": int(out[1]), "step": int(out[2]), "vec": int(out[3]), "resize_vec": int(out[4]),
+            "resize_block": int(out[5]), "block": int(out[6])}
 
 
 def iou_constants():

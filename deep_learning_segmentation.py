@@ -7,7 +7,9 @@ contract.  The per-Gaussian projection + vote (reference lines 43-82, 252-308) r
 kernels behind libgsx.so; PLY parsing/writing is native too.  The 2-D segmentation networks stay what
 they are in the reference (Hugging Face / Ultralytics models, imported lazily): they need weights that
 are fetched by name, so `--segmap_dir` lets a run consume the `<image>_segmap.npy` files the reference
-itself writes next to every segmented image (reference line 165) instead of running a network.
+itself writes next to every segmented image (reference line 165) instead of running a network.  What follows the
+network - arg-max and nearest resize of SegFormer's logits, the compositing of YOLO's instances (reference lines 85-124,
+142-144) - runs in HIP kernels too, and the class map goes from the network to the vote without leaving the GPU.
 
 Added flags: --segmap_dir DIR, --n_classes C (default: 150 for the ADE20K models, 80 for YOLO), --gpus N
 (informational).  Several GPUs: `python -m torch.distributed.run --nproc-per-node N deep_learning_segmentation.py
@@ -69,38 +71,52 @@ def initialize_model(model_type, device):
     raise ValueError(f"Unknown model type: {model_type}")
 
 
-def segment_image(image_path, output_dir, processor, model, device, model_type):
-    """int32 (H, W) class map of one image, -1 = no class; also saved as <image>_segmap.npy.
-    OUT OF SCOPE of this build: kept minimal so that the CLI still runs end to end where the
-    networks' weights are available; it cannot be tested here (no weights, no network).  The hot path only depends on its
-    OUTPUT contract (a 2-D integer map), which `--segmap_dir` feeds directly.  Nearest-neighbour resizes use
-    torch's legacy 'nearest' (source index = floor(dst * scale)), the rule of the reference's cv2.INTER_NEAREST."""
+def _segment_image_device(image, processor, model, device, model_type, ctx):
+    """The device half of segment_image: network -> int32 (H, W) class map as a torch tensor on ctx's GPU, -1 = no class.
+    The network's output never leaves the device: SegFormer logits and YOLO instances go through libgsx's own kernels
+    (Context.segmap_from_logits / segmap_from_masks: torch.argmax's rule, OpenCV's nearest resize, the reference's instance
+    loop - reference lines 85-124, 142-144), Mask2Former's post-processed map is taken as it is."""
     import torch
-    from PIL import Image
-    os.makedirs(output_dir, exist_ok=True)
-    image = Image.open(image_path)
     width, height = image.size
     if model_type == "yolo":
         res = model(image, verbose=False)[0]
-        seg_map = np.full(res.orig_shape, -1, dtype=np.int32)
-        if getattr(res, "masks", None) is not None and res.boxes is not None:
-            masks = torch.nn.functional.interpolate(res.masks.data[None].float(), size=tuple(res.orig_shape), mode="nearest")[0]
-            for mask, box in zip(masks, res.boxes):
-                if float(box.conf[0]) > 0.5:
-                    seg_map = np.where(mask.cpu().numpy() > 0.5, int(box.cls[0]), seg_map)
-        seg_map = seg_map.astype(np.int32)
-    else:
-        inputs = {k: v.to(device) for k, v in processor(images=image, return_tensors="pt").items()}
-        with torch.no_grad():
-            outputs = model(**inputs)
-        if model_type == "segformer":
-            low = outputs.logits.argmax(dim=1)[None].float()
-            seg_map = torch.nn.functional.interpolate(low, size=(height, width), mode="nearest")[0, 0].cpu().numpy().astype(np.int32)
-        else:
-            result = processor.post_process_instance_segmentation(outputs, target_sizes=[(height, width)])[0]
-            seg_map = result["segmentation"].cpu().numpy().astype(np.int32)
+        orig_height, orig_width = res.orig_shape
+        masks = getattr(res, "masks", None)
+        if masks is None or res.boxes is None:
+            return ctx.segmap_from_masks(None, None, None, (orig_width, orig_height))
+        K = min(int(masks.data.shape[0]), int(res.boxes.cls.shape[0]))     # the reference zips the masks with the boxes
+        return ctx.segmap_from_masks(masks.data[:K], res.boxes.cls[:K], res.boxes.conf[:K], (orig_width, orig_height))
+    inputs = {k: v.to(device) for k, v in processor(images=image, return_tensors="pt").items()}
+    with torch.no_grad():
+        outputs = model(**inputs)
+    if model_type == "segformer":
+        return ctx.segmap_from_logits(outputs.logits[0], (width, height))
+    result = processor.post_process_instance_segmentation(outputs, target_sizes=[(height, width)])[0]
+    seg_dev = result["segmentation"].to(torch.int32)
+    ctx.order_after_torch()                   # torch wrote it on its own stream: the vote's stream waits for that, on the device
+    return seg_dev
+
+
+def _save_segmap(image_path, output_dir, seg_map):
     base = os.path.splitext(os.path.basename(image_path))[0]
     np.save(os.path.join(output_dir, f"{base}_segmap.npy"), seg_map)
+
+
+def segment_image(image_path, output_dir, processor, model, device, model_type, ctx=None):
+    """int32 (H, W) class map of one image, -1 = no class; also saved as <image>_segmap.npy (reference line 165).
+    The map is made on the GPU (_segment_image_device) and copied down here; assign_labels votes the device map instead and
+    copies it down afterwards.  The reference's side-by-side PNG (its lines 198-214) is not written."""
+    from PIL import Image
+    os.makedirs(output_dir, exist_ok=True)
+    image = Image.open(image_path)
+    own = ctx is None
+    ctx = ctx or gsx.Context()
+    try:
+        seg_map = _segment_image_device(image, processor, model, device, model_type, ctx).cpu().numpy()
+    finally:
+        if own:
+            ctx.close()
+    _save_segmap(image_path, output_dir, seg_map)
     return seg_map
 
 
@@ -148,9 +164,14 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
             print(f"Processing image {os.path.basename(img_path)}...")
             if segmap_dir is not None:
                 seg_map = np.load(os.path.join(segmap_dir, camera["img_name"] + "_segmap.npy"))
-            else:
-                seg_map = segment_image(img_path, output_dir, processor, model, device, model_type)
-            ctx.vote_view(camera, seg_map, _image_size(img_path))
+                ctx.vote_view(camera, seg_map, _image_size(img_path))
+                continue
+            from PIL import Image
+            os.makedirs(output_dir, exist_ok=True)
+            image = Image.open(img_path)
+            seg_dev = _segment_image_device(image, processor, model, device, model_type, ctx)
+            ctx.vote_view(camera, seg_dev, image.size)          # the map goes from the network to the vote on the device ...
+            _save_segmap(img_path, output_dir, seg_dev.cpu().numpy())   # ... and is copied down behind it, for the .npy only
         if world > 1:
             return gsx.dist.exchange_labels_gather(gsx.dist.GpuGatherShard(ctx), cap_views=total)
         return ctx.vote_finalize()

@@ -67,6 +67,14 @@ typedef enum gsx_mask_dtype {
     GSX_MASK_F64 = 4
 } gsx_mask_dtype;
 
+/* element type of a network output handed to gsx_segmap_from_logits / gsx_segmap_from_masks.  fp16 and bf16 are compared by
+ * value, with no rounding step: every one of their values is an fp32 value. */
+typedef enum gsx_float_dtype {
+    GSX_F32 = 0,
+    GSX_F16 = 1,
+    GSX_BF16 = 2
+} gsx_float_dtype;
+
 /* ---------------------------------------------------------------------------------------------
  * context
  * ------------------------------------------------------------------------------------------- */
@@ -755,6 +763,43 @@ int gsx_iou_best(int32_t n_masks, int32_t n_gt, const double* iou, double* best_
 int gsx_debug_iou_constants(int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * class maps from a segmentation network's output (dls.py:85-124, 142-144; SURVEY row 3's post-processing): int32 maps at the
+ * image size, written on the device for gsx_vote_view_device / gsx_vote_views_device - no byte of a map visits the host.
+ * Both calls run on the ctx stream (gsx_stream), which the caller orders behind the producer of the inputs, write only the
+ * output map(s), read nothing back and synchronise nothing; inputs and outputs stay alive until the stream has passed.
+ *
+ * Nearest resize, per axis from S source to D destination pixels: s(d) = min(floor(d * (1.0 / ((double)D / S))), S - 1), in
+ * double with two roundings - OpenCV's resizeNN, the rule behind the reference's cv2.INTER_NEAREST.  It is not
+ * floor(d * S / D) and not torch's float32 floor(d * (float)S / D): S = 2, D = 98 sends destination 49 to source 0 here and
+ * to source 1 under both others.  It covers upsampling and downsampling alike.  cv2 is not installed on this machine, so this
+ * rule is restated from OpenCV's source and cannot be executed against.  Everything else is pinned by running the reference.
+ *
+ * Errors, before anything touches the device: GSX_E_INVALID for a NULL ctx or pointer (masks_dev, cls_dev and conf_dev may be
+ * NULL only when K == 0), a size <= 0 (K == 0 is allowed), an unknown dtype, a pointer not aligned to its element (element
+ * alignment is all that is asked: a view into a larger tensor works); GSX_E_UNSUPPORTED for C > 65535, for h * w,
+ * out_h * out_w or n * out_h * out_w >= 2^31, and for n * ceil(h * w / 128) >= 2^31 workgroups.
+ * ------------------------------------------------------------------------------------------- */
+/* replaces dls.py:142-144 (outputs.logits.argmax(dim=1) and the cv2.resize of the map to the image size).
+ * logits_dev: n contiguous volumes (n, C, h, w) of gsx_float_dtype dtype; maps_dev: int32 (n, out_h, out_w),
+ * map[y][x] = argmax_c logits[c][sy(y)][sx(x)].  The arg-max is torch.argmax's: the first index of the maximum wins, a NaN
+ * counts as the maximum and the first NaN wins, -0.0 == +0.0, all -inf gives 0. */
+int gsx_segmap_from_logits(gsx_ctx* ctx, const void* logits_dev, int32_t dtype, int32_t n, int32_t C, int32_t h, int32_t w,
+                           int32_t out_w, int32_t out_h, int32_t* maps_dev);
+/* replaces dls.py:100-124 (process_yolo_segmentation after the model call).  masks_dev: K instance masks (K, mh, mw) of
+ * gsx_float_dtype dtype; cls_dev, conf_dev: fp32 [K] on the device (conf is never read on the host); map_dev: int32 (out_h, out_w).
+ * An instance counts iff conf > 0.5 in fp32 (0.5 itself and NaN do not, dls.py:117); a pixel is its iff the resized mask value
+ * is > 0.5 (dls.py:121); later instances overwrite earlier ones whatever their confidence (the loop of dls.py:113-122 - its
+ * comment says otherwise); the class id is truncated to int32 (dls.py:124) and unspecified when it is not finite; the
+ * background, K == 0 and "nothing accepted" are -1 (dls.py:101). */
+int gsx_segmap_from_masks(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, int32_t K, int32_t mh, int32_t mw,
+                          const float* cls_dev, const float* conf_dev, int32_t out_w, int32_t out_h, int32_t* map_dev);
+/* test hook, host only: the units the kernels are built on, out[8] = pixels per workgroup of the arg-max and the instance
+ * kernel, channel (instance) slices per workgroup (its waves), channels (instances) per step of a wave - slice s walks the
+ * steps s, s + slices, .. -, elements per load of those kernels, output pixels per lane and threads per workgroup of the
+ * resize kernel, threads per workgroup of the other two, 0 */
+int gsx_debug_segmap_constants(int32_t* out);
+
+/* ---------------------------------------------------------------------------------------------
  * profiling hooks (HIP events on the ctx stream around each kernel launch)
  * ------------------------------------------------------------------------------------------- */
 int gsx_profile_enable(gsx_ctx* ctx, int on);
@@ -765,7 +810,7 @@ const char* gsx_profile_name(gsx_ctx* ctx, int32_t index);
 int gsx_host_threads(gsx_ctx* ctx);
 /* the pool size a context would choose on its own in this process right now (no context, no GPU needed) */
 int gsx_default_host_threads(void);
-/* name: "vote_fused_labels", "seg_pack", "iou_pack", "iou_pairs", "iou_table", "iou_top_index", ...; returns launches and total milliseconds since reset */
+/* name: "vote_fused_labels", "seg_pack", "iou_pack", "iou_pairs", "iou_table", "iou_top_index", "segmap_argmax", "segmap_masks", "segmap_resize", ...; returns launches and total milliseconds since reset */
 int gsx_profile_get(gsx_ctx* ctx, const char* name, int64_t* launches, double* total_ms);
 
 #ifdef __cplusplus
