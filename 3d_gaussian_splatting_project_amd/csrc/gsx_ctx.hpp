@@ -221,6 +221,10 @@ struct Ctx {
     DevBuf labels8;             // [n] u8: bin = label + 1, what labels_to_host sends over PCIe
     DevBuf bcnt, bcodes;        // > 255 views on one GPU: per-batch u8 count planes [S][bins][n_pad], tie codes u16 [S][n_pad]
     DevBuf cand, codes;         // exchange v3: candidate masks u32[8][sn] of this slab; tie codes u16[n_pad]
+    // the layout gsx_vote_flush_counts / gsx_vote_tie_codes last wrote into cnt / codes: their kernels write the Gaussians (whole
+    // workgroups of them) only, so the pad entries behind them are zero as long as the layout is still this one
+    long long counts_n = -1, counts_npad = -1, counts_sn = -1, codes_n = -1, codes_npad = -1;
+    int counts_bins = -1;
     bool labels_valid = false;
     // early vote (vote.hip: early_vote_stage): the views [0, early_done) are voted on a second stream while the host is
     // still handing over the rest of the run; vote_finalize then only walks the views behind them

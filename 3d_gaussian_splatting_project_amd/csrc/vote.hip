@@ -2071,6 +2071,7 @@ static int ensure_planes(Ctx* c) {
     const size_t esz = c->wide ? 2 : 1;
     const size_t bytes = (size_t)c->bins * (size_t)c->n_pad * esz;
     const bool grew = bytes > c->cnt.cap || bytes > c->fv.cap;
+    c->counts_n = -1;  // cnt is about to hold planes of this layout: the next vote_flush_counts clears its pad entries again
     GSX_HIP(c, c->cnt.ensure(bytes ? bytes : 4));
     GSX_HIP(c, c->fv.ensure(bytes ? bytes : 4));
     if (grew || !(c->planes_valid || c->planes_zero || c->planes_stale)) {
@@ -2943,9 +2944,13 @@ int vote_flush_counts(Ctx* c) {
     int rc = sync_views(c);
     if (rc) return rc;
     const size_t bytes = (size_t)c->bins * (size_t)c->n_pad;
-    if (bytes > c->cnt.cap) {
+    // pad Gaussians stay zero as long as the plane keeps its layout: a context that comes back with another scene, bin count or
+    // slab count (or whose buffer held vote_flush's planes in between) would otherwise show the earlier run's counters there
+    const bool same = c->counts_n == c->n && c->counts_npad == c->n_pad && c->counts_sn == c->sn && c->counts_bins == c->bins;
+    if (bytes > c->cnt.cap || !same) {
         GSX_HIP(c, c->cnt.ensure(bytes));
-        GSX_HIP(c, hipMemsetAsync(c->cnt.p, 0, bytes, c->stream));  // pad Gaussians stay zero for ever
+        GSX_HIP(c, hipMemsetAsync(c->cnt.p, 0, bytes, c->stream));
+        c->counts_n = c->n, c->counts_npad = c->n_pad, c->counts_sn = c->sn, c->counts_bins = c->bins;
     }
     if (c->n > 0) {
         FusedParams p = fused_params(c, 1);
@@ -2979,9 +2984,10 @@ int vote_tie_codes(Ctx* c, const void* cand_all) {
     if (!cand_all) return fail(c, GSX_E_INVALID, "vote_tie_codes: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
     const size_t bytes = sizeof(uint16_t) * (size_t)c->n_pad;
-    if (bytes > c->codes.cap) {
+    if (bytes > c->codes.cap || c->codes_n != c->n || c->codes_npad != c->n_pad) {  // pad entries are zero: see vote_flush_counts
         GSX_HIP(c, c->codes.ensure(bytes));
         GSX_HIP(c, hipMemsetAsync(c->codes.p, 0, bytes, c->stream));
+        c->codes_n = c->n, c->codes_npad = c->n_pad;
     }
     if (c->n > 0) {
         FusedParams p = fused_params(c, 1);
