@@ -688,6 +688,11 @@ int gsx_debug_segmap_constants(int32_t* out) {
     gsx::segmap_constants(out);
     return GSX_OK;
 }
+int gsx_debug_segpack_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_segpack_constants: NULL argument");
+    gsx::segpack_constants(out);
+    return GSX_OK;
+}
 
 int gsx_vote_culled(gsx_ctx* ctx, int64_t* wave_views, int32_t reset) {
     CTX_OR_FAIL(ctx);

@@ -442,6 +442,7 @@ int segmap_from_logits(Ctx* c, const void* logits, int dtype, int n, int C, int 
 int segmap_from_masks(Ctx* c, const void* masks, int dtype, int K, int mh, int mw, const float* cls, const float* conf, int out_w, int out_h,
                       int32_t* map);
 void segmap_constants(int32_t out[8]);
+void segpack_constants(int32_t out[8]);  // vote.hip
 void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, int img_w, int img_h);
 
 }  // namespace gsx

@@ -359,34 +359,63 @@ __device__ __forceinline__ unsigned logical_block(unsigned b, unsigned nwg, int 
 // map) — and validates the label range.  One thread = one 4x4 cell: four 16-byte loads (int32), four u32 stores
 // (the four lanes of a strip write 64 contiguous bytes) and one coarse byte.  Up to kPackBatch maps of one geometry
 // per launch (blockIdx.y): a 1080p map is 8 MB, i.e. ~2 us of HBM time, less than a launch.
+// Every byte of the map's pool stride is written, as seg_expand_kernel and the host packer's zeroed ring do: the threads
+// cover the PADDED cell grid (whole strips and bands of the coarse level, which contain those of the full-resolution
+// level), cells and rows past the map are 0 in both levels, and the first workgroup of a map clears the alignment gaps.
+// The pool is reused from run to run, so a byte left out would carry the previous run's data into what vote_export ships.
 // -------------------------------------------------------------------------------------------------
 static constexpr int kPackBatch = 16;
+static constexpr int kStripCols = 16, kBandRows = 8;    // pixel columns per strip, pixel rows per band (full-resolution level)
+static constexpr int kCStripCells = 16, kCBandRows = 8;  // cells per coarse strip, cell rows per coarse band
 struct PackArgs {
     const void* src[kPackBatch];
     uint8_t* dst[kPackBatch];
     int view[kPackBatch];  // index reported through `err` when the map holds a label outside [-1, bins-2]
     int w, h, strip_bytes, cstrip_bytes, cw, ch, bins;
-    unsigned coarse_off;
+    int pw, ph;            // cells per row / column of the full-resolution level including its padding (row-major: cw, ch)
+    int gw, gh;            // the cell grid the threads cover: the coarse level including its padding (no coarse level: pw, ph)
+    unsigned gap_lo, coarse_off, map_bytes, stride;  // [gap_lo, coarse_off) and [map_bytes, stride) belong to no cell: zeroed
     int* err;              // atomicMin of the offending view indices (INT_MAX = none)
 };
 
+static void pack_geometry(PackArgs& a, const MapLayout& L, int bins, int* err) {
+    a.w = L.w, a.h = L.h, a.strip_bytes = L.strip_bytes, a.cstrip_bytes = L.cstrip_bytes, a.cw = L.cw, a.ch = L.ch;
+    a.bins = bins;
+    a.pw = L.strip_bytes ? (L.w + kStripCols - 1) / kStripCols * (kStripCols / 4) : L.cw;
+    a.ph = L.strip_bytes ? (L.h + kBandRows - 1) / kBandRows * (kBandRows / 4) : L.ch;
+    a.gw = L.cstrip_bytes ? (L.cw + kCStripCells - 1) / kCStripCells * kCStripCells : a.pw;
+    a.gh = L.cstrip_bytes ? (L.ch + kCBandRows - 1) / kCBandRows * kCBandRows : a.ph;
+    a.gap_lo = (unsigned)(L.strip_bytes ? L.fine_bytes : (size_t)L.w * (size_t)L.h);  // row-major: the four tail bytes too
+    a.coarse_off = (unsigned)L.coarse_off;  // no coarse level: the end of the stride
+    a.map_bytes = (unsigned)L.map_bytes;
+    a.stride = (unsigned)((L.map_bytes + 255) / 256 * 256);
+    a.err = err;
+}
+
 template <typename T, int ADD, bool VEC>
 __global__ __launch_bounds__(kBlock) void seg_pack_fused_kernel(PackArgs a) {
-    const long long q = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const int cy = (int)(q / a.cw), cx = (int)(q % a.cw);
-    if (cy >= a.ch) return;
     const int job = blockIdx.y;
     const T* __restrict__ in = static_cast<const T*>(a.src[job]);
     uint8_t* __restrict__ out = a.dst[job];
+    if (blockIdx.x == 0) {  // the two alignment gaps, each shorter than 256 bytes
+        for (unsigned j = a.gap_lo + threadIdx.x; j < a.coarse_off; j += kBlock) out[j] = 0;
+        for (unsigned j = a.map_bytes + threadIdx.x; j < a.stride; j += kBlock) out[j] = 0;
+    }
+    const long long q = (long long)blockIdx.x * kBlock + threadIdx.x;
+    const int cy = (int)(q / a.gw), cx = (int)(q % a.gw);
+    if (cy >= a.gh) return;
     const int x0 = cx * 4, y0 = cy * 4;
     const unsigned bins = (unsigned)a.bins;
+    const bool fine_pad = a.strip_bytes && cx < a.pw && cy < a.ph;  // a cell of a strip, in the map or in its padding
     unsigned bad = 0;
     uint32_t rows[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int y = y0 + r;
         uint32_t packed = 0;
-        if (y < a.h) {
+        if (y >= a.h || cx >= a.cw) {  // rows below the map, cells right of it: bin 0 in the strips' padding
+            if (fine_pad) *reinterpret_cast<uint32_t*>(out + (long long)(x0 >> 4) * a.strip_bytes + ((long long)y << 4) + (x0 & 15)) = 0u;
+        } else {
             const T* row = in + (long long)y * a.w + x0;
             T v[4];
             bool have[4];
@@ -422,7 +451,9 @@ __global__ __launch_bounds__(kBlock) void seg_pack_fused_kernel(PackArgs a) {
     if (a.cstrip_bytes) {
         const uint32_t same = (rows[0] & 0xffu) * 0x01010101u;
         const bool uniform = x0 + 4 <= a.w && y0 + 4 <= a.h && rows[0] == same && rows[1] == same && rows[2] == same && rows[3] == same;
-        out[a.coarse_off + (long long)(cx >> 4) * a.cstrip_bytes + (cx & 15) + ((long long)cy << 4)] = uniform ? (uint8_t)(rows[0] & 0xffu) : (uint8_t)255;
+        const bool cell = cx < a.cw && cy < a.ch;  // else the coarse strips' padding: 0
+        out[a.coarse_off + (long long)(cx >> 4) * a.cstrip_bytes + (cx & 15) + ((long long)cy << 4)] =
+            uniform ? (uint8_t)(rows[0] & 0xffu) : cell ? (uint8_t)255 : (uint8_t)0;
     }
     if (bad) atomicMin(a.err, a.view[job]);
 }
@@ -1517,7 +1548,7 @@ static void push_view(Ctx* c, const gsx_camera* cam, const MapLayout& L, size_t 
 }
 
 // near: a buffer the pool is about to read (the first map of a run): the workers are placed on its NUMA node
-static void launch_pack(Ctx* c, const PackArgs& a, int jobs, int seg_dtype, bool vec, long long cells);
+static void launch_pack(Ctx* c, const PackArgs& a, int jobs, int seg_dtype, bool vec);
 
 static Workers* host_workers(Ctx* c, const void* near = nullptr) {
     if (!c->workers) {
@@ -1679,11 +1710,8 @@ static int vote_view_host(Ctx* c, const gsx_camera* cam, const void* seg, int se
         a.src[0] = land.p;
         a.dst[0] = c->segpool.as<uint8_t>() + off;
         a.view[0] = c->first_view + (int)c->views.size();
-        a.w = L.w, a.h = L.h, a.strip_bytes = L.strip_bytes, a.cstrip_bytes = L.cstrip_bytes, a.cw = L.cw, a.ch = L.ch;
-        a.bins = c->bins;
-        a.coarse_off = (unsigned)L.coarse_off;
-        a.err = c->errflag.as<int>();
-        launch_pack(c, a, 1, seg_dtype, seg_w % 4 == 0, (long long)L.cw * L.ch);
+        pack_geometry(a, L, c->bins, c->errflag.as<int>());
+        launch_pack(c, a, 1, seg_dtype, seg_w % 4 == 0);
         GSX_HIP(c, hipGetLastError());
         GSX_HIP(c, hipEventRecord(slot.ev, c->stream));  // after the kernel: it is the last reader of this slot's landing zone
         slot.busy = true;
@@ -1699,14 +1727,24 @@ int vote_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int
     return rc ? rc : early_vote_stage(c);  // enough of the run staged: its first views are voted while the rest is handed over
 }
 
-static void launch_pack(Ctx* c, const PackArgs& a, int jobs, int seg_dtype, bool vec, long long cells) {
+static void launch_pack(Ctx* c, const PackArgs& a, int jobs, int seg_dtype, bool vec) {
     using K = void (*)(PackArgs);
     static const K table[4][2] = {{seg_pack_fused_kernel<int32_t, 1, false>, seg_pack_fused_kernel<int32_t, 1, true>},
                                   {seg_pack_fused_kernel<int64_t, 1, false>, seg_pack_fused_kernel<int64_t, 1, true>},
                                   {seg_pack_fused_kernel<uint8_t, 0, false>, seg_pack_fused_kernel<uint8_t, 0, true>},
                                   {seg_pack_fused_kernel<uint8_t, 1, false>, seg_pack_fused_kernel<uint8_t, 1, true>}};
     ProfScope ps(c, "seg_pack");
-    hipLaunchKernelGGL(table[seg_dtype][vec ? 1 : 0], dim3(grid_for(cells), jobs), dim3(kBlock), 0, c->stream, a);
+    hipLaunchKernelGGL(table[seg_dtype][vec ? 1 : 0], dim3(grid_for((long long)a.gw * a.gh), jobs), dim3(kBlock), 0, c->stream, a);
+}
+
+void segpack_constants(int32_t out[8]) {
+    out[0] = kBlock;
+    out[1] = kPackBatch;
+    out[2] = kStripCols;
+    out[3] = kBandRows;
+    out[4] = kCStripCells;
+    out[5] = kCBandRows;
+    out[6] = out[7] = 0;
 }
 
 // Device maps (all of one geometry and dtype): kPackBatch maps per launch of the fused pack kernel.  Nothing is
@@ -1720,7 +1758,6 @@ int vote_views_device(Ctx* c, int n, const gsx_camera* cams, const void* const* 
     for (int i = 0; i < n; ++i)
         if (!segs[i]) return fail(c, GSX_E_INVALID, "vote_views_device: map %d is NULL", i);
     const size_t esz = seg_dtype == GSX_SEG_I32 ? 4 : seg_dtype == GSX_SEG_I64 ? 8 : 1;
-    const long long cells = (long long)L.cw * L.ch;
     for (int i0 = 0; i0 < n; i0 += kPackBatch) {
         const int m = std::min(kPackBatch, n - i0);
         PackArgs a{};
@@ -1734,11 +1771,8 @@ int vote_views_device(Ctx* c, int n, const gsx_camera* cams, const void* const* 
             vec = vec && reinterpret_cast<uintptr_t>(segs[i0 + k]) % (4 * esz) == 0;
             push_view(c, cams + i0 + k, L, off, img_w, img_h);
         }
-        a.w = L.w, a.h = L.h, a.strip_bytes = L.strip_bytes, a.cstrip_bytes = L.cstrip_bytes, a.cw = L.cw, a.ch = L.ch;
-        a.bins = c->bins;
-        a.coarse_off = (unsigned)L.coarse_off;
-        a.err = c->errflag.as<int>();
-        launch_pack(c, a, m, seg_dtype, vec, cells);
+        pack_geometry(a, L, c->bins, c->errflag.as<int>());
+        launch_pack(c, a, m, seg_dtype, vec);
         GSX_HIP(c, hipGetLastError());
     }
     return GSX_OK;

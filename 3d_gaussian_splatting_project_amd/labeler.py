@@ -1032,6 +1032,14 @@ def segmap_constants():
             "resize_block": int(out[5]), "block": int(out[6])}
 
 
+def segpack_constants():
+    """Test hook, host only: the units the device map pack is built on (gsx_debug_segpack_constants)."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_segpack_constants(out.ctypes.data))
+    names = ("block", "batch", "strip_cols", "band_rows", "cstrip_cells", "cband_rows")
+    return dict(zip(names, (int(v) for v in out)))
+
+
 def iou_constants():
     """Test hook, host only: the units the IoU kernels are built on (gsx_debug_iou_constants)."""
     out = np.zeros(8, np.int32)

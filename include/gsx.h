@@ -798,6 +798,10 @@ int gsx_segmap_from_masks(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, in
  * steps s, s + slices, .. -, elements per load of those kernels, output pixels per lane and threads per workgroup of the
  * resize kernel, threads per workgroup of the other two, 0 */
 int gsx_debug_segmap_constants(int32_t* out);
+/* test hook, host only: the units the device map pack (gsx_vote_view_device, gsx_vote_views_device, "host_pack" = 0) is built on,
+ * out[8] = cells (threads) per workgroup, maps per launch, pixel columns per strip and pixel rows per band of the full-resolution
+ * level, cells per strip and cell rows per band of the coarse level, 0, 0 */
+int gsx_debug_segpack_constants(int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
  * profiling hooks (HIP events on the ctx stream around each kernel launch)
