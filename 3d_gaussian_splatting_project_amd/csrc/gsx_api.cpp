@@ -224,8 +224,8 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
     else if (k == "host_threads") {
         if (value < 0 || value > 256) return gsx::fail(c, GSX_E_INVALID, "set_option: host_threads must be in [0,256]");
         if ((int)value != c->opt_host_threads) {
-            delete c->workers;  // re-created with the new size at the next host-side hand-over
-            c->workers = nullptr;
+            delete c->ho.workers;  // re-created with the new size at the next host-side hand-over
+            c->ho.workers = nullptr;
         }
         c->opt_host_threads = (int)value;
     }
@@ -491,7 +491,7 @@ int64_t gsx_vote_pool_bytes(const gsx_ctx* ctx) {
 }
 int64_t gsx_vote_link_bytes(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return (c && c->vote_begun) ? (int64_t)c->compact_bytes : 0;
+    return (c && c->vote_begun) ? (int64_t)c->ho.compact_bytes : 0;
 }
 int64_t gsx_vote_early_views(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);

@@ -120,6 +120,47 @@ struct ProfEvent {
     hipEvent_t start, stop;
 };
 
+// ---- small expressions with one spelling -----------------------------------------------------------------------------
+// maps, records and staging areas start on 256-byte boundaries
+constexpr size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+// bytes per element of a map handed over as GSX_SEG_*
+constexpr size_t seg_elem_size(int seg_dtype) { return seg_dtype == GSX_SEG_I32 ? 4 : seg_dtype == GSX_SEG_I64 ? 8 : 1; }
+
+// State of the segmentation-map hand-over (handover.hip): worker pool, the pinned rings of the three transfer forms and the
+// packed maps that wait for their DMA.  Plain data; only handover.hip (and the option "host_threads") writes it.
+struct HandOver {
+    Workers* workers = nullptr;
+    DevBuf dstage[kPinSlots];  // host_pack = 0: device-side landing zone of the raw map of each ring slot
+    PinSlot ring[kPinSlots];   // host_pack = 0: raw maps
+    int ring_next = 0;
+    // host_pack = 1: ONE pinned buffer of kDmaGroups * kDmaBatch slots, a slot = the pool stride of the map geometry, so that
+    // consecutive packed maps are consecutive both here and in the pool and a whole group goes up in one DMA
+    void* hring = nullptr;
+    size_t hring_bytes = 0, hring_slot = 0;
+    hipEvent_t hring_ev[kDmaGroups] = {nullptr, nullptr, nullptr};
+    bool hring_busy[kDmaGroups] = {false, false, false};
+    int hring_next = 0;
+    int pend_first = 0, pend_count = 0;  // packed maps of the filling group whose DMA has not been queued yet
+    size_t pend_dst = 0;
+    // compact transfer form: the records of a group lie back to back in its part of the ring
+    bool hring_compact = false;
+    size_t grp_used = 0;                 // bytes of the filling group in use
+    size_t pend_lo = 0;                  // where the pending records start in the group
+    size_t pend_rec[kCompactBatch] = {}; // their offsets in the group
+    size_t pend_map[kCompactBatch] = {}; // their maps' offsets in the pool
+    int cgrp = 0, grp_recs = 0;          // the filling group and the records it holds
+    int pend_group = 0;                  // group of the pending records
+    MapLayout pend_L;                    // their geometry (one expansion launch = one geometry)
+    DevBuf cstage;                       // device staging of one group of records
+    void* h_scratch = nullptr;           // host: the narrowed strips of the map being packed (ordinary memory)
+    size_t h_scratch_cap = 0;
+    long long compact_bytes = 0;         // statistics: bytes of host maps sent over PCIe since vote_begin (compact records or pool form)
+    void begin_run() {  // vote_begin: packed maps of an abandoned run that never went up are forgotten with it
+        pend_count = 0;
+        compact_bytes = 0;
+    }
+};
+
 struct Ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -167,42 +208,17 @@ struct Ctx {
     DevBuf segpool;
     size_t seg_used = 0;
     DevBuf errflag;  // int: smallest view index whose device-side map held a label out of range (kNoBadView: none)
-    // host hand-over (vote.hip): worker pool, pinned ring for the maps, pinned landing zone for the labels
-    Workers* workers = nullptr;
+    // host hand-over: the maps' way in (handover.hip), then the pinned landing zone for the labels (vote.hip: labels_to_host)
+    HandOver ho;
     int opt_host_threads = 0;  // 0: default_host_threads()
     int opt_host_compact = 1;  // host maps cross PCIe in the compact form (coarse level + the mixed cells' blocks), expanded on the GPU
 #ifdef GSX_EXPERIMENTS  // `make experiments` only (libgsx_experiments.so, used by tools/): timing-only switches, results invalid
-    int opt_ablate = 0;        // 1 = host maps are packed but not copied, 2 = copied but not packed; << 4: last-stage ablations (vote.hip)
+    int opt_ablate = 0;        // 1 = host maps are packed but not copied, 2 = copied but not packed (handover.hip); << 4: last-stage ablations (vote.hip)
 #else
     static constexpr int opt_ablate = 0;  // the product library has no such option: every branch on it folds away
 #endif
     int opt_labels_u8 = 1;     // 1: the labels cross PCIe as one byte each (bin = label + 1) and are widened by the workers; 0: as int32
     int opt_host_pack = 1;     // 1: host maps are narrowed to u8 by the workers (2.2 MB/map over PCIe); 0: raw copy + GPU pack kernel (8.3 MB/map)
-    DevBuf dstage[kPinSlots];  // host_pack = 0: device-side landing zone of the raw map of each ring slot
-    PinSlot ring[kPinSlots];   // host_pack = 0: raw maps
-    int ring_next = 0;
-    // host_pack = 1: ONE pinned buffer of kDmaGroups * kDmaBatch slots, a slot = the pool stride of the map geometry, so that
-    // consecutive packed maps are consecutive both here and in the pool and a whole group goes up in one DMA
-    void* hring = nullptr;
-    size_t hring_bytes = 0, hring_slot = 0;
-    hipEvent_t hring_ev[kDmaGroups] = {nullptr, nullptr, nullptr};
-    bool hring_busy[kDmaGroups] = {false, false, false};
-    int hring_next = 0;
-    int pend_first = 0, pend_count = 0;  // packed maps of the filling group whose DMA has not been queued yet
-    size_t pend_dst = 0;
-    // compact transfer form: the records of a group lie back to back in its part of the ring
-    bool hring_compact = false;
-    size_t grp_used = 0;                 // bytes of the filling group in use
-    size_t pend_lo = 0;                  // where the pending records start in the group
-    size_t pend_rec[kCompactBatch] = {}; // their offsets in the group
-    size_t pend_map[kCompactBatch] = {}; // their maps' offsets in the pool
-    int cgrp = 0, grp_recs = 0;          // the filling group and the records it holds
-    int pend_group = 0;                  // group of the pending records
-    MapLayout pend_L;                    // their geometry (one expansion launch = one geometry)
-    DevBuf cstage;                       // device staging of one group of records
-    void* h_scratch = nullptr;           // host: the narrowed strips of the map being packed (ordinary memory)
-    size_t h_scratch_cap = 0;
-    long long compact_bytes = 0;         // statistics: bytes of host maps sent over PCIe since vote_begin (compact records or pool form)
     void* h_labels = nullptr;  // pinned: n u8 bins (label + 1) + one int (the error flag) land here before the caller's array
     size_t h_labels_cap = 0;
     hipEvent_t h_ev[kLabelChunks] = {nullptr, nullptr, nullptr, nullptr};
@@ -345,6 +361,11 @@ struct ProfScope {
 // vote.hip
 int vote_begin(Ctx* c, int n_classes, int first_view, int total_views);
 int vote_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h);
+int early_pool_moves(Ctx* c);    // the seg pool is about to be re-allocated: wait for the early vote that reads it, drop its result
+void vote_release_host(Ctx* c);  // pinned buffers, events, worker pool, second stream (gsx_destroy)
+int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size);
+// handover.hip: segmentation maps into the seg pool, descriptors between ranks
+int vote_view_host(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h);
 int vote_views_device(Ctx* c, int n, const gsx_camera* cams, const void* const* segs, int seg_dtype, int seg_w, int seg_h,
                       int img_w, int img_h);
 int vote_export(Ctx* c, int64_t reserve_bytes, void* blobs_out, void** pool_dev, int64_t* pool_bytes);
@@ -355,14 +376,16 @@ int vote_import_uniform(Ctx* c, int n_parts, const int32_t* part_views, const in
 int vote_import_undo(Ctx* c);
 int vote_map_stride(Ctx* c, int seg_w, int seg_h, int64_t* stride);
 int vote_views_match_uniform(Ctx* c, int n, const gsx_camera* cams, int seg_w, int seg_h, int img_w, int img_h, int32_t* match);
-int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size);
+Workers* host_workers(Ctx* c, const void* near = nullptr);  // the context's pool, created at first use (nullptr: pack on the caller)
 int host_threads(Ctx* c);
 int vote_flush_pending(Ctx* c);  // queue the DMA of packed host maps that are still waiting for their group to fill
-void vote_release_host(Ctx* c);  // pinned buffers, events, worker pool (gsx_destroy)
+void handover_release(Ctx* c);   // rings, their events, staging, worker pool
+void segpack_constants(int32_t out[8]);
 int debug_host_pack(const void* seg, int seg_dtype, int w, int h, int n_classes, int tiled, int coarse, int threads,
                     uint8_t* out, int64_t out_cap, int64_t* bytes, int64_t* coarse_off, int32_t* bad);
 int debug_host_pack_compact(const void* seg, int seg_dtype, int w, int h, int n_classes, int threads, uint8_t* out, int64_t out_cap,
                             int64_t* bytes, int64_t* table_bytes, int64_t* stream_off, int32_t* bad);
+// vote.hip
 int vote_rewind(Ctx* c);
 int vote_finalize(Ctx* c, int32_t* labels_out);
 int vote_flush(Ctx* c);
@@ -442,7 +465,7 @@ int segmap_from_logits(Ctx* c, const void* logits, int dtype, int n, int C, int 
 int segmap_from_masks(Ctx* c, const void* masks, int dtype, int K, int mh, int mw, const float* cls, const float* conf, int out_w, int out_h,
                       int32_t* map);
 void segmap_constants(int32_t out[8]);
-void segpack_constants(int32_t out[8]);  // vote.hip
+// vote.hip
 void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, int img_w, int img_h);
 
 }  // namespace gsx

@@ -1,17 +1,16 @@
 // vote.hip — majority-vote labeler kernels for gfx950 (MI355X) and their host drivers.
 //
 // Replaces the double loop of assign_labels (deep_learning_segmentation.py:255-295) and its arg-max
-// (:297-308); project() restates project_gaussian (:43-82) operation for operation in fp64.
+// (:297-308); project() (vote_device.hpp) restates project_gaussian (:43-82) operation for operation in fp64.
 // This translation unit MUST be compiled with -ffp-contract=off: every fma below is explicit and
 // every other product/sum must round separately, exactly as the reference's Python floats do.
+// How the segmentation maps get into the seg pool: handover.hip.
 //
 // Data layout in HBM
 //   positions      SoA  x[n], y[n], z[n] f32                      (coalesced 4 B/lane loads)
 //   views          ViewDesc[V], 256 B each (176 hot), wave-uniform -> four scalar loads, operands live in SGPRs
-//   seg pool       u8 maps, value = label+1 (bin index), one after another, each stored as strips of 16 pixel
-//                  columns (rows of a strip back to back, 16 B each; 8 rows = one 128-B L2 line): the pixels
-//                  a wave gathers are a compact patch, so they fall into few lines; 1 B gathers
-//   planes         cnt[slab][bins][sn], fv[slab][bins][sn]  u8 or u16 (16 bit only for the all-reduce
+//   seg pool       u8 maps, value = label+1 (bin index), in strips of 16 pixel columns (handover.hip); 1 B gathers
+//   planes        cnt[slab][bins][sn], fv[slab][bins][sn]  u8 or u16 (16 bit only for the all-reduce
 //                  protocol with > 255 views in total): bin-major so that a wave's 64 Gaussians touch 64
 //                  consecutive elements of a row; slab = one rank's share in the all-to-all protocols
 //                  (a single slab is plain [bins][n_pad])
@@ -31,291 +30,16 @@
 //   order) is earliest among the max-count labels is the last one to do so.  See DESIGN.md §3.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
 #include <cstring>
-#include <new>
-
 #include <type_traits>
 
 #include "gsx_ctx.hpp"
+#include "vote_device.hpp"
 
 namespace gsx {
-
-static constexpr int kBlock = 256;
-static constexpr int kMaxBatch = 255;  // views per fused launch: LDS counters are 8 bit
-int early_join(Ctx* c);
-
-// -------------------------------------------------------------------------------------------------
-// device: project_gaussian + seg-map addressing
-// -------------------------------------------------------------------------------------------------
-// One view's hot fields, held in SGPRs.  load_view() pins all of them behind ONE batch of scalar loads: left
-// to itself hipcc sinks every s_load next to its first use, behind the early-out branches, and each view
-// then pays ~5 exposed scalar-cache round trips (the kernel was waiting, not computing).
-struct ViewRegs {
-    double R[9], t[3], fx, fy, half_w, half_h, width, height;
-    long long seg_off;
-    int seg_w, unit_scale, seg_row_bytes, cam_w, cam_h;
-    int coarse_row_bytes;
-    unsigned coarse_delta;
-    float hw32, hh32;
-};
-
-typedef int v16i __attribute__((ext_vector_type(16)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double chunk_f64(const v16i& v, int k) {
-    v2i t;
-    t.x = v[2 * k];
-    t.y = v[2 * k + 1];
-    return __builtin_bit_cast(double, t);
-}
-
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-// The hot 184 bytes of a ViewDesc as four scalar loads (x16, x16, x8, x8), pinned as whole register tuples: the
-// fields below are sub-registers of those tuples, no scalar move is spent on them.  (Pinning the 24 fields one
-// by one cost 15 s_mov per view; the scalar unit is shared by the four SIMDs of a CU and every wave issues at
-// most one instruction per turn, so scalar bookkeeping was costing as much as the fp64 arithmetic.)
-__device__ __forceinline__ void unpack_core(ViewRegs& r, const v16i& a, const v16i& b) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r.R[k] = chunk_f64(a, k);
-    r.R[8] = chunk_f64(b, 0);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r.t[k] = chunk_f64(b, 1 + k);
-    r.fx = chunk_f64(b, 4);
-    r.fy = chunk_f64(b, 5);
-    r.seg_off = __builtin_bit_cast(long long, chunk_f64(b, 6));
-    r.seg_row_bytes = b[14];
-    r.unit_scale = b[15];
-}
-
-__device__ __forceinline__ ViewRegs load_view(const ViewDesc* __restrict__ vp) {
-    static_assert(offsetof(ViewDesc, R) == 0 && offsetof(ViewDesc, t) == 72 && offsetof(ViewDesc, fx) == 96 &&
-                      offsetof(ViewDesc, seg_off) == 112 && offsetof(ViewDesc, seg_row_bytes) == 120 &&
-                      offsetof(ViewDesc, unit_scale) == 124 && offsetof(ViewDesc, half_w) == 128 &&
-                      offsetof(ViewDesc, width) == 144 && offsetof(ViewDesc, seg_w) == 160 &&
-                      offsetof(ViewDesc, cam_w) == 168 && offsetof(ViewDesc, coarse_row_bytes) == 176 &&
-                      offsetof(ViewDesc, coarse_delta) == 180 && offsetof(ViewDesc, hw32) == 184 && sizeof(ViewDesc) % 64 == 0,
-                  "load_view reads the hot part of ViewDesc as 64 + 64 + 32 + 32 bytes");
-    const char* q = reinterpret_cast<const char*>(vp);
-    v16i a = *reinterpret_cast<const v16i*>(q);
-    v16i b = *reinterpret_cast<const v16i*>(q + 64);
-    v8i c = *reinterpret_cast<const v8i*>(q + 128);
-    v8i d = *reinterpret_cast<const v8i*>(q + 160);
-    asm volatile("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d));
-    ViewRegs r;
-    unpack_core(r, a, b);
-    v2i t;
-    t.x = c[0], t.y = c[1];
-    r.half_w = __builtin_bit_cast(double, t);
-    t.x = c[2], t.y = c[3];
-    r.half_h = __builtin_bit_cast(double, t);
-    t.x = c[4], t.y = c[5];
-    r.width = __builtin_bit_cast(double, t);
-    t.x = c[6], t.y = c[7];
-    r.height = __builtin_bit_cast(double, t);
-    r.seg_w = d[0];
-    r.cam_w = d[2];
-    r.cam_h = d[3];
-    r.coarse_row_bytes = d[4];
-    r.coarse_delta = (unsigned)d[5];
-    const int hw_bits = d[6], hh_bits = d[7];  // (a bit_cast straight from a vector element reads element 0)
-    r.hw32 = __builtin_bit_cast(float, hw_bits);
-    r.hh32 = __builtin_bit_cast(float, hh_bits);
-    return r;
-}
-
-
-// OpenBLAS dgemv association of `R @ v` for a C-contiguous 3x3 (oracle/vote_oracle.c, header)
-__device__ __forceinline__ double row_dot(const double* Rr, double v0, double v1, double v2) {
-    return __builtin_fma(Rr[2], v2, __builtin_fma(Rr[0], v0, Rr[1] * v1));
-}
-
-// project_gaussian (dls.py:43-82).  Returns false where the reference returns None (:72-73, :80-82).
-//
-// DIV == kDivExact: the two IEEE-754 divisions of dls.py:76-77, operation for operation.
-// (A certified form, the same results from ONE reciprocal, option "fast_div", was measured and removed: DESIGN.md.)
-// DIV == kDivFlat: the exact divisions again, but as ONE straight-line block: all three rows and both quotients are
-//   evaluated unconditionally and the reference's tests (:72, :80) become a single predicate at the end.  The
-//   branchy form serialises ~45 dependent fp64 instructions behind three divergent branches; here the three rows
-//   and the two quotients are independent chains the scheduler interleaves.  Same operations, same operands,
-//   same results; lanes the reference rejects early merely compute values nobody reads.
-// DIV == kDivFlatSimple: kDivFlat for a batch whose views ALL have unit scale and tiled maps (the host checks): the
-//   two wave-uniform tests per view disappear from the instruction stream.
-// DIV == kDivFlatCoarse: kDivFlatSimple for a batch whose maps all carry a coarse level (see gather_chunk).
-// DIV == kDivFiltCoarse: kDivFlatCoarse with the fp32 filter of project_filtered() in front of the two divisions.
-enum { kDivExact = 0, kDivFlat = 1, kDivFlatSimple = 2, kDivFlatCoarse = 3, kDivFiltCoarse = 4 };
-
-// Two IEEE-754 divisions by the same denominator, bit-identical to `ax / b` and `ay / b`.
-// hipcc expands an fp64 division into div_scale(den), rcp, two Newton steps, div_scale(num), mul, fma, div_fmas,
-// div_fixup.  Everything up to the refined reciprocal depends only on the SCALED denominator, which is the same
-// for both quotients unless v_div_scale rescales for an extreme exponent gap; so the reciprocal chain (v_rcp_f64,
-// which costs as much as 3.4 fp64 FMAs on gfx950, plus 4 FMAs) is evaluated once.  Lanes whose two scaled
-// denominators differ redo the second quotient with the plain division (extreme-exponent tests only).
-__device__ __forceinline__ void div2_shared(double ax, double ay, double b, double& qx, double& qy) {
-    bool unused, vx, vy;
-    const double sdx = __builtin_amdgcn_div_scale(ax, b, false, &unused);
-    const double sdy = __builtin_amdgcn_div_scale(ay, b, false, &unused);
-    const double nsd = -sdx;
-    double r = __builtin_amdgcn_rcp(sdx);
-    r = __builtin_fma(r, __builtin_fma(nsd, r, 1.0), r);
-    r = __builtin_fma(r, __builtin_fma(nsd, r, 1.0), r);
-    const double snx = __builtin_amdgcn_div_scale(ax, b, true, &vx);
-    const double mx = snx * r;
-    qx = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(__builtin_fma(nsd, mx, snx), r, mx, vx), b, ax);
-    const double sny = __builtin_amdgcn_div_scale(ay, b, true, &vy);
-    const double my = sny * r;
-    qy = __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(__builtin_fma(nsd, my, sny), r, my, vy), b, ay);
-    // wave-uniform test on purpose: behind a per-lane `if` the compiler turns the fallback into a select and
-    // evaluates the second reciprocal chain unconditionally
-    const bool differ = __double_as_longlong(sdx) != __double_as_longlong(sdy);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(differ) != 0, 0)) {
-        const double slow = ay / b;
-        qy = differ ? slow : qy;
-    }
-}
-
-template <int DIV>
-__device__ __forceinline__ bool project(const ViewRegs& vd, double X, double Y, double Z, int& xi, int& yi) {
-    const double pc2 = row_dot(vd.R + 6, X, Y, Z) + vd.t[2];
-    if (DIV == kDivFlat || DIV == kDivFlatSimple || DIV == kDivFlatCoarse) {
-        // one wave-uniform early-out keeps what matters of the branchy form: a wave whose 64 Gaussians are all
-        // behind the camera (Morton order makes that the common way to be culled) skips the view
-        if (__builtin_amdgcn_ballot_w64(pc2 > 0.0) == 0) return false;
-        const double q0 = row_dot(vd.R + 0, X, Y, Z) + vd.t[0];
-        const double q1 = row_dot(vd.R + 3, X, Y, Z) + vd.t[1];
-        double qx, qy;
-        div2_shared(vd.fx * q0, vd.fy * q1, pc2, qx, qy);
-        const double fpx = qx + vd.half_w;  // dls.py:76
-        const double fpy = qy + vd.half_h;  // dls.py:77
-        const bool vis = (pc2 > 0.0) & (0.0 <= fpx) & (fpx < vd.width) & (0.0 <= fpy) & (fpy < vd.height);  // :72, :80
-        if (!vis) return false;
-        xi = (int)fpx;  // :81
-        yi = (int)fpy;
-        return true;
-    }
-    if (!(pc2 > 0.0)) return false;  // `pc2 <= 0` -> None; a NaN depth fails the bounds test below anyway
-    const double pc0 = row_dot(vd.R + 0, X, Y, Z) + vd.t[0];
-    const double pc1 = row_dot(vd.R + 3, X, Y, Z) + vd.t[1];
-    const double ax = vd.fx * pc0, ay = vd.fy * pc1;
-    const double px = ax / pc2 + vd.half_w;  // dls.py:76
-    const double py = ay / pc2 + vd.half_h;  // dls.py:77
-    if (!((0.0 <= px) && (px < vd.width) && (0.0 <= py) && (py < vd.height))) return false;  // :80
-    xi = (int)px;  // int() truncation, :81
-    yi = (int)py;
-    return true;
-}
-
-// ---- filtered exact projection ------------------------------------------------------------------------------------------
-// project<kDivFlatSimple>() spends two thirds of its time on the two IEEE-754 divisions of dls.py:76-77 (v_div_scale, v_rcp_f64,
-// two Newton steps, v_div_fmas, v_div_fixup: ~43 ns of ~95 per wave and view, tools/valu_rate.hip) to obtain px, py to the last
-// bit - of which only floor() and the comparison with the frame are ever used.  Here the camera-space point (pc0, pc1, pc2) and
-// the products ax = fx * pc0, ay = fy * pc1 are the reference's own fp64 values as before, but the perspective division runs
-// in fp32: one v_rcp_f32 and two v_fma_f32 give px^, py^ with a PROVEN error bound E, and a lane whose px^ and py^ are both
-// farther than E from every integer has floor(px^) == floor(px), floor(py^) == floor(py) for certain - which decides the
-// visibility test (an integer frame: 0 <= px < W  <=>  0 <= floor(px) <= W - 1) and the pixel.  If any lane of the wave is
-// closer than that to an integer (or its depth lies outside [2^-40, 2^40)), the whole wave takes the exact divisions for
-// this view behind a wave-uniform branch: ~4 E of the lanes, i.e. one (wave, view) pair in ten at 1080p.  Bit-exact by
-// construction; the bound:
-//   u = 2^-24.  a^ = fl32(a) = a (1 + e1), z^ = fl32(pc2) = pc2 (1 + e2), |e1|, |e2| <= u (round to nearest; pc2 in
-//   [2^-40, 2^40) keeps z^ and r^ normal, and the 2^-126 absolute error of an a below the normal range is < 2^-86 after the
-//   multiplication by r^ <= 2^40); r^ = v_rcp_f32(z^) = (1 + e3) / z^ with |e3| <= 3 u (1 ulp by the ISA manual; the
-//   exhaustive check gsx_debug_filter_check() measures it on the device, and the GPU suite asserts <= 3 u);
-//   px^ = fl32(a^ r^ + hw) (fused, hw = W / 2 exact in fp32) = (a^ r^ + hw)(1 + e4), |e4| <= u.  With P = a / pc2 + hw:
-//   |px^ - P| <= |P - hw| ((1 + u)(1 + 3u) / (1 - u) - 1) + u |px^| / (1 - u) <= 5.01 u |P - hw| + 1.01 u |px^|.
-//   The reference's px = fl64(fl64(a / pc2) + hw) differs from P by <= 2^-52 (|P| + hw).
-//   Inside or within one pixel of the frame, |P - hw| <= W / 2 + 1 and |px^| <= W + 1:  |px^ - px| < 3.6 W u.
-//   E = 4 D u (kFilterK; D = the larger side of the largest frame of the batch, at least 64) leaves 10 % - 0.4 D u >= 2^-20 -
-//   for the terms dropped above (a few u) and for the rounding of fract() on (-1, 0) and of `fract - 0.5` (<= 2^-25 each).
-//   Outside that band no bound is needed: a lane is declared invisible only when floor(px^) lies outside [0, W - 1] while
-//   px^ is at least E away from the integers, and then P is on the same side of the frame (for px^ >= W + 1 or px^ <= -1
-//   the relative error 6.02 u cannot move P across the frame edge; between, the bound above applies); infinities saturate
-//   the conversion and fail the range test, NaNs fail the comparison with E and send the wave to the exact path.
-static constexpr double kFilterK = 4.0;
-__device__ __forceinline__ int cvt_floor_i32(float v) {
-    int k;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(k) : "v"(v));  // floor + saturating conversion in one instruction (NaN -> 0)
-    return k;
-}
-
-// filt_h = 0.5 - E.  Returns what project<kDivFlatSimple>() returns, bit for bit.
-__device__ __forceinline__ bool project_filtered(const ViewRegs& vd, float filt_h, double X, double Y, double Z, int& xi, int& yi) {
-    const double pc2 = row_dot(vd.R + 6, X, Y, Z) + vd.t[2];
-    const bool pos = pc2 > 0.0;  // dls.py:72
-    if (__builtin_amdgcn_ballot_w64(pos) == 0) return false;
-    const double q0 = row_dot(vd.R + 0, X, Y, Z) + vd.t[0];
-    const double q1 = row_dot(vd.R + 3, X, Y, Z) + vd.t[1];
-    const double ax = vd.fx * q0, ay = vd.fy * q1;
-    {
-        const float zf = (float)pc2, axf = (float)ax, ayf = (float)ay;
-        const float r = __builtin_amdgcn_rcpf(zf);
-        const float pxf = __builtin_fmaf(axf, r, vd.hw32), pyf = __builtin_fmaf(ayf, r, vd.hh32);
-        const float dx = __builtin_amdgcn_fractf(pxf) - 0.5f, dy = __builtin_amdgcn_fractf(pyf) - 0.5f;
-        // 2^-40 <= pc2 < 2^40, on the high word (a negative, zero, infinite or NaN depth fails)
-        const bool zrange = (unsigned)(__double2hiint(pc2) - 0x3D700000) < (unsigned)(0x42700000 - 0x3D700000);
-        const bool cert = zrange & (__builtin_fabsf(dx) <= filt_h) & (__builtin_fabsf(dy) <= filt_h);  // false for NaN
-        const int kx = cvt_floor_i32(pxf), ky = cvt_floor_i32(pyf);
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(pos & !cert) == 0, 1)) {
-            xi = kx;
-            yi = ky;
-            return cert & ((unsigned)kx < (unsigned)vd.cam_w) & ((unsigned)ky < (unsigned)vd.cam_h);
-        }
-    }
-    // some lane is too close to a pixel boundary: the exact divisions for the whole wave (dls.py:76-81)
-    double qx, qy;
-    div2_shared(ax, ay, pc2, qx, qy);
-    const double fpx = qx + vd.half_w, fpy = qy + vd.half_h;
-    const bool vis = pos & (0.0 <= fpx) & (fpx < vd.width) & (0.0 <= fpy) & (fpy < vd.height);
-    if (!vis) return false;
-    xi = (int)fpx;
-    yi = (int)fpy;
-    return true;
-}
-
-// The vote of one Gaussian in one view: the map byte (bin = label + 1) under its projection, or -1 where the
-// reference skips the pair (dls.py:278-279).  All in-map offsets are 32-bit (maps are <= 65535 x 65535, checked in
-// vote_view), added to the view's wave-uniform base pointer: the gather is `global_load_ubyte v, v_off, s[base]`.
-template <int DIV>
-__device__ __forceinline__ int seg_bin_regs(const ViewRegs& vd, const ViewDesc* __restrict__ vp,
-                                            const uint8_t* __restrict__ pool, double X, double Y, double Z) {
-    int xi, yi;
-    int bin = -1;
-    if (project<DIV>(vd, X, Y, Z, xi, yi)) {
-        constexpr bool kSimple = DIV == kDivFlatSimple;
-        if (!kSimple && !vd.unit_scale) {
-            const double xs = trunc((double)xi * vp->wscale);  // :281
-            const double ys = trunc((double)yi * vp->hscale);  // :282
-            const int seg_h = vp->seg_h;
-            xi = xs > (double)(vd.seg_w - 1) ? vd.seg_w - 1 : (int)xs;  // :285 (xs >= 0 always)
-            yi = ys > (double)(seg_h - 1) ? seg_h - 1 : (int)ys;        // :286
-        }
-        unsigned off;
-        if (kSimple || vd.seg_row_bytes) {
-            // strips of 16 pixel columns, rows of a strip back to back (16 B each): any 8 consecutive rows of a strip
-            // are one 128-B line, so a compact patch of pixels is a compact set of cache lines, and the offset is
-            // (xi>>4) * strip_bytes + (yi<<4) + (xi&15): four integer instructions
-            off = __umul24((unsigned)xi >> 4, (unsigned)vd.seg_row_bytes) + ((unsigned)xi & 15u) + ((unsigned)yi << 4);
-        } else {
-            off = __umul24((unsigned)yi, (unsigned)vd.seg_w) + (unsigned)xi;
-        }
-        // the device copy of the descriptor holds the map's absolute address; say "global" explicitly, a pointer made
-        // from an integer would otherwise be a FLAT one (flat loads also count in lgkmcnt and stall the scalar waits)
-        typedef const __attribute__((address_space(1))) uint8_t* global_u8;
-        bin = ((global_u8)(unsigned long long)vd.seg_off)[off];
-    }
-    return bin;
-}
-
-template <int DIV>
-__device__ __forceinline__ int seg_bin(const ViewDesc* __restrict__ vp, const uint8_t* __restrict__ pool, double X, double Y,
-                                       double Z) {
-    const ViewRegs vd = load_view(vp);
-    return seg_bin_regs<DIV>(vd, vp, pool, X, Y, Z);
-}
 
 template <int DIV>
 __global__ __launch_bounds__(kBlock) void project_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -333,204 +57,6 @@ __global__ __launch_bounds__(kBlock) void project_kernel(const float* __restrict
     const long long o = perm ? (long long)perm[i] : i;  // back to the caller's order
     ox[o] = vis ? xi : -1;
     oy[o] = vis ? yi : -1;
-}
-
-// Workgroups b and b+8 run on the same XCD (round-robin dispatch; a speed heuristic, never needed for
-// correctness).  swizzle == 1: XCD x takes the x-th contiguous eighth of the Morton curve.  swizzle == C >= 2: the
-// curve is cut into chunks of C workgroups and chunk k goes to XCD k % 8: an XCD still works on compact pieces
-// of space (its L2 serves compact patches of every segmentation map), but every XCD sees every part of the scene, so
-// the eight of them finish together even when visibility differs from one region to the next.  Bijective for any grid.
-__device__ __forceinline__ unsigned logical_block(unsigned b, unsigned nwg, int swizzle) {
-    if (!swizzle) return b;
-    if (swizzle == 1) {
-        const unsigned q = nwg >> 3, r = nwg & 7u, xcd = b & 7u;
-        return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
-    const unsigned C = (unsigned)swizzle, super = 8u * C;
-    if (b >= nwg / super * super) return b;  // the ragged tail keeps its order
-    const unsigned j = b >> 3;
-    return (j / C) * super + (b & 7u) * C + j % C;
-}
-
-// -------------------------------------------------------------------------------------------------
-// seg-map packing on the device (gsx_vote_view_device / gsx_vote_views_device): ONE pass over the int32 / int64 /
-// u8 map writes both levels of the library's form — the u8 bins (label + 1) in strips of 16 pixel columns and the
-// 4x4-coarsened level (a cell = the bin its 16 pixels share, 255 where they differ or the cell sticks out of the
-// map) — and validates the label range.  One thread = one 4x4 cell: four 16-byte loads (int32), four u32 stores
-// (the four lanes of a strip write 64 contiguous bytes) and one coarse byte.  Up to kPackBatch maps of one geometry
-// per launch (blockIdx.y): a 1080p map is 8 MB, i.e. ~2 us of HBM time, less than a launch.
-// Every byte of the map's pool stride is written, as seg_expand_kernel and the host packer's zeroed ring do: the threads
-// cover the PADDED cell grid (whole strips and bands of the coarse level, which contain those of the full-resolution
-// level), cells and rows past the map are 0 in both levels, and the first workgroup of a map clears the alignment gaps.
-// The pool is reused from run to run, so a byte left out would carry the previous run's data into what vote_export ships.
-// -------------------------------------------------------------------------------------------------
-static constexpr int kPackBatch = 16;
-static constexpr int kStripCols = 16, kBandRows = 8;    // pixel columns per strip, pixel rows per band (full-resolution level)
-static constexpr int kCStripCells = 16, kCBandRows = 8;  // cells per coarse strip, cell rows per coarse band
-struct PackArgs {
-    const void* src[kPackBatch];
-    uint8_t* dst[kPackBatch];
-    int view[kPackBatch];  // index reported through `err` when the map holds a label outside [-1, bins-2]
-    int w, h, strip_bytes, cstrip_bytes, cw, ch, bins;
-    int pw, ph;            // cells per row / column of the full-resolution level including its padding (row-major: cw, ch)
-    int gw, gh;            // the cell grid the threads cover: the coarse level including its padding (no coarse level: pw, ph)
-    unsigned gap_lo, coarse_off, map_bytes, stride;  // [gap_lo, coarse_off) and [map_bytes, stride) belong to no cell: zeroed
-    int* err;              // atomicMin of the offending view indices (INT_MAX = none)
-};
-
-static void pack_geometry(PackArgs& a, const MapLayout& L, int bins, int* err) {
-    a.w = L.w, a.h = L.h, a.strip_bytes = L.strip_bytes, a.cstrip_bytes = L.cstrip_bytes, a.cw = L.cw, a.ch = L.ch;
-    a.bins = bins;
-    a.pw = L.strip_bytes ? (L.w + kStripCols - 1) / kStripCols * (kStripCols / 4) : L.cw;
-    a.ph = L.strip_bytes ? (L.h + kBandRows - 1) / kBandRows * (kBandRows / 4) : L.ch;
-    a.gw = L.cstrip_bytes ? (L.cw + kCStripCells - 1) / kCStripCells * kCStripCells : a.pw;
-    a.gh = L.cstrip_bytes ? (L.ch + kCBandRows - 1) / kCBandRows * kCBandRows : a.ph;
-    a.gap_lo = (unsigned)(L.strip_bytes ? L.fine_bytes : (size_t)L.w * (size_t)L.h);  // row-major: the four tail bytes too
-    a.coarse_off = (unsigned)L.coarse_off;  // no coarse level: the end of the stride
-    a.map_bytes = (unsigned)L.map_bytes;
-    a.stride = (unsigned)((L.map_bytes + 255) / 256 * 256);
-    a.err = err;
-}
-
-template <typename T, int ADD, bool VEC>
-__global__ __launch_bounds__(kBlock) void seg_pack_fused_kernel(PackArgs a) {
-    const int job = blockIdx.y;
-    const T* __restrict__ in = static_cast<const T*>(a.src[job]);
-    uint8_t* __restrict__ out = a.dst[job];
-    if (blockIdx.x == 0) {  // the two alignment gaps, each shorter than 256 bytes
-        for (unsigned j = a.gap_lo + threadIdx.x; j < a.coarse_off; j += kBlock) out[j] = 0;
-        for (unsigned j = a.map_bytes + threadIdx.x; j < a.stride; j += kBlock) out[j] = 0;
-    }
-    const long long q = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const int cy = (int)(q / a.gw), cx = (int)(q % a.gw);
-    if (cy >= a.gh) return;
-    const int x0 = cx * 4, y0 = cy * 4;
-    const unsigned bins = (unsigned)a.bins;
-    const bool fine_pad = a.strip_bytes && cx < a.pw && cy < a.ph;  // a cell of a strip, in the map or in its padding
-    unsigned bad = 0;
-    uint32_t rows[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int y = y0 + r;
-        uint32_t packed = 0;
-        if (y >= a.h || cx >= a.cw) {  // rows below the map, cells right of it: bin 0 in the strips' padding
-            if (fine_pad) *reinterpret_cast<uint32_t*>(out + (long long)(x0 >> 4) * a.strip_bytes + ((long long)y << 4) + (x0 & 15)) = 0u;
-        } else {
-            const T* row = in + (long long)y * a.w + x0;
-            T v[4];
-            bool have[4];
-            if (VEC) {  // host checked: w % 4 == 0 and a 16-byte aligned base, so x0 + 4 <= w and the vector is aligned
-                typedef T vec4 __attribute__((ext_vector_type(4)));
-                const vec4 t = *reinterpret_cast<const vec4*>(row);
-                v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-                have[0] = have[1] = have[2] = have[3] = true;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    have[k] = x0 + k < a.w;
-                    v[k] = have[k] ? row[k] : (T)0;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned long long b = (unsigned long long)(long long)v[k] + (unsigned)ADD;  // label -2 wraps far above bins
-                bad |= (unsigned)(have[k] & (b >= bins));
-                packed |= (have[k] ? (uint32_t)(b & 0xffu) : 0u) << (8 * k);  // columns past the edge: bin 0
-            }
-            if (a.strip_bytes) {
-                *reinterpret_cast<uint32_t*>(out + (long long)(x0 >> 4) * a.strip_bytes + ((long long)y << 4) + (x0 & 15)) = packed;
-            } else {
-                const long long o = (long long)y * a.w + x0;
-                if (VEC) *reinterpret_cast<uint32_t*>(out + o) = packed;
-                else
-                    for (int k = 0; k < 4 && x0 + k < a.w; ++k) out[o + k] = (uint8_t)(packed >> (8 * k));
-            }
-        }
-        rows[r] = packed;
-    }
-    if (a.cstrip_bytes) {
-        const uint32_t same = (rows[0] & 0xffu) * 0x01010101u;
-        const bool uniform = x0 + 4 <= a.w && y0 + 4 <= a.h && rows[0] == same && rows[1] == same && rows[2] == same && rows[3] == same;
-        const bool cell = cx < a.cw && cy < a.ch;  // else the coarse strips' padding: 0
-        out[a.coarse_off + (long long)(cx >> 4) * a.cstrip_bytes + (cx & 15) + ((long long)cy << 4)] =
-            uniform ? (uint8_t)(rows[0] & 0xffu) : cell ? (uint8_t)255 : (uint8_t)0;
-    }
-    if (bad) atomicMin(a.err, a.view[job]);
-}
-
-// -------------------------------------------------------------------------------------------------
-// Host maps arrive in the COMPACT form of host_pack.hpp (coarse level + one 16-byte block per mixed 4x4 cell: the PCIe
-// link, not the host pass, is what a run's hand-over waits for, and a segmentation map is mostly uniform cells).  This
-// kernel, queued behind the DMA of a group of maps on a GPU that has nothing else to do while maps are handed over,
-// rebuilds the pool form: one workgroup = one band of 8 pixel rows (two cell rows) of one map; a thread takes the cells of a
-// cell row in the stream's order (by cell column), a ballot scan ranks the mixed ones, and every cell is written
-// as four 4-byte rows - its block, or its coarse byte four times over.  The coarse level is copied as it is; every
-// byte of the map's pool stride is written (cells and rows past the map, alignment gaps: 0), so a pool map stays a pure
-// function of the map, which exchange protocol v4 ships.
-// -------------------------------------------------------------------------------------------------
-struct ExpandArgs {
-    const uint8_t* rec[kCompactBatch];  // compact records in the device staging buffer
-    uint8_t* map[kCompactBatch];        // their places in the pool
-    int w, h, strip_bytes, cstrip_bytes, cw, ch, strips;
-    unsigned table_bytes, stream_off, coarse_off, fine_bytes, map_bytes, stride;
-    unsigned max_block;  // last block a cell row of this geometry can hold, counted from its first
-};
-
-__global__ __launch_bounds__(kBlock) void seg_expand_kernel(ExpandArgs a) {
-    __shared__ unsigned wave_total[kBlock / 64];
-    const uint8_t* __restrict__ rec = a.rec[blockIdx.y];
-    uint8_t* __restrict__ map = a.map[blockIdx.y];
-    const int band = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint8_t* __restrict__ coarse = rec + a.table_bytes;
-    const uint32_t* __restrict__ table = reinterpret_cast<const uint32_t*>(rec);
-    const uint4* __restrict__ stream = reinterpret_cast<const uint4*>(rec + a.stream_off);
-    const int per = a.strips * 4;  // cells per cell row (padded to whole strips)
-    for (int cyl = 0; cyl < 2; ++cyl) {  // the band's two cell rows: each has its own run of blocks in the stream
-        const int cy = band * 2 + cyl;
-        const unsigned first = table[2 * band + cyl];
-        unsigned running = 0;  // mixed cells of this cell row before the current round
-        for (int i0 = 0; i0 < per; i0 += kBlock) {
-            const int cx = i0 + tid;
-            const bool valid = cx < per;
-            const int s = cx >> 2, cc = cx & 3;
-            const bool cell = valid && cy < a.ch && cx < a.cw;
-            const unsigned cb = cell ? coarse[(size_t)(cx >> 4) * a.cstrip_bytes + (cx & 15) + ((size_t)cy << 4)] : 0u;
-            const bool mixed = cell && cb == 255u;
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(mixed);
-            const unsigned below = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-            __syncthreads();  // the previous round's totals have been read
-            if (lane == 0) wave_total[wv] = (unsigned)__popcll(m);
-            __syncthreads();
-            unsigned before = running;
-#pragma unroll
-            for (int k = 0; k < kBlock / 64; ++k) {
-                before += k < wv ? wave_total[k] : 0u;
-                running += wave_total[k];
-            }
-            if (valid) {
-                uint32_t r0, r1, r2, r3;
-                if (mixed) {
-                    const uint4 b = stream[first + min(before + below, a.max_block)];  // (a record is the library's own: the clamp never acts)
-                    r0 = b.x, r1 = b.y, r2 = b.z, r3 = b.w;
-                } else {
-                    r0 = r1 = r2 = r3 = cb * 0x01010101u;  // a uniform cell; 0 for the cells and rows past the map
-                }
-                uint8_t* o = map + (size_t)s * a.strip_bytes + ((size_t)(band * 8 + cyl * 4) << 4) + cc * 4;
-                *reinterpret_cast<uint32_t*>(o) = r0;
-                *reinterpret_cast<uint32_t*>(o + 16) = r1;
-                *reinterpret_cast<uint32_t*>(o + 32) = r2;
-                *reinterpret_cast<uint32_t*>(o + 48) = r3;
-            }
-        }
-    }
-    // the coarse level, verbatim (16-byte pieces dealt over the bands), and the alignment gaps
-    const unsigned cbytes = a.map_bytes - a.coarse_off;  // a multiple of 128
-    for (unsigned j = (unsigned)band * kBlock + tid; j < cbytes / 16; j += gridDim.x * kBlock)
-        reinterpret_cast<uint4*>(map + a.coarse_off)[j] = reinterpret_cast<const uint4*>(coarse)[j];
-    if (band == 0) {
-        for (unsigned j = a.fine_bytes + tid; j < a.coarse_off; j += kBlock) map[j] = 0;
-        for (unsigned j = a.map_bytes + tid; j < a.stride; j += kBlock) map[j] = 0;
-    }
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -553,6 +79,38 @@ struct FusedParams {
     unsigned long long* cull_tally;  // [0] += (wave, view) pairs skipped
     float filt_h;                    // kDivFiltCoarse: 0.5 - E of project_filtered() for the largest frame among the staged views
 };
+
+static inline int odd_dwords(int bytes) {
+    int dw = (bytes + 3) / 4;
+    return dw | 1;
+}
+// 0.5 - E of project_filtered() for the staged views (E grows with the frame: the largest one decides)
+static float filter_half_width(const Ctx* c) {
+    int dim = 64;
+    for (const ViewDesc& v : c->views) dim = std::max(dim, std::max(v.cam_w, v.cam_h));
+    return (float)(0.5 - kFilterK * (double)dim * 5.9604644775390625e-08);
+}
+// The parameters of a walk over ALL staged views of the whole scene (host side; call after sync_views()).  Every launch starts
+// from these and overrides what differs: the views and culling planes of a batch, the Gaussians of a range.
+static FusedParams fused_params(Ctx* c, int stride_bytes_per_bin) {
+    FusedParams p{};
+    p.x = c->x.as<float>();
+    p.y = c->y.as<float>();
+    p.z = c->z.as<float>();
+    p.n = c->n;
+    p.views = c->d_views.as<ViewDesc>();
+    p.nviews = (int)c->views.size();
+    p.pool = c->segpool.as<uint8_t>();
+    p.bins = c->bins;
+    p.xcd_swizzle = c->opt_xcd_swizzle;
+    p.perm = c->sorted ? c->perm.as<uint32_t>() : nullptr;
+    p.stride_dw = odd_dwords(c->bins * stride_bytes_per_bin);
+    p.cull = c->opt_wave_cull ? c->d_cull.as<double>() : nullptr;
+    p.cull_pitch = c->cull_pitch;
+    p.cull_tally = c->d_cull_tally.as<unsigned long long>();
+    p.filt_h = filter_half_width(c);
+    return p;
+}
 
 // ---- wave-level view culling ------------------------------------------------------------------------------------
 // 40 % of the (Gaussian, view) pairs of an ordinary capture are invisible, and in Morton order they come in whole
@@ -1383,13 +941,6 @@ static inline auto with_div(int dm, F&& f) {
         default: return f(std::integral_constant<int, FLAT_ONLY ? kDivFlat : kDivExact>{});
     }
 }
-// 0.5 - E of project_filtered() for the staged views (E grows with the frame: the largest one decides)
-static float filter_half_width(const Ctx* c) {
-    int dim = 64;
-    for (const ViewDesc& v : c->views) dim = std::max(dim, std::max(v.cam_w, v.cam_h));
-    return (float)(0.5 - kFilterK * (double)dim * 5.9604644775390625e-08);
-}
-static inline unsigned grid_for(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 int project_all(Ctx* c, const gsx_camera* cam, const float* dx, const float* dy, const float* dz, int64_t n,
                 int32_t* x_host, int32_t* y_host, const uint32_t* perm) {
@@ -1408,15 +959,10 @@ int project_all(Ctx* c, const gsx_camera* cam, const float* dx, const float* dy,
         // the filtered form is the vote kernels' (kDivFiltCoarse): frames up to 65535 pixels a side (hw32 exact, E < 1/64)
         const int dim = std::max(cam->width, cam->height);
         const float filt_h = (float)(0.5 - kFilterK * (double)std::max(dim, 64) * 5.9604644775390625e-08);
-        if (c->opt_flat_project && c->opt_filter_project && dim <= 65535)
-            hipLaunchKernelGGL(project_kernel<kDivFiltCoarse>, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n,
-                               dvd.as<ViewDesc>(), perm, ox.as<int>(), oy.as<int>(), filt_h);
-        else if (c->opt_flat_project)
-            hipLaunchKernelGGL(project_kernel<kDivFlat>, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n,
-                               dvd.as<ViewDesc>(), perm, ox.as<int>(), oy.as<int>(), 0.f);
-        else
-            hipLaunchKernelGGL(project_kernel<kDivExact>, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n,
-                               dvd.as<ViewDesc>(), perm, ox.as<int>(), oy.as<int>(), 0.f);
+        const bool filtered = c->opt_flat_project && c->opt_filter_project && dim <= 65535;
+        auto k = filtered ? project_kernel<kDivFiltCoarse> : c->opt_flat_project ? project_kernel<kDivFlat> : project_kernel<kDivExact>;
+        hipLaunchKernelGGL(k, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n, dvd.as<ViewDesc>(), perm, ox.as<int>(),
+                           oy.as<int>(), filtered ? filt_h : 0.f);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(x_host, ox.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream);
@@ -1427,6 +973,16 @@ int project_all(Ctx* c, const gsx_camera* cam, const float* dx, const float* dy,
     ox.release();
     oy.release();
     return rc;
+}
+
+// Orders c->stream behind whatever the second stream was last asked to do.  Needed wherever an early stage's buffers (ecnt,
+// efv, erec, bcnt) or the pool it reads are touched again: by the last stage that uses its result, and just as much by every
+// path that DROPS the result (fewer views than announced, rewind, a new run) and is about to overwrite those buffers.
+int early_join(Ctx* c) {
+    if (!c->early_inflight) return GSX_OK;
+    GSX_HIP(c, hipStreamWaitEvent(c->stream, c->early_done_ev, 0));
+    c->early_inflight = false;
+    return GSX_OK;
 }
 
 int vote_begin(Ctx* c, int n_classes, int first_view, int total_views) {
@@ -1447,8 +1003,7 @@ int vote_begin(Ctx* c, int n_classes, int first_view, int total_views) {
     if (c->sn == 0) c->sn = 256;
     c->n_pad = c->sn * c->slabs;
     c->views.clear();
-    c->pend_count = 0;  // packed maps of an abandoned run that never went up: forgotten with it
-    c->compact_bytes = 0;
+    c->ho.begin_run();
     c->views_dirty = true;
     c->pool_base = nullptr;
     c->seg_used = 0;
@@ -1457,466 +1012,13 @@ int vote_begin(Ctx* c, int n_classes, int first_view, int total_views) {
     c->planes_zero = false;
     c->planes_stale = false;
     c->labels_valid = false;
-    {
-        const int rcj = early_join(c);  // an abandoned run's early stage may still be running: this run reuses its buffers
-        if (rcj) return rcj;
-    }
+    if (const int rc = early_join(c)) return rc;  // an abandoned run's early stage may still be running: this run reuses its buffers
     c->early_state = 0;
     c->early_done = 0;
     c->early_batches = 0;
     GSX_HIP(c, c->errflag.ensure(sizeof(int)));
     GSX_HIP(c, hipMemsetAsync(c->errflag.p, 0x7f, sizeof(int), c->stream));  // kNoBadView
     c->vote_begun = true;
-    return GSX_OK;
-}
-
-static int pool_reserve(Ctx* c, size_t need) {
-    if (need <= c->segpool.cap) return GSX_OK;
-    {
-        const int rcf = vote_flush_pending(c);  // the pool is about to move: maps still waiting in the pinned ring go up first
-        if (rcf) return rcf;
-    }
-    if (c->early_state == 1 || c->early_batches > 0) {  // the early stage reads the pool that is about to be freed
-        GSX_HIP(c, hipStreamSynchronize(c->stream2));
-        c->early_inflight = false;
-        c->early_state = -1;
-        c->early_batches = 0;
-    }
-    size_t cap = c->segpool.cap ? c->segpool.cap : ((size_t)64 << 20);
-    while (cap < need) cap *= 2;
-    void* np = nullptr;
-    GSX_HIP(c, hipMalloc(&np, cap));
-    if (c->seg_used) {
-        hipError_t e = hipMemcpyAsync(np, c->segpool.p, c->seg_used, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(np);
-            return fail(c, GSX_E_HIP, "seg pool growth copy failed: %s", hipGetErrorString(e));
-        }
-    }
-    c->segpool.release();
-    c->segpool.p = np;
-    c->segpool.cap = cap;
-    return GSX_OK;
-}
-
-// ---- seg-map hand-over ------------------------------------------------------------------------------------------
-// Common front part of gsx_vote_view / gsx_vote_views_device: argument checks, the map's layout, room in the pool.
-static int view_prologue(Ctx* c, const char* who, const void* cams, const void* seg, int n, int seg_dtype, int seg_w, int seg_h,
-                         int img_w, int img_h, MapLayout& L) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "%s before vote_begin", who);
-    if (c->pool_base) return fail(c, GSX_E_STATE, "%s after gsx_vote_import: the run's views are final; start the next one with gsx_vote_begin", who);
-    if (!cams || !seg) return fail(c, GSX_E_INVALID, "%s: NULL argument", who);
-    if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1)
-        return fail(c, GSX_E_INVALID, "%s: sizes must be positive (seg %dx%d, image %dx%d)", who, seg_w, seg_h, img_w, img_h);
-    if (seg_w > 65535 || seg_h > 65535)  // in-map byte offsets are 32-bit, row products use 24-bit multiplies
-        return fail(c, GSX_E_RANGE, "%s: segmentation map %dx%d exceeds 65535 pixels a side", who, seg_w, seg_h);
-    if (seg_dtype != GSX_SEG_I32 && seg_dtype != GSX_SEG_I64 && seg_dtype != GSX_SEG_U8 && seg_dtype != GSX_SEG_U8_LABELS)
-        return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
-    if (c->first_view + (int)c->views.size() + n > c->total_views)
-        return fail(c, GSX_E_RANGE, "%s: more views than total_views=%d announced at vote_begin", who, c->total_views);
-    if (c->local_codes && (int)c->views.size() + n > kMaxBatch)
-        return fail(c, GSX_E_RANGE, "%s: the all-to-all exchange keeps 8-bit per-rank counters: at most %d views per rank", who,
-                    kMaxBatch);
-    GSX_HIP(c, hipSetDevice(c->device));
-    // bin 255 must be free to mean "mixed" in the coarse level
-    L = map_layout(seg_w, seg_h, c->opt_seg_tiled != 0, c->opt_seg_coarse && c->bins <= 255);
-    if (L.map_bytes > 0xffffffffull) return fail(c, GSX_E_RANGE, "%s: segmentation map %dx%d exceeds 4 GiB", who, seg_w, seg_h);
-    const size_t stride = (L.map_bytes + 255) / 256 * 256;  // 256-B aligned maps
-    const size_t off = (c->seg_used + 255) / 256 * 256;
-    size_t need = off + stride * (size_t)n;
-    if (c->views.empty()) {
-        // first view of a run: room for all announced views of this geometry at once (capped), so that the pool is
-        // not re-allocated and copied while maps stream in
-        const size_t all = stride * (size_t)(c->total_views - c->first_view);
-        need = std::max(need, std::min(all, (size_t)32 << 30));
-    }
-    return pool_reserve(c, need);
-}
-
-static void push_view(Ctx* c, const gsx_camera* cam, const MapLayout& L, size_t off, int img_w, int img_h) {
-    ViewDesc vd;
-    fill_view_desc(vd, cam, L.w, L.h, img_w, img_h);
-    vd.seg_off = (long long)off;
-    vd.seg_row_bytes = L.strip_bytes;
-    vd.coarse_row_bytes = L.cstrip_bytes;
-    vd.coarse_delta = (unsigned)L.coarse_off;
-    c->views.push_back(vd);
-    c->views_dirty = true;
-    c->seg_used = off + L.map_bytes;
-    c->labels_valid = false;
-}
-
-// near: a buffer the pool is about to read (the first map of a run): the workers are placed on its NUMA node
-static void launch_pack(Ctx* c, const PackArgs& a, int jobs, int seg_dtype, bool vec);
-
-static Workers* host_workers(Ctx* c, const void* near = nullptr) {
-    if (!c->workers) {
-        try {
-            c->workers = new Workers(c->opt_host_threads > 0 ? c->opt_host_threads : default_host_threads(), numa_node_of(near));
-        } catch (...) {  // out of memory (a thread that cannot be started is handled inside: the pool then has one thread)
-            c->workers = nullptr;
-        }
-    }
-    return c->workers;  // nullptr: single-threaded packing on the calling thread
-}
-
-// Host map: the worker threads narrow it into the next slot of the pinned ring (u8 strips + coarse level, range
-// checked on the way: an out-of-range label fails THIS call), one asynchronous DMA moves the packed map into the
-// pool.  No kernel, no synchronisation; the call returns as soon as the caller's buffer has been read.
-static int early_vote_stage(Ctx* c);
-
-static int vote_view_host(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h) {
-    MapLayout L;
-    int rc = view_prologue(c, "vote_view", cam, seg, 1, seg_dtype, seg_w, seg_h, img_w, img_h, L);
-    if (rc) return rc;
-    if (c->opt_host_pack) {
-        const size_t stride = (L.map_bytes + 255) / 256 * 256;
-        constexpr int kSlots = kDmaBatch * kDmaGroups;
-        // compact transfer form (host_pack.hpp) whenever the pool form has both levels; else the pool form itself
-        const bool compact = c->opt_host_compact && L.strip_bytes && L.cstrip_bytes;
-        const CompactLayout CL = compact ? compact_layout(L) : CompactLayout{};
-        const size_t slot_bytes = compact ? (CL.capacity + 255) / 256 * 256 : stride;
-        if (c->hring_slot != slot_bytes || !c->hring || c->hring_compact != compact) {  // first map, or a new geometry: re-lay the ring
-            if ((rc = vote_flush_pending(c))) return rc;
-            for (int g = 0; g < kDmaGroups; ++g) {
-                if (c->hring_busy[g]) GSX_HIP(c, hipEventSynchronize(c->hring_ev[g]));
-                c->hring_busy[g] = false;
-                if (!c->hring_ev[g]) GSX_HIP(c, hipEventCreateWithFlags(&c->hring_ev[g], hipEventDisableTiming));
-            }
-            if (c->hring_bytes < slot_bytes * kSlots) {
-                if (c->hring) GSX_HIP(c, hipHostFree(c->hring));
-                c->hring = nullptr;
-                c->hring_bytes = 0;
-                GSX_HIP(c, hipHostMalloc(&c->hring, slot_bytes * kSlots, hipHostMallocDefault));
-                c->hring_bytes = slot_bytes * kSlots;
-            }
-            if (!compact) std::memset(c->hring, 0, slot_bytes * kSlots);  // the bytes between a map's end and its stride travel too
-            c->hring_slot = slot_bytes;
-            c->hring_compact = compact;
-            c->hring_next = 0;
-            c->cgrp = 0;
-            c->grp_recs = 0;
-        }
-        const size_t off = (c->seg_used + 255) / 256 * 256;
-        if (compact) {
-            // records of a group lie back to back (a record is as long as its map has mixed cells): one DMA per group moves
-            // exactly the bytes in use, and a group takes as many records as fit (at most kCompactBatch)
-            const size_t gcap = (size_t)kDmaBatch * slot_bytes;
-            if (c->grp_recs == 0) {
-                if (c->hring_busy[c->cgrp]) {  // the group's previous DMA must have left the buffer
-                    GSX_HIP(c, hipEventSynchronize(c->hring_ev[c->cgrp]));
-                    c->hring_busy[c->cgrp] = false;
-                }
-                c->grp_used = 0;
-            }
-            if (c->h_scratch_cap < L.fine_bytes) {
-                std::free(c->h_scratch);
-                c->h_scratch = nullptr;
-                c->h_scratch_cap = 0;
-                const size_t cap = (L.fine_bytes + 4095) / 4096 * 4096;
-                if (!(c->h_scratch = std::aligned_alloc(4096, cap))) return fail(c, GSX_E_HIP, "vote_view: out of host memory");
-                c->h_scratch_cap = cap;
-            }
-            uint8_t* rec = static_cast<uint8_t*>(c->hring) + (size_t)c->cgrp * gcap + c->grp_used;
-            size_t blocks = 0;
-            if (!(c->opt_ablate & 2) &&  // timing experiment only: the DMA stream without the host pass; results invalid
-                host_pack_map_compact(host_workers(c, seg), seg, seg_dtype, L, c->bins, static_cast<uint8_t*>(c->h_scratch), rec, &blocks))
-                return fail(c, GSX_E_RANGE, "vote_view: segmentation map holds a label outside [-1, %d]", c->n_classes - 1);
-            if (c->pend_count && (L.w != c->pend_L.w || L.h != c->pend_L.h)) {  // one expansion launch = one geometry
-                if ((rc = vote_flush_pending(c))) return rc;
-            }
-            if (!c->pend_count) {
-                c->pend_group = c->cgrp;
-                c->pend_lo = c->grp_used;
-                c->pend_L = L;
-            }
-            c->pend_rec[c->pend_count] = c->grp_used;
-            c->pend_map[c->pend_count] = off;
-            ++c->pend_count;
-            ++c->grp_recs;
-            c->grp_used += (CL.stream_off + blocks * 16 + 255) / 256 * 256;
-            c->compact_bytes += CL.stream_off + blocks * 16;
-            push_view(c, cam, L, off, img_w, img_h);
-            const bool full = c->grp_recs == kCompactBatch || c->grp_used + slot_bytes > gcap;  // no room for a worst-case record
-            // the last views of the run (as announced to vote_begin) go up one by one: a group waiting for more maps would put
-            // its DMA between the last hand-over and the vote
-            const bool tail = c->total_views - c->first_view - (int)c->views.size() < kDmaBatch;
-            if (tail || full) rc = vote_flush_pending(c);
-            if (full) {
-                c->cgrp = (c->cgrp + 1) % kDmaGroups;
-                c->grp_recs = 0;
-            }
-            return rc;
-        }
-        const int s = c->hring_next, g = s / kDmaBatch;
-        if (s % kDmaBatch == 0 && c->hring_busy[g]) {  // the group's previous DMA must have left the buffer
-            GSX_HIP(c, hipEventSynchronize(c->hring_ev[g]));
-            c->hring_busy[g] = false;
-        }
-        uint8_t* slot = static_cast<uint8_t*>(c->hring) + (size_t)s * stride;
-        if (!(c->opt_ablate & 2) && host_pack_map(host_workers(c, seg), seg, seg_dtype, L, c->bins, slot))
-            return fail(c, GSX_E_RANGE, "vote_view: segmentation map holds a label outside [-1, %d]", c->n_classes - 1);
-        if (c->pend_count && off != c->pend_dst + (size_t)c->pend_count * stride) {  // the pool moved on (device maps in between)
-            if ((rc = vote_flush_pending(c))) return rc;
-        }
-        if (!c->pend_count) {
-            c->pend_first = s;
-            c->pend_dst = off;
-        }
-        ++c->pend_count;
-        c->compact_bytes += stride;
-        push_view(c, cam, L, off, img_w, img_h);
-        c->hring_next = (s + 1) % kSlots;
-        // the last views of the run (as announced to vote_begin) go up one by one: a whole group waiting for its fourth map
-        // would put its 4-map DMA between the last hand-over and the vote
-        const bool tail = c->total_views - c->first_view - (int)c->views.size() < kDmaBatch;
-        if (tail || c->pend_count == kDmaBatch || c->hring_next % kDmaBatch == 0) return vote_flush_pending(c);
-        return GSX_OK;
-    }
-    PinSlot& slot = c->ring[c->ring_next];
-    if (slot.busy) {
-        GSX_HIP(c, hipEventSynchronize(slot.ev));
-        slot.busy = false;
-    }
-    if (slot.cap < L.map_bytes) {
-        if (slot.p) GSX_HIP(c, hipHostFree(slot.p));
-        slot.p = nullptr;
-        slot.cap = 0;
-        const size_t cap = (L.map_bytes + ((size_t)1 << 20) - 1) >> 20 << 20;
-        GSX_HIP(c, hipHostMalloc(&slot.p, cap, hipHostMallocDefault));
-        slot.cap = cap;
-    }
-    if (!slot.ev) GSX_HIP(c, hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
-    {
-        // The alternative this library does NOT default to (kept for hosts short of cores, and as the A/B of DESIGN.md §3):
-        // the raw map crosses PCIe (8.3 MB instead of 2.2 MB per 1080p int32 map) and the fused kernel packs it on the GPU.
-        // The range check is then the device-side one (reported with the labels).
-        const size_t esz = seg_dtype == GSX_SEG_I32 ? 4 : seg_dtype == GSX_SEG_I64 ? 8 : 1;
-        const size_t raw = esz * (size_t)seg_w * (size_t)seg_h;
-        if (slot.cap < raw) {
-            GSX_HIP(c, hipHostFree(slot.p));
-            slot.p = nullptr;
-            slot.cap = 0;
-            GSX_HIP(c, hipHostMalloc(&slot.p, raw, hipHostMallocDefault));
-            slot.cap = raw;
-        }
-        DevBuf& land = c->dstage[c->ring_next];
-        GSX_HIP(c, land.ensure(raw));
-        host_copy(host_workers(c, seg), slot.p, seg, raw);
-        GSX_HIP(c, hipMemcpyAsync(land.p, slot.p, raw, hipMemcpyHostToDevice, c->stream));
-        const size_t off = (c->seg_used + 255) / 256 * 256;
-        PackArgs a{};
-        a.src[0] = land.p;
-        a.dst[0] = c->segpool.as<uint8_t>() + off;
-        a.view[0] = c->first_view + (int)c->views.size();
-        pack_geometry(a, L, c->bins, c->errflag.as<int>());
-        launch_pack(c, a, 1, seg_dtype, seg_w % 4 == 0);
-        GSX_HIP(c, hipGetLastError());
-        GSX_HIP(c, hipEventRecord(slot.ev, c->stream));  // after the kernel: it is the last reader of this slot's landing zone
-        slot.busy = true;
-        c->ring_next = (c->ring_next + 1) % kPinSlots;
-        push_view(c, cam, L, off, img_w, img_h);
-        return GSX_OK;
-    }
-    return GSX_OK;  // unreachable: both hand-over paths return above
-}
-
-int vote_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h) {
-    const int rc = vote_view_host(c, cam, seg, seg_dtype, seg_w, seg_h, img_w, img_h);
-    return rc ? rc : early_vote_stage(c);  // enough of the run staged: its first views are voted while the rest is handed over
-}
-
-static void launch_pack(Ctx* c, const PackArgs& a, int jobs, int seg_dtype, bool vec) {
-    using K = void (*)(PackArgs);
-    static const K table[4][2] = {{seg_pack_fused_kernel<int32_t, 1, false>, seg_pack_fused_kernel<int32_t, 1, true>},
-                                  {seg_pack_fused_kernel<int64_t, 1, false>, seg_pack_fused_kernel<int64_t, 1, true>},
-                                  {seg_pack_fused_kernel<uint8_t, 0, false>, seg_pack_fused_kernel<uint8_t, 0, true>},
-                                  {seg_pack_fused_kernel<uint8_t, 1, false>, seg_pack_fused_kernel<uint8_t, 1, true>}};
-    ProfScope ps(c, "seg_pack");
-    hipLaunchKernelGGL(table[seg_dtype][vec ? 1 : 0], dim3(grid_for((long long)a.gw * a.gh), jobs), dim3(kBlock), 0, c->stream, a);
-}
-
-void segpack_constants(int32_t out[8]) {
-    out[0] = kBlock;
-    out[1] = kPackBatch;
-    out[2] = kStripCols;
-    out[3] = kBandRows;
-    out[4] = kCStripCells;
-    out[5] = kCBandRows;
-    out[6] = out[7] = 0;
-}
-
-// Device maps (all of one geometry and dtype): kPackBatch maps per launch of the fused pack kernel.  Nothing is
-// read back: a label out of range is recorded on the device and reported by the call that hands out the labels.
-int vote_views_device(Ctx* c, int n, const gsx_camera* cams, const void* const* segs, int seg_dtype, int seg_w, int seg_h,
-                      int img_w, int img_h) {
-    if (n <= 0) return n == 0 ? GSX_OK : fail(c, GSX_E_INVALID, "vote_views_device: n < 0");
-    MapLayout L;
-    int rc = view_prologue(c, "vote_views_device", cams, segs, n, seg_dtype, seg_w, seg_h, img_w, img_h, L);
-    if (rc) return rc;
-    for (int i = 0; i < n; ++i)
-        if (!segs[i]) return fail(c, GSX_E_INVALID, "vote_views_device: map %d is NULL", i);
-    const size_t esz = seg_dtype == GSX_SEG_I32 ? 4 : seg_dtype == GSX_SEG_I64 ? 8 : 1;
-    for (int i0 = 0; i0 < n; i0 += kPackBatch) {
-        const int m = std::min(kPackBatch, n - i0);
-        PackArgs a{};
-        bool vec = seg_w % 4 == 0;
-        size_t off = 0;
-        for (int k = 0; k < m; ++k) {
-            off = (c->seg_used + 255) / 256 * 256;
-            a.src[k] = segs[i0 + k];
-            a.dst[k] = c->segpool.as<uint8_t>() + off;
-            a.view[k] = c->first_view + (int)c->views.size();
-            vec = vec && reinterpret_cast<uintptr_t>(segs[i0 + k]) % (4 * esz) == 0;
-            push_view(c, cams + i0 + k, L, off, img_w, img_h);
-        }
-        pack_geometry(a, L, c->bins, c->errflag.as<int>());
-        launch_pack(c, a, m, seg_dtype, vec);
-        GSX_HIP(c, hipGetLastError());
-    }
-    return GSX_OK;
-}
-
-// One DMA for the packed maps that wait in the filling group of the pinned ring (up to kDmaBatch consecutive slots =
-// consecutive pool offsets).  Called when the group is full, for each of the last maps of a run, and by everything that
-// needs the maps on the device.
-int vote_flush_pending(Ctx* c) {
-    if (!c->pend_count) return GSX_OK;
-    GSX_HIP(c, hipSetDevice(c->device));
-    if (c->hring_compact) {
-        const int g = c->pend_group;
-        const size_t gcap = (size_t)kDmaBatch * c->hring_slot;
-        GSX_HIP(c, c->cstage.ensure(gcap));
-        const uint8_t* src = static_cast<uint8_t*>(c->hring) + (size_t)g * gcap;
-        if (!(c->opt_ablate & 1))  // timing experiment only (tools/tail_probe.py): the host pass without its DMA; results invalid
-            GSX_HIP(c, hipMemcpyAsync(c->cstage.as<uint8_t>() + c->pend_lo, src + c->pend_lo, c->grp_used - c->pend_lo, hipMemcpyHostToDevice,
-                                      c->stream));
-        GSX_HIP(c, hipEventRecord(c->hring_ev[g], c->stream));
-        c->hring_busy[g] = true;
-        const MapLayout& L = c->pend_L;
-        const CompactLayout CL = compact_layout(L);
-        ExpandArgs a{};
-        for (int k = 0; k < c->pend_count; ++k) {
-            a.rec[k] = c->cstage.as<uint8_t>() + c->pend_rec[k];
-            a.map[k] = c->segpool.as<uint8_t>() + c->pend_map[k];
-        }
-        a.w = L.w, a.h = L.h, a.strip_bytes = L.strip_bytes, a.cstrip_bytes = L.cstrip_bytes, a.cw = L.cw, a.ch = L.ch;
-        a.strips = (L.w + 15) / 16;
-        a.table_bytes = (unsigned)CL.table_bytes, a.stream_off = (unsigned)CL.stream_off, a.coarse_off = (unsigned)L.coarse_off;
-        a.fine_bytes = (unsigned)L.fine_bytes, a.map_bytes = (unsigned)L.map_bytes, a.stride = (unsigned)((L.map_bytes + 255) / 256 * 256);
-        a.max_block = (unsigned)(L.cw - 1);
-        if (!(c->opt_ablate & 3)) {  // (an ablation of the hand-over leaves no valid record to expand)
-            ProfScope ps(c, "seg_expand");
-            hipLaunchKernelGGL(seg_expand_kernel, dim3((unsigned)CL.bands, (unsigned)c->pend_count), dim3(kBlock), 0, c->stream, a);
-            GSX_HIP(c, hipGetLastError());
-        }
-        c->pend_count = 0;
-        return GSX_OK;
-    }
-    const int g = c->pend_first / kDmaBatch;
-    const size_t bytes = (size_t)c->pend_count * c->hring_slot;
-    if (!(c->opt_ablate & 1))
-        GSX_HIP(c, hipMemcpyAsync(c->segpool.as<uint8_t>() + c->pend_dst, static_cast<uint8_t*>(c->hring) + (size_t)c->pend_first * c->hring_slot,
-                                  bytes, hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(c, hipEventRecord(c->hring_ev[g], c->stream));
-    c->hring_busy[g] = true;
-    c->pend_count = 0;
-    // a group that was flushed before it was full keeps filling: its later slots are not in flight, and the event (recorded
-    // again by the next flush) always stands for the group's LAST copy, which is what the next lap waits for
-    return GSX_OK;
-}
-
-int host_threads(Ctx* c) {
-    Workers* w = host_workers(c);
-    return w ? w->threads() : 1;
-}
-
-void vote_release_host(Ctx* c) {
-    for (PinSlot& s : c->ring) {
-        if (s.ev) (void)hipEventDestroy(s.ev);
-        if (s.p) (void)hipHostFree(s.p);
-        s = PinSlot{};
-    }
-    for (DevBuf& b : c->dstage) b.release();
-    for (hipEvent_t& e : c->hring_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    if (c->hring) (void)hipHostFree(c->hring);
-    c->hring = nullptr;
-    c->hring_bytes = c->hring_slot = 0;
-    std::free(c->h_scratch);
-    c->h_scratch = nullptr;
-    c->h_scratch_cap = 0;
-    c->cstage.release();
-    c->pend_count = 0;
-    for (hipEvent_t& e : c->h_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    if (c->h_labels) (void)hipHostFree(c->h_labels);
-    c->h_labels = nullptr;
-    c->h_labels_cap = 0;
-    if (c->h_views_ev) (void)hipEventDestroy(c->h_views_ev);
-    c->h_views_ev = nullptr;
-    if (c->h_views) (void)hipHostFree(c->h_views);
-    c->h_views = nullptr;
-    c->h_views_cap = 0;
-    delete c->workers;
-    c->workers = nullptr;
-    if (c->stream2) {
-        (void)hipStreamSynchronize(c->stream2);
-        (void)hipStreamDestroy(c->stream2);
-        c->stream2 = nullptr;
-    }
-    for (hipEvent_t* e : {&c->early_maps_ev, &c->early_done_ev, &c->early_up_ev}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
-    if (c->h_early) (void)hipHostFree(c->h_early);
-    c->h_early = nullptr;
-    c->h_early_cap = 0;
-    for (DevBuf* b : {&c->ecnt, &c->efv, &c->erec, &c->e_views, &c->e_cull}) b->release();
-    c->early_state = -1;
-}
-
-// test hook, host only: the packed form of one map exactly as gsx_vote_view stages it
-int debug_host_pack(const void* seg, int seg_dtype, int w, int h, int n_classes, int tiled, int coarse, int threads,
-                    uint8_t* out, int64_t out_cap, int64_t* bytes, int64_t* coarse_off, int32_t* bad) {
-    if (!seg || w < 1 || h < 1 || w > 65535 || h > 65535 || n_classes < 1 || n_classes > 255 || seg_dtype < 0 || seg_dtype > 3)
-        return fail(nullptr, GSX_E_INVALID, "debug_host_pack: bad arguments");
-    const MapLayout L = map_layout(w, h, tiled != 0, coarse != 0 && n_classes + 1 <= 255);
-    if (bytes) *bytes = (int64_t)L.map_bytes;
-    if (coarse_off) *coarse_off = L.cstrip_bytes ? (int64_t)L.coarse_off : -1;
-    if (!out) return GSX_OK;
-    if (out_cap < (int64_t)L.map_bytes) return fail(nullptr, GSX_E_INVALID, "debug_host_pack: output buffer too small");
-    Workers pool(threads > 0 ? threads : 1);
-    const int b = host_pack_map(&pool, seg, seg_dtype, L, n_classes + 1, out);
-    if (bad) *bad = b;
-    return GSX_OK;
-}
-
-// test hook, host only: the compact transfer form of one map (host_pack.hpp), as gsx_vote_view writes it into the pinned ring
-int debug_host_pack_compact(const void* seg, int seg_dtype, int w, int h, int n_classes, int threads, uint8_t* out, int64_t out_cap,
-                            int64_t* bytes, int64_t* table_bytes, int64_t* stream_off, int32_t* bad) {
-    if (!seg || w < 1 || h < 1 || w > 65535 || h > 65535 || n_classes < 1 || n_classes > 254 || seg_dtype < 0 || seg_dtype > 3 || !bytes)
-        return fail(nullptr, GSX_E_INVALID, "debug_host_pack_compact: bad arguments");
-    const MapLayout L = map_layout(w, h, true, true);
-    const CompactLayout CL = compact_layout(L);
-    if (table_bytes) *table_bytes = (int64_t)CL.table_bytes;
-    if (stream_off) *stream_off = (int64_t)CL.stream_off;
-    *bytes = (int64_t)CL.capacity;
-    if (!out) return GSX_OK;
-    if (out_cap < (int64_t)CL.capacity) return fail(nullptr, GSX_E_INVALID, "debug_host_pack_compact: output buffer too small");
-    void* scratch = std::aligned_alloc(4096, (L.fine_bytes + 4095) / 4096 * 4096);
-    if (!scratch) return fail(nullptr, GSX_E_HIP, "debug_host_pack_compact: out of memory");
-    Workers pool(threads > 0 ? threads : 1);
-    size_t blocks = 0;
-    const int b = host_pack_map_compact(&pool, seg, seg_dtype, L, n_classes + 1, static_cast<uint8_t*>(scratch), out, &blocks);
-    std::free(scratch);
-    if (bad) *bad = b;
-    *bytes = (int64_t)(CL.stream_off + blocks * 16);
     return GSX_OK;
 }
 
@@ -2040,20 +1142,38 @@ void debug_cull_planes(const gsx_camera* cam, double* out) {
     cull_planes(vd, out);
 }
 
+// The device form of the views [lo, hi) into dev[0 .. hi - lo): the host descriptor with the map's absolute address (seg_off +
+// pool_base; one scalar add less per view and wave); their culling planes into planes[k * pitch + (i - lo)], plane-component-
+// major so that lane l reads view l with unit stride.  Returns what the projection variants ask of a batch (flat_div_mode).
+struct ViewKinds {
+    bool simple, coarse;  // every view: unit scale + tiled map; ... and a coarse level
+};
+static ViewKinds stage_views(const Ctx* c, int lo, int hi, const void* pool_base, ViewDesc* dev, double* planes, size_t pitch) {
+    const long long base = (long long)reinterpret_cast<uintptr_t>(pool_base);
+    ViewKinds kinds{true, true};
+    for (int i = lo; i < hi; ++i) {
+        ViewDesc& v = dev[i - lo];
+        v = c->views[i];
+        v.seg_off += base;
+        kinds.simple = kinds.simple && v.unit_scale && v.seg_row_bytes;
+        kinds.coarse = kinds.coarse && v.coarse_row_bytes;
+        double pl[kCullStride * kCullPlanes];
+        cull_planes(v, pl);
+        for (int k = 0; k < kCullStride * kCullPlanes; ++k) planes[(size_t)k * pitch + (i - lo)] = pl[k];
+    }
+    return kinds;
+}
+
 // Host descriptors -> device: the map's absolute address goes into the device copy (one scalar add less per view
 // and wave), the culling planes are derived here.  Staged through pinned memory owned by the ctx and guarded by an
 // event, so nothing waits for the stream: the maps that vote_view queued keep flowing while this is prepared.
 static int sync_views(Ctx* c) {
-    {
-        const int rcf = vote_flush_pending(c);  // every consumer of the views comes through here
-        if (rcf) return rcf;
-    }
+    if (const int rc = vote_flush_pending(c)) return rc;  // every consumer of the views comes through here
     if (!c->views_dirty) return GSX_OK;
     const size_t nv = c->views.size();
     const size_t bytes = sizeof(ViewDesc) * (nv ? nv : 1);
     GSX_HIP(c, c->d_views.ensure(bytes));
-    c->views_simple = nv != 0;
-    c->views_coarse = c->views_simple;
+    c->views_simple = c->views_coarse = false;  // no views: nothing to be simple about
     if (nv) {
         const int pitch = (int)((nv + 63) / 64 * 64);
         const size_t plane_doubles = (size_t)kCullStride * kCullPlanes * pitch;
@@ -2070,35 +1190,18 @@ static int sync_views(Ctx* c) {
         ViewDesc* dev = static_cast<ViewDesc*>(c->h_views);
         double* planes = reinterpret_cast<double*>(static_cast<char*>(c->h_views) + bytes);
         std::memset(planes, 0, sizeof(double) * plane_doubles);
-        const long long base = (long long)reinterpret_cast<uintptr_t>(c->pool_base ? c->pool_base : c->segpool.p);
-        for (size_t i = 0; i < nv; ++i) {
-            ViewDesc& v = dev[i];
-            v = c->views[i];
-            v.seg_off += base;
-            c->views_simple = c->views_simple && v.unit_scale && v.seg_row_bytes;
-            c->views_coarse = c->views_coarse && v.coarse_row_bytes;
-            // culling planes, plane-component-major so that lane l reads view l with unit stride
-            double pl[kCullStride * kCullPlanes];
-            cull_planes(v, pl);
-            for (int k = 0; k < kCullStride * kCullPlanes; ++k) planes[(size_t)k * pitch + i] = pl[k];
-        }
+        const ViewKinds kinds = stage_views(c, 0, (int)nv, c->pool_base ? c->pool_base : c->segpool.p, dev, planes, (size_t)pitch);
+        c->views_simple = kinds.simple;
+        c->views_coarse = kinds.coarse;
         GSX_HIP(c, c->d_cull.ensure(sizeof(double) * plane_doubles));
         GSX_HIP(c, hipMemcpyAsync(c->d_views.p, dev, bytes, hipMemcpyHostToDevice, c->stream));
         GSX_HIP(c, hipMemcpyAsync(c->d_cull.p, planes, sizeof(double) * plane_doubles, hipMemcpyHostToDevice, c->stream));
         GSX_HIP(c, hipEventRecord(c->h_views_ev, c->stream));
         c->cull_pitch = pitch;
-        {
-            const int rct = ensure_tally(c);
-            if (rct) return rct;
-        }
+        if (const int rc = ensure_tally(c)) return rc;
     }
     c->views_dirty = false;
     return GSX_OK;
-}
-
-static inline int odd_dwords(int bytes) {
-    int dw = (bytes + 3) / 4;
-    return dw | 1;
 }
 
 static int ensure_planes(Ctx* c) {
@@ -2138,10 +1241,7 @@ int vote_rewind(Ctx* c) {
     c->labels_valid = false;
     c->early_state = -1;  // a rewound run is voted in one piece (its views are all there)
     c->early_batches = 0;
-    {
-        const int rcj = early_join(c);  // ... behind whatever the early stage is still doing to bcnt / ecnt / erec
-        if (rcj) return rcj;
-    }
+    if (const int rc = early_join(c)) return rc;  // ... behind whatever the early stage is still doing to bcnt / ecnt / erec
     if (c->planes_valid) {
         c->planes_valid = false;
         c->planes_zero = false;
@@ -2160,8 +1260,22 @@ static int set_lds(Ctx* c, K kernel, size_t bytes) {
 
 static constexpr int kUnroll = 8;
 
+// One launch of a kernel that walks p's views over n Gaussians with a histogram row of p.stride_dw dwords per thread in LDS:
+// k(p, p.views, args...) on stream st, timed as `name` when profiling is on.
+template <class K, class... Args>
+static int launch_walk(Ctx* c, const char* name, hipStream_t st, K k, long long n, const FusedParams& p, Args... args) {
+    const size_t lds = (size_t)kBlock * p.stride_dw * 4;
+    const int rc = set_lds(c, k, lds);
+    if (rc) return rc;
+    ProfScope ps(c, name, st);
+    hipLaunchKernelGGL(k, dim3(grid_for(n)), dim3(kBlock), lds, st, p, p.views, args...);
+    GSX_HIP(c, hipGetLastError());
+    return GSX_OK;
+}
+// bytes of keys / labels: int32 [n_pad], never an empty buffer
+static inline size_t label_bytes(const Ctx* c) { return sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1); }
+
 // ---- early vote ---------------------------------------------------------------------------------------------------
-FusedParams fused_params(Ctx* c, int stride_bytes_per_bin);
 // A run is the hand-over of its maps (the host pass over them, ~37 us per 1080p map) followed by the vote over all of
 // them (~1.2 ms for 3 M Gaussians x 200 views) with the GPU idle during the first and the host during the second.
 // When enough of the announced views are staged (`early_vote_at` permille, or a split chosen from the hand-over rate), their
@@ -2191,7 +1305,6 @@ static bool early_possible(const Ctx* c) { return early_common(c) && c->total_vi
 // kernels on the second stream as soon as their views are staged; only the last batch, the totals and the tie walk are
 // left behind the last map
 static bool early_batched_possible(const Ctx* c) { return early_common(c) && c->total_views > kMaxBatch && c->opt_batched_counts; }
-static int early_batch_stage(Ctx* c);
 // The early batches: a short LAST batch (its count kernel is what stays behind the last map) after balanced ones of <= 255
 // views.  Any cut of the view order into consecutive batches gives the same labels (the earliest batch wins a tie).
 static int early_batch_count(int total) {
@@ -2226,19 +1339,8 @@ static int early_upload(Ctx* c, int lo, int hi, int block, int blocks, hipStream
     ViewDesc* hv = static_cast<ViewDesc*>(c->h_early);  // the stage's views, at most kEarlyPitch
     double* planes = reinterpret_cast<double*>(static_cast<char*>(c->h_early) + vbytes);
     std::memset(planes, 0, cbytes);
-    const long long base = (long long)reinterpret_cast<uintptr_t>(c->segpool.p);
-    bool simple = true, coarse = true;
-    for (int i = lo; i < hi; ++i) {
-        ViewDesc& v = hv[i - lo];
-        v = c->views[i];
-        v.seg_off += base;
-        simple = simple && v.unit_scale && v.seg_row_bytes;
-        coarse = coarse && v.coarse_row_bytes;
-        double pl[kCullStride * kCullPlanes];
-        cull_planes(v, pl);
-        for (int k = 0; k < kCullStride * kCullPlanes; ++k) planes[(size_t)k * kEarlyPitch + (i - lo)] = pl[k];
-    }
-    *dm = flat_div_mode(c, simple, coarse);
+    const ViewKinds kinds = stage_views(c, lo, hi, c->segpool.p, hv, planes, kEarlyPitch);  // (early_common: no imported pool)
+    *dm = flat_div_mode(c, kinds.simple, kinds.coarse);
     if (hi > lo) GSX_HIP(c, hipMemcpyAsync(c->e_views.as<ViewDesc>() + lo, hv, sizeof(ViewDesc) * (size_t)(hi - lo), hipMemcpyHostToDevice, st));
     GSX_HIP(c, hipMemcpyAsync(c->e_cull.as<double>() + (size_t)block * kEarlyCullDoubles, planes, cbytes, hipMemcpyHostToDevice, st));
     GSX_HIP(c, hipEventRecord(c->early_up_ev, st));
@@ -2252,16 +1354,6 @@ static FusedParams early_params(Ctx* c, int lo, int hi, int block, int stride_by
     p.cull = c->opt_wave_cull ? c->e_cull.as<double>() + (size_t)block * kEarlyCullDoubles : nullptr;
     p.cull_pitch = kEarlyPitch;
     return p;
-}
-
-// Orders c->stream behind whatever the second stream was last asked to do.  Needed wherever an early stage's buffers (ecnt,
-// efv, erec, bcnt) or the pool it reads are touched again: by the last stage that uses its result, and just as much by every
-// path that DROPS the result (fewer views than announced, rewind, a new run) and is about to overwrite those buffers.
-int early_join(Ctx* c) {
-    if (!c->early_inflight) return GSX_OK;
-    GSX_HIP(c, hipStreamWaitEvent(c->stream, c->early_done_ev, 0));
-    c->early_inflight = false;
-    return GSX_OK;
 }
 
 // The context's SECOND stream: the early vote's, and the stream of the first extra frame of gsx_render_views (render.hip borrows
@@ -2281,6 +1373,63 @@ static int early_streams(Ctx* c) {
     if (rc) return rc;
     if (!c->early_maps_ev) GSX_HIP(c, hipEventCreateWithFlags(&c->early_maps_ev, hipEventDisableTiming));
     if (!c->early_done_ev) GSX_HIP(c, hipEventCreateWithFlags(&c->early_done_ev, hipEventDisableTiming));
+    return GSX_OK;
+}
+
+// pool_reserve (handover.hip) is about to free the pool an early stage may still be reading: wait for it, and vote this run in one
+// piece
+int early_pool_moves(Ctx* c) {
+    if (c->early_state == 1 || c->early_batches > 0) {
+        GSX_HIP(c, hipStreamSynchronize(c->stream2));
+        c->early_inflight = false;
+        c->early_state = -1;
+        c->early_batches = 0;
+    }
+    return GSX_OK;
+}
+
+static void early_release(Ctx* c) {  // the second stream and everything the early stages allocate
+    if (c->stream2) {
+        (void)hipStreamSynchronize(c->stream2);
+        (void)hipStreamDestroy(c->stream2);
+        c->stream2 = nullptr;
+    }
+    for (hipEvent_t* e : {&c->early_maps_ev, &c->early_done_ev, &c->early_up_ev}) {
+        if (*e) (void)hipEventDestroy(*e);
+        *e = nullptr;
+    }
+    if (c->h_early) (void)hipHostFree(c->h_early);
+    c->h_early = nullptr;
+    c->h_early_cap = 0;
+    for (DevBuf* b : {&c->ecnt, &c->efv, &c->erec, &c->e_views, &c->e_cull}) b->release();
+    c->early_state = -1;
+}
+
+static int early_batch_stage(Ctx* c) {
+    const int nv = (int)c->views.size();
+    const int S = early_batch_count(c->total_views);
+    const int s = c->early_batches;
+    if (s >= S - 1) return GSX_OK;  // the last batch ends with the last view: vote_finalize launches it
+    int lo, hi;
+    early_batch_bounds(c->total_views, s, lo, hi);
+    if (nv != hi) return GSX_OK;
+    int rc = vote_flush_pending(c);
+    if (rc) return rc;
+    if ((rc = early_streams(c))) return rc;
+    const size_t plane = (size_t)c->bins * (size_t)c->n_pad;
+    GSX_HIP(c, c->bcnt.ensure(plane * S));  // all batches at the first stage: a later one must find the earlier planes in place
+    if ((rc = ensure_tally(c))) return rc;
+    GSX_HIP(c, hipEventRecord(c->early_maps_ev, c->stream));
+    GSX_HIP(c, hipStreamWaitEvent(c->stream2, c->early_maps_ev, 0));
+    int dm = kDivFlat;
+    if ((rc = early_upload(c, lo, hi, s, S, c->stream2, &dm))) return rc;
+    const FusedParams p = early_params(c, lo, hi, s, 1);
+    auto k = with_div<true>(dm, [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
+    if ((rc = launch_walk(c, "vote_early_counts", c->stream2, k, c->n, p, c->bcnt.as<uint8_t>() + plane * s, (long long)c->n_pad))) return rc;
+    GSX_HIP(c, hipEventRecord(c->early_done_ev, c->stream2));
+    c->early_inflight = true;
+    c->early_batches = s + 1;
+    c->early_done = hi;
     return GSX_OK;
 }
 
@@ -2321,32 +1470,20 @@ static int early_vote_stage(Ctx* c) {
     GSX_HIP(c, hipStreamWaitEvent(c->stream2, c->early_maps_ev, 0));
     int dm = kDivFlat;
     if ((rc = early_upload(c, 0, at, 0, 2, c->stream2, &dm))) return rc;
-    if (c->opt_early_replay) {  // record only: the last stage replays it
-        FusedParams p = early_params(c, 0, at, 0, 1);
+    c->early_replayed = c->opt_early_replay != 0;  // (read once early_state says that a stage has started)
+    if (c->early_replayed) {  // record only (no LDS): the last stage replays it
+        const FusedParams p = early_params(c, 0, at, 0, 1);
         auto kr = with_div<true>(dm, [](auto d) { return vote_record_kernel<kUnroll, decltype(d)::value>; });
-        {
-            ProfScope ps(c, "vote_early_record", c->stream2);
-            hipLaunchKernelGGL(kr, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream2, p, p.views, c->erec.as<uint8_t>());
-            GSX_HIP(c, hipGetLastError());
-        }
-        GSX_HIP(c, hipEventRecord(c->early_done_ev, c->stream2));
-        c->early_inflight = true;
-        c->early_done = at;
-        c->early_state = 1;
-        c->early_replayed = true;
-        return GSX_OK;
-    }
-    c->early_replayed = false;
-    FusedParams p = early_params(c, 0, at, 0, 2);
-    const size_t lds = (size_t)kBlock * p.stride_dw * 4;
-    auto k = with_div<true>(dm, [](auto d) { return vote_fused_planes_kernel<kUnroll, uint8_t, decltype(d)::value>; });
-    if ((rc = set_lds(c, k, lds))) return rc;
-    {
-        ProfScope ps(c, "vote_early_planes", c->stream2);
-        // fresh planes, one "slab" per wave (sn = 64: the wave-major layout the last stage streams), global view codes 255 - v
-        hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream2, p, p.views, c->ecnt.as<uint8_t>(), c->efv.as<uint8_t>(),
-                           64LL, 0, 1, 0, c->erec.as<uint8_t>());
+        ProfScope ps(c, "vote_early_record", c->stream2);
+        hipLaunchKernelGGL(kr, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream2, p, p.views, c->erec.as<uint8_t>());
         GSX_HIP(c, hipGetLastError());
+    } else {
+        const FusedParams p = early_params(c, 0, at, 0, 2);
+        auto k = with_div<true>(dm, [](auto d) { return vote_fused_planes_kernel<kUnroll, uint8_t, decltype(d)::value>; });
+        // fresh planes, one "slab" per wave (sn = 64: the wave-major layout the last stage streams), global view codes 255 - v
+        if ((rc = launch_walk(c, "vote_early_planes", c->stream2, k, c->n, p, c->ecnt.as<uint8_t>(), c->efv.as<uint8_t>(), 64LL, 0, 1, 0,
+                              c->erec.as<uint8_t>())))
+            return rc;
     }
     GSX_HIP(c, hipEventRecord(c->early_done_ev, c->stream2));
     c->early_inflight = true;
@@ -2355,38 +1492,9 @@ static int early_vote_stage(Ctx* c) {
     return GSX_OK;
 }
 
-static int early_batch_stage(Ctx* c) {
-    const int nv = (int)c->views.size();
-    const int S = early_batch_count(c->total_views);
-    const int s = c->early_batches;
-    if (s >= S - 1) return GSX_OK;  // the last batch ends with the last view: vote_finalize launches it
-    int lo, hi;
-    early_batch_bounds(c->total_views, s, lo, hi);
-    if (nv != hi) return GSX_OK;
-    int rc = vote_flush_pending(c);
-    if (rc) return rc;
-    if ((rc = early_streams(c))) return rc;
-    const size_t plane = (size_t)c->bins * (size_t)c->n_pad;
-    GSX_HIP(c, c->bcnt.ensure(plane * S));  // all batches at the first stage: a later one must find the earlier planes in place
-    if ((rc = ensure_tally(c))) return rc;
-    GSX_HIP(c, hipEventRecord(c->early_maps_ev, c->stream));
-    GSX_HIP(c, hipStreamWaitEvent(c->stream2, c->early_maps_ev, 0));
-    int dm = kDivFlat;
-    if ((rc = early_upload(c, lo, hi, s, S, c->stream2, &dm))) return rc;
-    FusedParams p = early_params(c, lo, hi, s, 1);
-    const size_t lds = (size_t)kBlock * p.stride_dw * 4;
-    auto k = with_div<true>(dm, [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
-    if ((rc = set_lds(c, k, lds))) return rc;
-    {
-        ProfScope ps(c, "vote_early_counts", c->stream2);
-        hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream2, p, p.views, c->bcnt.as<uint8_t>() + plane * s, (long long)c->n_pad);
-        GSX_HIP(c, hipGetLastError());
-    }
-    GSX_HIP(c, hipEventRecord(c->early_done_ev, c->stream2));
-    c->early_inflight = true;
-    c->early_batches = s + 1;
-    c->early_done = hi;
-    return GSX_OK;
+int vote_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h) {
+    const int rc = vote_view_host(c, cam, seg, seg_dtype, seg_w, seg_h, img_w, img_h);
+    return rc ? rc : early_vote_stage(c);  // enough of the run staged: its first views are voted while the rest is handed over
 }
 
 // vote_finalize behind an early stage: the views [early_done, nv) on top of the early planes -> c->labels
@@ -2396,19 +1504,13 @@ static int early_vote_finish(Ctx* c) {
     if (rc) return rc;
     int dm = kDivFlat;
     if ((rc = early_upload(c, c->early_done, nv, 1, 2, c->stream, &dm))) return rc;
-    GSX_HIP(c, c->labels.ensure(sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1)));
+    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
     if (c->early_replayed) {
         FusedParams pr = early_params(c, c->early_done, nv, 1, 1);
-        const size_t ldsr = (size_t)kBlock * pr.stride_dw * 4;
         auto kr = with_div<true>(dm, [](auto d) { return vote_fused_replay_kernel<kUnroll, decltype(d)::value>; });
-        if ((rc = set_lds(c, kr, ldsr))) return rc;
         if ((rc = early_join(c))) return rc;
         if ((c->opt_ablate >> 4) & 2) pr.nviews = 0;  // timing experiment (tools/early_probe.py)
-        ProfScope ps(c, "vote_fused_replay");
-        hipLaunchKernelGGL(kr, dim3(grid_for(c->n)), dim3(kBlock), ldsr, c->stream, pr, pr.views, c->erec.as<uint8_t>(), c->early_done,
-                           c->labels.as<int>());
-        GSX_HIP(c, hipGetLastError());
-        return GSX_OK;
+        return launch_walk(c, "vote_fused_replay", c->stream, kr, c->n, pr, c->erec.as<uint8_t>(), c->early_done, c->labels.as<int>());
     }
     FusedParams p = early_params(c, c->early_done, nv, 1, 1);
     const size_t lds = (size_t)(kBlock / 64) * ((c->bins + 3) / 4) * 256;  // per wave: [bin][64] bytes, rows padded to a multiple of four
@@ -2439,47 +1541,28 @@ int vote_flush(Ctx* c) {
     int rc = early_join(c);
     if (rc) return rc;
     if ((rc = sync_views(c))) return rc;
-    rc = ensure_planes(c);
-    if (rc) return rc;
+    if ((rc = ensure_planes(c))) return rc;
     const int nv = (int)c->views.size();
     if (c->n <= 0 || c->n_flushed >= nv) {
         c->n_flushed = nv;
         return clear_stale_planes(c);  // nothing will overwrite them
     }
-    FusedParams p{};
-    p.x = c->x.as<float>();
-    p.y = c->y.as<float>();
-    p.z = c->z.as<float>();
-    p.n = c->n;
-    p.pool = c->segpool.as<uint8_t>();
-    p.bins = c->bins;
-    p.xcd_swizzle = c->opt_xcd_swizzle;
-    p.perm = c->sorted ? c->perm.as<uint32_t>() : nullptr;
-    p.stride_dw = odd_dwords(c->bins * 2);
-    p.filt_h = filter_half_width(c);
-    const size_t lds = (size_t)kBlock * p.stride_dw * 4;
+    const FusedParams all = fused_params(c, 2);
     while (c->n_flushed < nv) {
         const int batch = std::min(kMaxBatch, nv - c->n_flushed);
-        p.views = c->d_views.as<ViewDesc>() + c->n_flushed;
+        FusedParams p = all;
+        p.views = all.views + c->n_flushed;
         p.nviews = batch;
-        p.cull = c->opt_wave_cull ? c->d_cull.as<double>() + c->n_flushed : nullptr;
-        p.cull_pitch = c->cull_pitch;
-        p.cull_tally = c->d_cull_tally.as<unsigned long long>();
+        if (p.cull) p.cull = all.cull + c->n_flushed;
         const int view_base = c->first_view + c->n_flushed;
         const int fresh = (c->planes_zero || c->planes_stale) ? 1 : 0;
-        ProfScope ps(c, "vote_fused_planes");
-        if (c->wide) {
-            auto k = with_div(div_mode(c), [](auto d) { return vote_fused_planes_kernel<kUnroll, uint16_t, decltype(d)::value>; });
-            if ((rc = set_lds(c, k, lds))) return rc;
-            hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->cnt.as<uint16_t>(),
-                               c->fv.as<uint16_t>(), (long long)c->sn, view_base, fresh, 0, (uint8_t*)nullptr);
-        } else {
-            auto k = with_div(div_mode(c), [](auto d) { return vote_fused_planes_kernel<kUnroll, uint8_t, decltype(d)::value>; });
-            if ((rc = set_lds(c, k, lds))) return rc;
-            hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->cnt.as<uint8_t>(),
-                               c->fv.as<uint8_t>(), (long long)c->sn, view_base, fresh, c->local_codes ? 1 : 0, (uint8_t*)nullptr);
-        }
-        GSX_HIP(c, hipGetLastError());
+        auto planes = [&](auto t) {  // PT = the planes' element: u16 only when `wide` (then never local codes, vote_begin)
+            using PT = decltype(t);
+            auto k = with_div(div_mode(c), [](auto d) { return vote_fused_planes_kernel<kUnroll, PT, decltype(d)::value>; });
+            return launch_walk(c, "vote_fused_planes", c->stream, k, c->n, p, c->cnt.as<PT>(), c->fv.as<PT>(), (long long)c->sn, view_base,
+                               fresh, c->local_codes ? 1 : 0, (uint8_t*)nullptr);
+        };
+        if ((rc = c->wide ? planes(uint16_t{}) : planes(uint8_t{}))) return rc;
         c->planes_zero = false;
         c->planes_stale = false;
         c->planes_valid = true;
@@ -2494,18 +1577,16 @@ int vote_tiebreak_keys(Ctx* c) {
     int rc = ensure_planes(c);
     if (rc) return rc;
     if ((rc = clear_stale_planes(c))) return rc;
-    GSX_HIP(c, c->keys.ensure(sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1)));
+    GSX_HIP(c, c->keys.ensure(label_bytes(c)));
     GSX_HIP(c, hipMemsetAsync(c->keys.p, 0, sizeof(int) * (size_t)c->n_pad, c->stream));
     if (c->n <= 0) return GSX_OK;
     ProfScope ps(c, "vote_keys");
-    if (c->wide)
-        hipLaunchKernelGGL(vote_keys_kernel<uint16_t>, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream,
-                           c->cnt.as<uint16_t>(), c->fv.as<uint16_t>(), (long long)c->n, (long long)c->sn, c->bins,
-                           c->keys.as<int>());
-    else
-        hipLaunchKernelGGL(vote_keys_kernel<uint8_t>, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream,
-                           c->cnt.as<uint8_t>(), c->fv.as<uint8_t>(), (long long)c->n, (long long)c->sn, c->bins,
-                           c->keys.as<int>());
+    auto keys = [&](auto t) {
+        using PT = decltype(t);
+        hipLaunchKernelGGL(vote_keys_kernel<PT>, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, c->cnt.as<PT>(), c->fv.as<PT>(),
+                           (long long)c->n, (long long)c->sn, c->bins, c->keys.as<int>());
+    };
+    c->wide ? keys(uint16_t{}) : keys(uint8_t{});
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;
 }
@@ -2553,7 +1634,7 @@ static int labels_to_host(Ctx* c, int32_t* labels_out) {
     int* flag = reinterpret_cast<int*>(land + flag_off);
     const char* src = c->labels.as<char>();
     if (n && c->opt_labels_u8) {
-        GSX_HIP(c, c->labels8.ensure((n + 255) / 256 * 256));
+        GSX_HIP(c, c->labels8.ensure(align256(n)));
         ProfScope ps(c, "labels_narrow");
         hipLaunchKernelGGL(labels_narrow_kernel, dim3(grid_for((long long)(n + 3) / 4)), dim3(kBlock), 0, c->stream, c->labels.as<int>(),
                            (long long)n, c->labels8.as<uint8_t>(), c->errflag.as<int>());
@@ -2591,11 +1672,32 @@ static int labels_to_host(Ctx* c, int32_t* labels_out) {
     return GSX_OK;
 }
 
+static void staging_release(Ctx* c) {  // the pinned landing zone of the labels and the descriptor staging of sync_views
+    for (hipEvent_t& e : c->h_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    if (c->h_labels) (void)hipHostFree(c->h_labels);
+    c->h_labels = nullptr;
+    c->h_labels_cap = 0;
+    if (c->h_views_ev) (void)hipEventDestroy(c->h_views_ev);
+    c->h_views_ev = nullptr;
+    if (c->h_views) (void)hipHostFree(c->h_views);
+    c->h_views = nullptr;
+    c->h_views_cap = 0;
+}
+
+void vote_release_host(Ctx* c) {  // gsx_destroy
+    handover_release(c);
+    staging_release(c);
+    early_release(c);
+}
+
 int vote_labels_from_keys(Ctx* c, int32_t* labels_out) {
     if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_labels_from_keys before vote_begin");
     if (c->keys.cap < sizeof(int) * (size_t)c->n_pad) return fail(c, GSX_E_STATE, "vote_labels_from_keys before vote_tiebreak_keys");
     GSX_HIP(c, hipSetDevice(c->device));
-    GSX_HIP(c, c->labels.ensure(sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1)));
+    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
     if (c->n > 0) {
         ProfScope ps(c, "vote_labels");
         hipLaunchKernelGGL(vote_labels_kernel, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, c->keys.as<int>(),
@@ -2604,8 +1706,6 @@ int vote_labels_from_keys(Ctx* c, int32_t* labels_out) {
     }
     return labels_to_host(c, labels_out);
 }
-
-FusedParams fused_params(Ctx* c, int stride_bytes_per_bin);
 
 // A contiguous range of the Gaussians in upload (Morton) order: the whole scene for a single GPU, one rank's slab in
 // exchange protocol v4.
@@ -2628,7 +1728,6 @@ static int labels_one_batch(Ctx* c, const VoteRange& r, const uint32_t* perm, in
     if (r.n <= 0) return GSX_OK;
     FusedParams p = range_params(c, r, 1);
     p.perm = perm ? perm + r.i0 : nullptr;
-    const size_t lds = (size_t)kBlock * p.stride_dw * 4;
     // kernel variants: unroll U in {2,4,8} x division mode
     using K = void (*)(FusedParams, const ViewDesc*, int*);
     const int ui = c->opt_vote_unroll == 2 ? 0 : c->opt_vote_unroll == 4 ? 1 : 2;
@@ -2637,12 +1736,7 @@ static int labels_one_batch(Ctx* c, const VoteRange& r, const uint32_t* perm, in
         static const K by_unroll[3] = {vote_fused_labels_kernel<2, kDiv>, vote_fused_labels_kernel<4, kDiv>, vote_fused_labels_kernel<8, kDiv>};
         return by_unroll[ui];
     });
-    int rc = set_lds(c, k, lds);
-    if (rc) return rc;
-    ProfScope ps(c, "vote_fused_labels");
-    hipLaunchKernelGGL(k, dim3(grid_for(r.n)), dim3(kBlock), lds, c->stream, p, p.views, out);
-    GSX_HIP(c, hipGetLastError());
-    return GSX_OK;
+    return launch_walk(c, "vote_fused_labels", c->stream, k, r.n, p, out);
 }
 
 // More than 255 views on one GPU (the reference's own cameras.json holds 311): the views are cut into S balanced
@@ -2667,10 +1761,7 @@ static int labels_batched(Ctx* c, const VoteRange& r) {
     GSX_HIP(c, c->bcodes.ensure(sizeof(uint16_t) * (size_t)npad * S));
     if (r.n <= 0) return GSX_OK;
     auto k = with_div(div_mode(c), [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
-    FusedParams base = range_params(c, r, 1);
-    const size_t lds = (size_t)kBlock * base.stride_dw * 4;
-    int rc = set_lds(c, k, lds);
-    if (rc) return rc;
+    const FusedParams base = range_params(c, r, 1);
     auto batch = [&](int s, FusedParams& p) {  // views [lo, hi) of batch s: balanced (sizes differ by at most one), or the early cut
         int lo = (int)((long long)nv * s / S), hi = (int)((long long)nv * (s + 1) / S);
         if (early) early_batch_bounds(nv, s, lo, hi);
@@ -2683,10 +1774,9 @@ static int labels_batched(Ctx* c, const VoteRange& r) {
     for (int s = s0; s < S; ++s) {
         FusedParams p;
         batch(s, p);
-        ProfScope ps(c, "vote_fused_counts");
-        hipLaunchKernelGGL(k, dim3(grid_for(r.n)), dim3(kBlock), lds, c->stream, p, p.views, c->bcnt.as<uint8_t>() + plane * s, npad);
+        const int rc = launch_walk(c, "vote_fused_counts", c->stream, k, r.n, p, c->bcnt.as<uint8_t>() + plane * s, npad);
+        if (rc) return rc;
     }
-    GSX_HIP(c, hipGetLastError());
     {
         ProfScope ps(c, "vote_slab_totals");
         hipLaunchKernelGGL(vote_slab_totals_kernel, dim3(grid_for(npad / 4)), dim3(kBlock), 0, c->stream, c->bcnt.as<uint8_t>(), S,
@@ -2716,8 +1806,8 @@ static int labels_for_range(Ctx* c, const VoteRange& r, bool to_sorted) {
     int rc = early_join(c);
     if (rc) return rc;
     if ((rc = sync_views(c))) return rc;
-    GSX_HIP(c, c->keys.ensure(sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1)));
-    GSX_HIP(c, c->labels.ensure(sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1)));
+    GSX_HIP(c, c->keys.ensure(label_bytes(c)));
+    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
     const uint32_t* perm = c->sorted ? c->perm.as<uint32_t>() : nullptr;
     if ((int)c->views.size() <= kMaxBatch)
         return labels_one_batch(c, r, to_sorted ? nullptr : perm, to_sorted ? c->keys.as<int>() : c->labels.as<int>());
@@ -2754,188 +1844,6 @@ int vote_finalize(Ctx* c, int32_t* labels_out) {
     return vote_labels_from_keys(c, labels_out);
 }
 
-// ---- exchange v4 host side: views sharded for the hand-over, Gaussians sharded for the vote ------------------------
-// The packed maps of 200 1080p views are 0.44 GB; the dense vote histogram of 3 M Gaussians is 0.45 GB PER RANK.  So
-// the maps travel (one all-gather), not the votes: afterwards every rank holds every view, votes its own slab of
-// the Gaussians with the single-GPU kernel, and only 4 bytes per Gaussian (the labels) are gathered.  No histogram,
-// no tie-break exchange: a slab sees all views in order, the tie rule is the single-GPU one.
-int vote_export(Ctx* c, int64_t reserve_bytes, void* blobs_out, void** pool_dev, int64_t* pool_bytes) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_export before vote_begin");
-    if (c->pool_base) return fail(c, GSX_E_STATE, "vote_export after vote_import");
-    GSX_HIP(c, hipSetDevice(c->device));
-    if (reserve_bytes < 0) return fail(c, GSX_E_INVALID, "vote_export: negative size");
-    {
-        const int rcf = vote_flush_pending(c);  // the caller is about to read the pool (all-gather)
-        if (rcf) return rcf;
-    }
-    const size_t used = (c->seg_used + 255) / 256 * 256;
-    int rc = pool_reserve(c, std::max<size_t>(std::max<size_t>((size_t)reserve_bytes, used), 256));
-    if (rc) return rc;
-    c->views_dirty = true;  // the pool may have moved
-    static_assert(sizeof(ViewDesc) == GSX_VIEW_BLOB_BYTES, "view blob size is part of the ABI");
-    if (blobs_out && !c->views.empty()) std::memcpy(blobs_out, c->views.data(), sizeof(ViewDesc) * c->views.size());
-    if (pool_dev) *pool_dev = c->segpool.p;
-    if (pool_bytes) *pool_bytes = (int64_t)used;
-    return GSX_OK;
-}
-
-// The imported views replace the rank's own; those are kept aside so that gsx_vote_import_undo can put them back (a protocol
-// that imports optimistically and then learns that a peer's pool was not what the schedule assumed falls back to the plain
-// exchange, which starts from the rank's own views again).
-static void import_commit(Ctx* c, std::vector<ViewDesc>& all, const void* pool_all_dev) {
-    if (!c->pool_base) {  // (a second import on top of an import keeps the first one's saved state)
-        c->own_views.swap(c->views);
-        c->own_first_view = c->first_view;
-    }
-    c->views.swap(all);
-    c->views_dirty = true;
-    c->pool_base = pool_all_dev;
-    c->first_view = 0;
-    c->n_flushed = 0;
-    c->labels_valid = false;
-}
-
-int vote_import_undo(Ctx* c) {
-    if (!c->vote_begun || !c->pool_base) return fail(c, GSX_E_STATE, "vote_import_undo without a gsx_vote_import");
-    c->views.swap(c->own_views);
-    c->own_views.clear();
-    c->first_view = c->own_first_view;
-    c->pool_base = nullptr;
-    c->views_dirty = true;
-    c->n_flushed = 0;
-    c->labels_valid = false;
-    return GSX_OK;
-}
-
-int vote_import(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* part_offsets, const void* blobs,
-                const void* pool_all_dev, int64_t pool_all_bytes) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_import before vote_begin");
-    if (n_parts < 1 || !part_views || !part_offsets || !pool_all_dev || pool_all_bytes < 0)
-        return fail(c, GSX_E_INVALID, "vote_import: bad arguments");
-    long long total = 0;
-    for (int r = 0; r < n_parts; ++r) {
-        if (part_views[r] < 0 || part_offsets[r] < 0) return fail(c, GSX_E_INVALID, "vote_import: negative count or offset");
-        total += part_views[r];
-    }
-    if (total > 65535) return fail(c, GSX_E_RANGE, "vote_import: %lld views exceed 65535", total);
-    if (total > 0 && !blobs) return fail(c, GSX_E_INVALID, "vote_import: blobs is NULL");
-    std::vector<ViewDesc> all((size_t)total);
-    if (total) std::memcpy(all.data(), blobs, sizeof(ViewDesc) * (size_t)total);
-    size_t k = 0;
-    for (int r = 0; r < n_parts; ++r)
-        for (int v = 0; v < part_views[r]; ++v, ++k) {
-            ViewDesc& d = all[k];
-            // the blob comes from another process: check what the kernels rely on before any address is formed from it
-            const MapLayout L = map_layout(d.seg_w, d.seg_h, d.seg_row_bytes != 0, d.coarse_row_bytes != 0);
-            const bool ok = d.seg_w >= 1 && d.seg_h >= 1 && d.seg_w <= 65535 && d.seg_h <= 65535 && d.seg_off >= 0 &&
-                            d.seg_row_bytes == L.strip_bytes && d.coarse_row_bytes == L.cstrip_bytes &&
-                            (!d.coarse_row_bytes || d.coarse_delta == (unsigned)L.coarse_off) &&
-                            (unsigned long long)d.seg_off + (unsigned long long)part_offsets[r] + L.map_bytes <= (unsigned long long)pool_all_bytes;
-            if (!ok) return fail(c, GSX_E_INVALID, "vote_import: descriptor %zu (part %d) is inconsistent with the gathered pool", k, r);
-            d.seg_off += part_offsets[r];
-            d.hw32 = (float)d.half_w;  // (never trusted from the blob: the filter's proof needs exactly these)
-            d.hh32 = (float)d.half_h;
-        }
-    import_commit(c, all, pool_all_dev);
-    return GSX_OK;
-}
-
-// gsx_vote_import without the blobs: every rank of a run holds the whole camera list (cameras.json) and, when all maps of the
-// run share ONE geometry, knows where view k of part r lies in the gathered buffer - part_offsets[r] + k * stride, the stride
-// gsx_vote_view gives a map of that geometry under this context's options (all ranks run the same build with the same
-// options).  So the descriptors are derived here, the same way gsx_vote_view derives them (fill_view_desc + map_layout),
-// and the header exchange of the blobs and its host wait disappear from the protocol.
-static MapLayout uniform_layout(const Ctx* c, int seg_w, int seg_h) {
-    return map_layout(seg_w, seg_h, c->opt_seg_tiled != 0, c->opt_seg_coarse && c->bins <= 255);  // as view_prologue
-}
-// a staged view has the map geometry that (L, image size) derive: everything of a descriptor that does not come from the camera
-static bool same_geometry(const ViewDesc& d, const MapLayout& L, int img_w, int img_h) {
-    return d.seg_w == L.w && d.seg_h == L.h && d.wscale == (double)L.w / (double)img_w && d.hscale == (double)L.h / (double)img_h &&
-           d.seg_row_bytes == L.strip_bytes && d.coarse_row_bytes == L.cstrip_bytes && d.coarse_delta == (unsigned)L.coarse_off;
-}
-
-int vote_map_stride(Ctx* c, int seg_w, int seg_h, int64_t* stride) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_map_stride before vote_begin (the layout depends on the number of classes)");
-    if (!stride) return fail(c, GSX_E_INVALID, "vote_map_stride: NULL argument");
-    if (seg_w < 1 || seg_h < 1 || seg_w > 65535 || seg_h > 65535) return fail(c, GSX_E_INVALID, "vote_map_stride: map %dx%d", seg_w, seg_h);
-    const MapLayout L = uniform_layout(c, seg_w, seg_h);
-    *stride = (int64_t)((L.map_bytes + 255) / 256 * 256);
-    return GSX_OK;
-}
-
-// Are this context's own views exactly views [0, n) of a uniform run as gsx_vote_import_uniform would derive them: n of them, view i
-// from cams[i] with this map and image size, at byte i * stride of the pool?  A rank asks before it votes on a schedule that assumes so.
-int vote_views_match_uniform(Ctx* c, int n, const gsx_camera* cams, int seg_w, int seg_h, int img_w, int img_h, int32_t* match) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_views_match_uniform before vote_begin");
-    if (c->pool_base) return fail(c, GSX_E_STATE, "vote_views_match_uniform after gsx_vote_import: the context holds imported views");
-    if (n < 0 || (n > 0 && !cams) || !match) return fail(c, GSX_E_INVALID, "vote_views_match_uniform: bad arguments");
-    if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1 || seg_w > 65535 || seg_h > 65535)
-        return fail(c, GSX_E_INVALID, "vote_views_match_uniform: map %dx%d, image %dx%d", seg_w, seg_h, img_w, img_h);
-    const MapLayout L = uniform_layout(c, seg_w, seg_h);
-    const size_t stride = (L.map_bytes + 255) / 256 * 256;
-    *match = 0;
-    if ((size_t)n != c->views.size()) return GSX_OK;
-    for (int i = 0; i < n; ++i) {
-        ViewDesc d;
-        fill_view_desc(d, &cams[i], L.w, L.h, img_w, img_h);
-        d.seg_off = (long long)((size_t)i * stride);
-        d.seg_row_bytes = L.strip_bytes;
-        d.coarse_row_bytes = L.cstrip_bytes;
-        d.coarse_delta = (unsigned)L.coarse_off;
-        if (std::memcmp(&d, &c->views[(size_t)i], sizeof d) != 0) return GSX_OK;  // (fill_view_desc zeroes the padding)
-    }
-    *match = 1;
-    return GSX_OK;
-}
-
-int vote_import_uniform(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* part_offsets, const gsx_camera* cams,
-                        int seg_w, int seg_h, int img_w, int img_h, const void* pool_all_dev, int64_t pool_all_bytes) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_import_uniform before vote_begin");
-    if (n_parts < 1 || !part_views || !part_offsets || !pool_all_dev || pool_all_bytes < 0)
-        return fail(c, GSX_E_INVALID, "vote_import_uniform: bad arguments");
-    if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1 || seg_w > 65535 || seg_h > 65535)
-        return fail(c, GSX_E_INVALID, "vote_import_uniform: map %dx%d, image %dx%d", seg_w, seg_h, img_w, img_h);
-    long long total = 0;
-    for (int r = 0; r < n_parts; ++r) {
-        if (part_views[r] < 0 || part_offsets[r] < 0) return fail(c, GSX_E_INVALID, "vote_import_uniform: negative count or offset");
-        total += part_views[r];
-    }
-    if (total > 65535) return fail(c, GSX_E_RANGE, "vote_import_uniform: %lld views exceed 65535", total);
-    if (total > 0 && !cams) return fail(c, GSX_E_INVALID, "vote_import_uniform: cams is NULL");
-    const MapLayout L = uniform_layout(c, seg_w, seg_h);
-    const size_t stride = (L.map_bytes + 255) / 256 * 256;
-    // the caller laid the parts out with a stride of its own: parts that overlap at THIS stride were sized for another geometry
-    std::vector<std::pair<unsigned long long, unsigned long long>> spans;  // (first byte, bytes) of the parts that hold views
-    for (int r = 0; r < n_parts; ++r)
-        if (part_views[r] > 0) spans.emplace_back((unsigned long long)part_offsets[r], (unsigned long long)part_views[r] * stride);
-    std::sort(spans.begin(), spans.end());
-    for (size_t s = 0; s + 1 < spans.size(); ++s)
-        if (spans[s].first + spans[s].second > spans[s + 1].first)
-            return fail(c, GSX_E_INVALID, "vote_import_uniform: the part offsets leave less than %llu bytes a view, the stride of a %dx%d map",
-                        (unsigned long long)stride, seg_w, seg_h);
-    // what this context staged itself is part of the run: its geometry must be the one the descriptors are derived for
-    for (const ViewDesc& o : c->pool_base ? c->own_views : c->views)
-        if (!same_geometry(o, L, img_w, img_h))
-            return fail(c, GSX_E_INVALID, "vote_import_uniform: map %dx%d / image %dx%d, but gsx_vote_view staged a %dx%d map (scales %g, %g)",
-                        seg_w, seg_h, img_w, img_h, o.seg_w, o.seg_h, o.wscale, o.hscale);
-    std::vector<ViewDesc> all((size_t)total);
-    size_t k = 0;
-    for (int r = 0; r < n_parts; ++r)
-        for (int v = 0; v < part_views[r]; ++v, ++k) {
-            const unsigned long long off = (unsigned long long)part_offsets[r] + (unsigned long long)v * stride;
-            if (off + L.map_bytes > (unsigned long long)pool_all_bytes)
-                return fail(c, GSX_E_INVALID, "vote_import_uniform: view %zu (part %d) lies outside the gathered pool", k, r);
-            ViewDesc& d = all[k];
-            fill_view_desc(d, &cams[k], L.w, L.h, img_w, img_h);
-            d.seg_off = (long long)off;
-            d.seg_row_bytes = L.strip_bytes;
-            d.coarse_row_bytes = L.cstrip_bytes;
-            d.coarse_delta = (unsigned)L.coarse_off;
-        }
-    import_commit(c, all, pool_all_dev);
-    return GSX_OK;
-}
-
 int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size) {
     if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_slab_labels before vote_begin");
     if (slabs < 1 || slab < 0 || slab >= slabs) return fail(c, GSX_E_INVALID, "vote_slab_labels: slab %d of %d", slab, slabs);
@@ -2952,26 +1860,6 @@ int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size) {
 }
 
 // ---- exchange v3 host side ------------------------------------------------------------------------------------
-FusedParams fused_params(Ctx* c, int stride_bytes_per_bin) {
-    FusedParams p{};
-    p.x = c->x.as<float>();
-    p.y = c->y.as<float>();
-    p.z = c->z.as<float>();
-    p.n = c->n;
-    p.views = c->d_views.as<ViewDesc>();
-    p.nviews = (int)c->views.size();
-    p.pool = c->segpool.as<uint8_t>();
-    p.bins = c->bins;
-    p.xcd_swizzle = c->opt_xcd_swizzle;
-    p.perm = c->sorted ? c->perm.as<uint32_t>() : nullptr;
-    p.stride_dw = odd_dwords(c->bins * stride_bytes_per_bin);
-    p.cull = c->opt_wave_cull ? c->d_cull.as<double>() : nullptr;
-    p.cull_pitch = c->cull_pitch;
-    p.cull_tally = c->d_cull_tally.as<unsigned long long>();
-    p.filt_h = filter_half_width(c);
-    return p;
-}
-
 int vote_flush_counts(Ctx* c) {
     if (!c->vote_begun || !c->local_codes) return fail(c, GSX_E_STATE, "vote_flush_counts needs vote_begin with the 'exchange_local' option");
     GSX_HIP(c, hipSetDevice(c->device));
@@ -2987,14 +1875,8 @@ int vote_flush_counts(Ctx* c) {
         c->counts_n = c->n, c->counts_npad = c->n_pad, c->counts_sn = c->sn, c->counts_bins = c->bins;
     }
     if (c->n > 0) {
-        FusedParams p = fused_params(c, 1);
-        const size_t lds = (size_t)kBlock * p.stride_dw * 4;
         auto k = with_div(div_mode(c), [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
-        if ((rc = set_lds(c, k, lds))) return rc;
-        ProfScope ps(c, "vote_fused_counts");
-        hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->cnt.as<uint8_t>(),
-                           (long long)c->sn);
-        GSX_HIP(c, hipGetLastError());
+        if ((rc = launch_walk(c, "vote_fused_counts", c->stream, k, c->n, fused_params(c, 1), c->cnt.as<uint8_t>(), (long long)c->sn))) return rc;
     }
     c->n_flushed = (int)c->views.size();
     return GSX_OK;
@@ -3060,7 +1942,7 @@ int vote_labels_from_sorted(Ctx* c, const void* sorted_labels_dev, int32_t* labe
     if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_labels_from_sorted before vote_begin");
     if (!sorted_labels_dev) return fail(c, GSX_E_INVALID, "vote_labels_from_sorted: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
-    GSX_HIP(c, c->labels.ensure(sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1)));
+    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
     if (c->n > 0) {
         ProfScope ps(c, "vote_labels");
         hipLaunchKernelGGL(unpermute_labels_kernel, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream,
@@ -3073,10 +1955,7 @@ int vote_labels_from_sorted(Ctx* c, const void* sorted_labels_dev, int32_t* labe
 
 int vote_debug_planes(Ctx* c, uint16_t* counts_out, uint16_t* first_out) {
     if (!c->vote_begun || !(c->planes_valid || c->planes_zero || c->planes_stale)) return fail(c, GSX_E_STATE, "vote_debug_planes: no planes");
-    {
-        const int rc0 = clear_stale_planes(c);
-        if (rc0) return rc0;
-    }
+    if (const int rc = clear_stale_planes(c)) return rc;
     if (!counts_out || !first_out) return fail(c, GSX_E_INVALID, "vote_debug_planes: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
     const size_t esz = c->wide ? 2 : 1;

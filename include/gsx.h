@@ -110,7 +110,7 @@ int gsx_synchronize(gsx_ctx* ctx);
  *                               v_fma_f32) with a proven error bound: a wave whose lanes are all farther than the bound from
  *                               every pixel boundary takes floor() of the filter's result, any other wave the exact
  *                               divisions for that view (about one wave and view in ten at 1080p).  Bit-identical by
- *                               construction (csrc/vote.hip: project_filtered; gsx_debug_filter_check)
+ *                               construction (csrc/vote_device.hpp: project_filtered; gsx_debug_filter_check)
  *   "host_compact" (default 1)  host maps (gsx_vote_view) cross PCIe as their coarse level plus the 16-byte blocks of the
  *                               mixed 4x4 cells only, and a kernel behind the DMA rebuilds the pool form (the link, not
  *                               the host pass, is what the hand-over of 200 1080p maps waits for); 0 = the pool form

@@ -420,7 +420,7 @@ class NumpySparseShard(NumpySlabShard):
 # ---- exchange protocol v4 (dist.exchange_labels_gather) ----------------------------------------------------------------
 def pack_map_numpy(seg, n_classes):
     """The library's on-device form of one segmentation map, restated in numpy (layout documented in
-    csrc/host_pack.hpp / vote.hip): u8 bins (label + 1) in strips of 16 pixel columns (16 B per row, rows padded to
+    csrc/host_pack.hpp / handover.hip): u8 bins (label + 1) in strips of 16 pixel columns (16 B per row, rows padded to
     a multiple of 8), then at a 256-B aligned offset the 4x4-coarsened level in the same strip layout (a cell = the bin
     its 16 pixels share, 255 where they differ or the cell sticks out of the map).  -> (bytes, coarse_off)."""
     seg = np.asarray(seg)

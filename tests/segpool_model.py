@@ -1,5 +1,5 @@
 """The pool form of one segmentation map, every byte of its stride, restated in numpy for all four layouts of map_layout()
-(csrc/host_pack.cpp), written from the layout comments of csrc/host_pack.hpp and csrc/vote.hip alone: it neither calls
+(csrc/host_pack.cpp), written from the layout comments of csrc/host_pack.hpp and csrc/handover.hip alone: it neither calls
 oracle.pack_map_numpy nor the host packer, and it builds the strips by reshaping padded planes where those scatter by index.
 
 A map of w x h pixels holds, from its 256-byte aligned start:

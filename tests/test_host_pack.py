@@ -1,5 +1,5 @@
-"""Host side of gsx_vote_view (no GPU): the packed form of a segmentation map that the worker threads write into the
-pinned staging ring — u8 bins (label + 1) in strips of 16 pixel columns plus the 4x4-coarsened level — against a
+"""Host side of gsx_vote_view (no GPU; csrc/handover.hip hands over what csrc/host_pack.cpp packs): the packed
+form of a segmentation map that the worker threads write into the pinned staging ring — u8 bins (label + 1) in strips of 16 pixel columns plus the 4x4-coarsened level — against a
 numpy model of the layout the vote kernels read (csrc/vote.hip gather_chunk), and the label range check
 (the reference indexes its vote dict with whatever the map holds, dls.py:288-295; the library supports
 -1 .. n_classes-1 and must refuse anything else loudly)."""

@@ -1,4 +1,4 @@
-"""GPU: the device map pack (csrc/vote.hip seg_pack_fused_kernel: gsx_vote_views_device, vote_view with a device tensor, the
+"""GPU: the device map pack (csrc/handover.hip seg_pack_fused_kernel: gsx_vote_views_device, vote_view with a device tensor, the
 "host_pack" = 0 hand-over) pinned byte for byte to the numpy model of the pool form (tests/segpool_model.py), padding included.
 
 Every run under test starts on a pool that was filled with 0xA5 first (the pool is one allocation reused from run to run, so what
