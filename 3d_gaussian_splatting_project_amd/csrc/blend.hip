@@ -455,13 +455,14 @@ __global__ __launch_bounds__(kBlend4Threads) void blend4_kernel(const int2* __re
 
 int launch_blend(Ctx* c, const uint32_t* vals, int W, int H, int tiles_x, int tiles_y, const int* dropped_dev,
                  unsigned long long* consumed_dev, uint8_t* sat, int first_phase, int last_phase) {
+    RenderFrame& f = c->frame;
     const int ntiles = tiles_x * tiles_y;
     const uint32_t* order = nullptr;
-    if (c->opt_tile_lpt && !c->r_bin32 && c->r_P > 0 && ntiles > 256) {  // (tile_order_key_kernel reads per-tile ranges)
-        GSX_HIP(c, c->r_tile_order.ensure(sizeof(uint32_t) * 4 * (size_t)ntiles));
-        uint32_t* k0 = c->r_tile_order.as<uint32_t>();
+    if (c->ropt.tile_lpt && !f.bin32 && f.P > 0 && ntiles > 256) {  // (tile_order_key_kernel reads per-tile ranges)
+        GSX_HIP(c, f.tile_order.ensure(sizeof(uint32_t) * 4 * (size_t)ntiles));
+        uint32_t* k0 = f.tile_order.as<uint32_t>();
         uint32_t *v0 = k0 + ntiles, *k1 = v0 + ntiles, *v1 = k1 + ntiles;
-        hipLaunchKernelGGL(tile_order_key_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, c->stream, c->r_ranges.as<int2>(),
+        hipLaunchKernelGGL(tile_order_key_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, c->stream, f.ranges.as<int2>(),
                            ntiles, k0, v0);
         int where = 0;
         int rc = radix_sort_pairs(c, k0, v0, k1, v1, ntiles, 6, &where);
@@ -469,26 +470,26 @@ int launch_blend(Ctx* c, const uint32_t* vals, int W, int H, int tiles_x, int ti
         order = where ? v1 : v0;
     }
     ProfScope ps(c, "render_blend");
-    if (c->opt_blend_pk2 == 2) {
+    if (c->ropt.blend_pk2 == 2) {
         const int bins_x = (tiles_x + 1) / 2, bins_y = (tiles_y + 1) / 2;
-        if (c->r_bin32)
-            hipLaunchKernelGGL(blend4_kernel<true>, dim3(4 * bins_x * bins_y), dim3(kBlend4Threads), 0, c->stream, c->r_ranges.as<int2>(),
-                               (const uint32_t*)nullptr, vals, c->r_rec.as<float4>(), W, H, tiles_x, dropped_dev,
-                               c->r_pre.as<int>(), (long long)c->rn, consumed_dev, c->r_image.as<float4>(), sat, first_phase, last_phase,
+        if (f.bin32)
+            hipLaunchKernelGGL(blend4_kernel<true>, dim3(4 * bins_x * bins_y), dim3(kBlend4Threads), 0, c->stream, f.ranges.as<int2>(),
+                               (const uint32_t*)nullptr, vals, f.cur->rec.as<float4>(), W, H, tiles_x, dropped_dev,
+                               f.cur->pre.as<int>(), (long long)c->scene.rn, consumed_dev, f.image.as<float4>(), sat, first_phase, last_phase,
                                bins_x, tiles_y);
         else
-            hipLaunchKernelGGL(blend4_kernel<false>, dim3(ntiles), dim3(kBlend4Threads), 0, c->stream, c->r_ranges.as<int2>(), order, vals,
-                               c->r_rec.as<float4>(), W, H, tiles_x, dropped_dev,
-                               c->r_pre.as<int>(), (long long)c->rn, consumed_dev, c->r_image.as<float4>(), sat, first_phase, last_phase,
+            hipLaunchKernelGGL(blend4_kernel<false>, dim3(ntiles), dim3(kBlend4Threads), 0, c->stream, f.ranges.as<int2>(), order, vals,
+                               f.cur->rec.as<float4>(), W, H, tiles_x, dropped_dev,
+                               f.cur->pre.as<int>(), (long long)c->scene.rn, consumed_dev, f.image.as<float4>(), sat, first_phase, last_phase,
                                bins_x, tiles_y);
-    } else if (c->opt_blend_pk2) {
-        hipLaunchKernelGGL(blend2_kernel, dim3(ntiles), dim3(kBlend2Threads), 0, c->stream, c->r_ranges.as<int2>(), order, vals,
-                           c->r_rec.as<float4>(), W, H, tiles_x, dropped_dev,
-                           c->r_pre.as<int>(), (long long)c->rn, consumed_dev, c->r_image.as<float4>(), sat, first_phase, last_phase);
+    } else if (c->ropt.blend_pk2) {
+        hipLaunchKernelGGL(blend2_kernel, dim3(ntiles), dim3(kBlend2Threads), 0, c->stream, f.ranges.as<int2>(), order, vals,
+                           f.cur->rec.as<float4>(), W, H, tiles_x, dropped_dev,
+                           f.cur->pre.as<int>(), (long long)c->scene.rn, consumed_dev, f.image.as<float4>(), sat, first_phase, last_phase);
     } else {
-        hipLaunchKernelGGL(blend_kernel, dim3(ntiles), dim3(kBlendThreads), 0, c->stream, c->r_ranges.as<int2>(), order, vals,
-                           c->r_rec.as<float4>(), W, H, tiles_x, dropped_dev,
-                           c->r_pre.as<int>(), (long long)c->rn, consumed_dev, c->r_image.as<float4>(), sat, first_phase, last_phase);
+        hipLaunchKernelGGL(blend_kernel, dim3(ntiles), dim3(kBlendThreads), 0, c->stream, f.ranges.as<int2>(), order, vals,
+                           f.cur->rec.as<float4>(), W, H, tiles_x, dropped_dev,
+                           f.cur->pre.as<int>(), (long long)c->scene.rn, consumed_dev, f.image.as<float4>(), sat, first_phase, last_phase);
     }
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;

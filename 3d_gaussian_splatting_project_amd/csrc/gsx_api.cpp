@@ -137,14 +137,9 @@ void gsx_destroy(gsx_ctx* ctx) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);  // an early vote stage may still read the buffers freed below
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2);  // an early vote stage may still read the buffers ~Ctx frees
     gsx::prof_drain(c);
     for (auto ev : c->event_pool) (void)hipEventDestroy(ev);
-    for (gsx::DevBuf* b : {&c->x, &c->y, &c->z, &c->perm, &c->sort_hist, &c->d_views, &c->d_cull, &c->d_cull_tally, &c->segpool, &c->errflag,
-                           &c->cnt, &c->fv, &c->bcnt, &c->bcodes, &c->keys, &c->labels, &c->cand, &c->codes, &c->r_order, &c->r_buffer, &c->r_tex, &c->r_sh, &c->r_fdc, &c->r_shc, &c->r_image,
-                           &c->r_ranges, &c->r_small, &c->r_scan, &c->r_depth, &c->r_bucket, &c->r_rect, &c->r_count,
-                           &c->r_offset, &c->r_rec, &c->r_keys0, &c->r_keys1, &c->r_vals0, &c->r_vals1, &c->r_tile_order, &c->r_sat, &c->r_d0, &c->r_d1, &c->r_d2, &c->r_d3, &c->r_rects})
-        b->release();
     gsx::render_release_twin(c);
     gsx::vote_release_host(c);
     gsx::iou_release(c);
@@ -174,28 +169,28 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
         c->opt_xcd_swizzle = (int)value;
     }
     else if (k == "seg_tiled") c->opt_seg_tiled = value != 0;
-    else if (k == "tile_lpt") c->opt_tile_lpt = value != 0;
-    else if (k == "exact_cull") c->opt_exact_cull = value != 0;
+    else if (k == "tile_lpt") c->ropt.tile_lpt = value != 0;
+    else if (k == "exact_cull") c->ropt.exact_cull = value != 0;
     else if (k == "render_phases") {
         if (value < 1 || value > 8) return gsx::fail(c, GSX_E_INVALID, "set_option: render_phases must be in [1,8]");
-        c->opt_render_phases = (int)value;
+        c->ropt.phases = (int)value;
     } else if (k == "render_phase_ratio") {
         if (value < 2 || value > 64) return gsx::fail(c, GSX_E_INVALID, "set_option: render_phase_ratio must be in [2,64]");
-        c->opt_render_phase_ratio = (int)value;
+        c->ropt.phase_ratio = (int)value;
     }
-    else if (k == "render_multi_pre") c->opt_render_multi_pre = value != 0;
-    else if (k == "render_bin32") c->opt_render_bin32 = value != 0;
-    else if (k == "render_compact") c->opt_render_compact = value != 0;
-    else if (k == "render_wide_sort") c->opt_render_wide_sort = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
+    else if (k == "render_multi_pre") c->ropt.multi_pre = value != 0;
+    else if (k == "render_bin32") c->ropt.bin32 = value != 0;
+    else if (k == "render_compact") c->ropt.compact = value != 0;
+    else if (k == "render_wide_sort") c->ropt.wide_sort = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
     else if (k == "render_share_stream") {
-        if ((value != 0) != (c->opt_render_share_stream != 0)) gsx::render_release_twin(c);  // the extra frames' streams are made anew
-        c->opt_render_share_stream = value != 0;
+        if ((value != 0) != (c->ropt.share_stream != 0)) gsx::render_release_twin(c);  // the extra frames' streams are made anew
+        c->ropt.share_stream = value != 0;
     }
     else if (k == "render_frames") {
-        if (value < 1 || value > Ctx::kMaxFrames) return gsx::fail(c, GSX_E_INVALID, "set_option: render_frames must be in [1,%d]", (int)Ctx::kMaxFrames);
-        c->opt_render_frames = (int)value;
+        if (value < 1 || value > gsx::kMaxFrames) return gsx::fail(c, GSX_E_INVALID, "set_option: render_frames must be in [1,%d]", (int)gsx::kMaxFrames);
+        c->ropt.frames = (int)value;
     }
-    else if (k == "blend_pk2") c->opt_blend_pk2 = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
+    else if (k == "blend_pk2") c->ropt.blend_pk2 = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
     else if (k == "exchange_slabs") {
         if (value < 1 || value > 64) return gsx::fail(c, GSX_E_INVALID, "set_option: exchange_slabs must be in [1,64]");
         c->opt_slabs = (int)value;
@@ -555,11 +550,11 @@ int gsx_render_set_edits(gsx_ctx* ctx, const gsx_render_edits* edits) {
 }
 int64_t gsx_render_num_hidden(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return c ? c->r_edit_hidden_n : 0;
+    return c ? c->scene.edit_hidden_n : 0;
 }
 int64_t gsx_num_splats(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return c ? c->rn : 0;
+    return c ? c->scene.rn : 0;
 }
 int gsx_render_view(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, float* rgba_out) {
     CTX_OR_FAIL(ctx);
@@ -571,15 +566,15 @@ int gsx_render_views(gsx_ctx* ctx, int32_t n, const gsx_camera* cams, int32_t wi
 }
 void* gsx_render_image_device(gsx_ctx* ctx) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    return c ? c->r_image.p : nullptr;
+    return c ? c->frame.image.p : nullptr;
 }
 int64_t gsx_render_num_pairs(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return c ? (int64_t)c->r_P : 0;
+    return c ? (int64_t)c->frame.P : 0;
 }
 int64_t gsx_render_num_pairs_consumed(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return c ? (int64_t)c->r_consumed : 0;
+    return c ? (int64_t)c->frame.consumed : 0;
 }
 int gsx_hit_test(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, double x, double y,
                  int32_t* label_out, int64_t* index_out) {
@@ -936,7 +931,7 @@ int gsx_debug_bin(gsx_ctx* ctx, int64_t n, const uint32_t* tile_rect, const floa
     GSX_HIP(c, hipMemsetAsync(dvals.p, 0xff, pb, c->stream));
     GSX_HIP(c, hipMemsetAsync(dsmall.p, 0xff, 16, c->stream));
     GSX_HIP(c, hipMemcpyAsync(dsmall.p, &nvis_host, 8, hipMemcpyHostToDevice, c->stream));
-    gsx::DebugBinArgs a;
+    gsx::BinPhaseArgs a;
     a.nvis_dev = dsmall.as<unsigned long long>();
     a.div0 = div0;
     a.div1 = div1;

@@ -161,6 +161,76 @@ struct HandOver {
     }
 };
 
+// ---- state of the rasterizer: plain data, three members of Ctx ------------------------------------------------------------
+// What exists once per scene: written by the upload (render_scene.hip) or by gsx_render_set_edits, only read by a frame.
+struct RenderScene {
+    int64_t rn = 0;             // splats uploaded
+    DevBuf order, buffer, tex;  // importance permutation, .splat rows, texel pairs
+    DevBuf fdc, shc;            // f_dc (source order); SH coefficients coef[k][c][i] (importance order)
+    bool sh_on = false;
+    int sh_deg = 0;
+    // label edits (gsx_render_set_edits): the exact int32 labels in importance order (kept from the upload), and per state a
+    // 16-bit code per splat, the tables (render_device.hpp: EditTables) and the sorted hidden labels
+    DevBuf labels, edit_code, edit_tab, edit_hidden;
+    bool edits_on = false;
+    int64_t edit_hidden_n = 0;  // splats the state hides
+    // a twin's view of its parent's scene: EVERY buffer aliased, every scalar copied (o must outlive this)
+    void alias(const RenderScene& o) {
+        rn = o.rn;
+        order.alias(o.order), buffer.alias(o.buffer), tex.alias(o.tex);
+        fdc.alias(o.fdc), shc.alias(o.shc);
+        sh_on = o.sh_on, sh_deg = o.sh_deg;
+        labels.alias(o.labels), edit_code.alias(o.edit_code), edit_tab.alias(o.edit_tab), edit_hidden.alias(o.edit_hidden);
+        edits_on = o.edits_on, edit_hidden_n = o.edit_hidden_n;
+    }
+};
+
+// The rasterizer's options (gsx_set_option); a twin gets them with `=`.
+struct RenderOpts {
+    int blend_pk2 = 2;     // 0 = one pixel per thread, 1 = two (packed fp32), 2 = four, one wave per tile (default since round 3)
+    int exact_cull = 0;    // keep only the tiles the splat's ellipse really reaches (pairs -23 %; the test costs more than the sort saves)
+    int tile_lpt = 0;      // launch the tiles with the longest lists first (blend -3 %, but net 0)
+    int phases = 2;        // depth phases per frame (1 = bin and sort every pair at once)
+    int phase_ratio = 6;   // phase p ends at nvis / ratio^(K-1-p) splats (front to back; nvis = the splats with a rectangle in the view; 4 until the level-1 sort left the others out)
+    int bin32 = 1;         // bin, sort and range the splats by 32x32-pixel BINS (2x2 tiles); a pair carries the mask of the bin's tiles
+                           // the splat's rectangle covers (one-wave blend kernel, no exact_cull, < 2^28 splats; else 16x16)
+    int compact = 1;       // the level-1 sort leaves out the splats without a rectangle in the view (its first pass is the partition)
+    int wide_sort = 1;     // the pair sorts in ONE pass when the list index fits 11 bits (sort.hip: radix_sort_values_wide; the ranges come with it):
+                           // 0 never, 1 for a frame on its own (gsx_render_view), 2 also with several frames in flight
+    int frames = 4;        // frames in flight in gsx_render_views (1 .. kMaxFrames): 935 / 1252 / 1359 / 1396 views/s with 1 / 2 / 3 / 4
+    int multi_pre = 1;     // gsx_render_views: one pre pass per group of frames in flight (0: every frame its own)
+    int share_stream = 1;  // gsx_render_views: the first extra frame runs on the context's second stream instead of one more stream
+};
+static constexpr int kMaxFrames = 6;
+
+// gsx_render_views with several frames in flight: ONE pre pass per group of frames (pre_multi_kernel) writes the per-view
+// records of all of them; a frame's records live in one of three rotating sets so that the pass for group g + 1 can run
+// while the frames of group g (and stragglers of g - 1) still read theirs
+struct PreSet {
+    DevBuf depth, rect, rec;
+    DevBuf pre;  // int[4]: min depth, max depth, splat 0's tile rectangle (written by the pre pass)
+};
+static constexpr int kPreSets = 3;
+
+// What one frame in flight owns (the context's own frame and every twin's).
+struct RenderFrame {
+    DevBuf image;                      // float4[H][W] of the last view
+    DevBuf ranges, small, scan, bucket, count, offset;
+    DevBuf d0, d1, d2, d3;             // level-1 sort ping-pong (bucket, splat)
+    DevBuf keys0, keys1, vals0, vals1;
+    DevBuf rects;                      // the tile rectangles of a phase's splats in the phase's order (bin COUNT -> EMIT)
+    DevBuf sat;                        // u8 per tile: every pixel is opaque (1 - alpha < 1e-5): later depth phases skip it
+    DevBuf tile_order;                 // blend launch order (longest list first)
+    PreSet sets[kPreSets];
+    PreSet* cur = nullptr;             // the set the frame being rendered reads (set by render_view: sets[0] for a frame on its own)
+    size_t pair_cap = 0;               // capacity (pairs) of keys* / vals*: grown when a phase overflows it, the frame is redone
+    unsigned long long P = 0;          // (tile, splat) pairs of the last view (all phases)
+    unsigned long long consumed = 0;   // pairs the blend kernel actually staged (early-out leaves the rest unread)
+    int bin32 = 0;                     // the frame being rendered uses bins (set by render_view, read by launch_blend)
+    bool in_flight = false;            // this context renders one of several frames in flight (set by render_views for the call)
+    int pre_ext = -1;                  // >= 0: this frame's pre pass has been run for it into sets[pre_ext] (render_view skips its own)
+};
+
 struct Ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -180,9 +250,6 @@ struct Ctx {
     int opt_vote_unroll = 8;   // views whose seg gathers are in flight together: 1, 2, 4 or 8
     int opt_slabs = 1;         // see Ctx::slabs (takes effect at the next vote_begin)
     int opt_local_codes = 0;   // see Ctx::local_codes
-    int opt_blend_pk2 = 2;     // rasterizer: 0 = one pixel per thread, 1 = two (packed fp32), 2 = four, one wave per tile (default since round 3)
-    int opt_exact_cull = 0;    // rasterizer: keep only the tiles the splat's ellipse really reaches (pairs -23 %; the test costs more than the sort saves)
-    int opt_tile_lpt = 0;      // rasterizer: launch the tiles with the longest lists first (blend -3 %, but net 0)
     int opt_seg_tiled = 1;     // store seg maps as 16x8-pixel tiles of 128 B
     int opt_batched_counts = 1; // > 255 views on one GPU: per-batch count planes + sparse tie pass instead of 16-bit planes
     int opt_seg_coarse = 1;    // keep a 4x4-coarsened level of every tiled map (views staged after the call)
@@ -255,7 +322,6 @@ struct Ctx {
     int early_batches = 0;       // > 255 announced views: batches of labels_batched() whose count kernels already ran on stream2
     hipStream_t stream2 = nullptr;
     bool stream_borrowed = false; // (a twin of gsx_render_views) `stream` is the parent context's second stream: not this context's to destroy
-    int opt_render_share_stream = 1;  // gsx_render_views: the first extra frame runs on the context's second stream instead of one more stream
     bool early_inflight = false; // early_done_ev was recorded on stream2 and c->stream has not been ordered behind it yet (early_join)
     hipEvent_t early_maps_ev = nullptr, early_done_ev = nullptr, early_up_ev = nullptr;
     DevBuf ecnt, efv;            // u8 [wave][bin][64]: counts / first-view codes of the early views
@@ -264,57 +330,17 @@ struct Ctx {
     void* h_early = nullptr;     // pinned staging of both
     size_t h_early_cap = 0;
 
-    // rasterizer (render.hip / blend.hip)
-    int64_t rn = 0;                      // splats uploaded
-    DevBuf r_order, r_buffer, r_tex;     // importance permutation, .splat rows, texel pairs
-    DevBuf r_sh;                         // per-view SH colour (n x 3 f32)
-    DevBuf r_fdc, r_shc;                 // f_dc (source order); SH coefficients coef[k][i][3] (importance order)
-    bool r_sh_valid = false, r_sh_on = false;
-    int r_sh_deg = 0;
-    // label edits (gsx_render_set_edits): the exact int32 labels in importance order (kept from the upload), and per state a
-    // 16-bit code per splat, the tables (render.hip: EditTables) and the sorted hidden labels
-    DevBuf r_labels, r_edit_code, r_edit_tab, r_edit_hidden;
-    bool r_edits_on = false;
-    int64_t r_edit_hidden_n = 0;         // splats the state hides
-    DevBuf r_image;                      // float4[H][W] of the last view
-    int r_W = 0, r_H = 0;
-    DevBuf r_ranges, r_small, r_scan;
-    DevBuf r_depth, r_bucket, r_rect, r_count, r_offset, r_rec;
-    DevBuf r_pre;                        // int[4]: min depth, max depth, splat 0's tile rectangle (written by the pre pass)
-    // gsx_render_views with several frames in flight: ONE pre pass per group of frames (pre_multi_kernel) writes the per-view
-    // records of all of them; a frame's records live in one of three rotating sets so that the pass for group g + 1 can run
-    // while the frames of group g (and stragglers of g - 1) still read theirs
-    struct PreSet {
-        DevBuf depth, rect, rec, pre;
-    };
-    static constexpr int kPreSets = 3;
-    PreSet r_sets[kPreSets];
+    // rasterizer (render_scene.hip / render_pre.hip / render.hip / blend.hip)
+    RenderScene scene;
+    RenderOpts ropt;
+    RenderFrame frame;
+    // gsx_render_views: further streams + per-frame buffers.  A twin is a whole Ctx because sort.hip, ProfScope and fail take
+    // one; what it uses of it is stream, sort_hist, err, scene (aliases of this context's), ropt (a copy) and frame
+    Ctx* twins[kMaxFrames - 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    // ... with ONE pre pass per group of frames (pre_multi_kernel), issued by this context for all of them
     DevBuf r_pre_args;                   // pre_multi_kernel's per-view arguments, one slot per record set
     std::vector<unsigned long long> r_pre_args_host;  // ... and their host copies (8-byte aligned; alive while the H2D copies run)
     hipEvent_t r_pre_ev[kPreSets] = {nullptr, nullptr, nullptr};  // recorded behind the pre pass that filled set s
-    int r_pre_ext = -1;                  // >= 0: this frame's pre pass has been run for it into r_sets[r_pre_ext] (render_view skips its own)
-    int opt_render_multi_pre = 1;        // gsx_render_views: one pre pass per group of frames in flight (0: every frame its own)
-    DevBuf r_keys0, r_keys1, r_vals0, r_vals1;
-    DevBuf r_tile_order;                 // blend launch order (longest list first)
-    int r_sorted_in = 0;
-    DevBuf r_sat;                        // u8 per tile: every pixel is opaque (1 - alpha < 1e-5): later depth phases skip it
-    int opt_render_phases = 2;           // depth phases per frame (1 = bin and sort every pair at once)
-    int opt_render_phase_ratio = 6;      // phase p ends at nvis / ratio^(K-1-p) splats (front to back; nvis = the splats with a rectangle in the view; 4 until the level-1 sort left the others out)
-    int opt_render_bin32 = 1;            // bin, sort and range the splats by 32x32-pixel BINS (2x2 tiles); a pair carries the mask of the bin's tiles
-                                         // the splat's rectangle covers (one-wave blend kernel, no exact_cull, < 2^28 splats; else 16x16)
-    int opt_render_compact = 1;          // the level-1 sort leaves out the splats without a rectangle in the view (its first pass is the partition)
-    int opt_render_wide_sort = 1;        // the pair sorts in ONE pass when the list index fits 11 bits (sort.hip: radix_sort_values_wide; the ranges come with it):
-                                         // 0 never, 1 for a frame on its own (gsx_render_view), 2 also with several frames in flight
-    bool r_in_flight = false;            // this context renders one of several frames in flight (set by render_views for the call)
-    int r_bin32 = 0;                     // the frame being rendered uses bins (set by render_view, read by launch_blend)
-    unsigned long long r_P = 0;          // (tile, splat) pairs of the last view (all phases)
-    static constexpr int kMaxFrames = 6;
-    Ctx* twins[kMaxFrames - 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // gsx_render_views: further streams + per-frame buffers, aliasing this context's scene
-    int opt_render_frames = 4;           // frames in flight in gsx_render_views (1 .. kMaxFrames): 935 / 1252 / 1359 / 1396 views/s with 1 / 2 / 3 / 4
-    size_t r_pair_cap = 0;               // capacity (pairs) of r_keys*/r_vals*: grown when a phase overflows it, the frame is redone
-    unsigned long long r_consumed = 0;   // pairs the blend kernel actually staged (early-out leaves the rest unread)
-    DevBuf r_d0, r_d1, r_d2, r_d3;       // level-1 sort ping-pong (bucket, splat)
-    DevBuf r_rects;                      // the tile rectangles of a phase's splats in the phase's order (bin COUNT -> EMIT)
 
     // nearest-neighbour search (normals.hip)
     int opt_nn_brute = 0;                // 1: a 1 x 1 x 1 grid, i.e. every query visits every point (the search the grid is tested against)
@@ -424,22 +450,30 @@ int debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, double* 
                   uint32_t* cell_start_out, int32_t* order_out);  // test hook: the grid and the counting sort, host only
 int region_growing(Ctx* c, int64_t n, const float* points, int64_t k_normals, int k, double residual_threshold, double angle_threshold,
                    int32_t* labels_out, double* normals_out, double* residuals_out, int32_t* n_regions_out);
-// render.hip
+// render_scene.hip: what exists once per scene
 int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const float* rot, const float* opacity,
                   const float* f_dc, const int32_t* labels);
 int upload_sh(Ctx* c, const float* f_rest, int deg);
 int render_set_edits(Ctx* c, const gsx_render_edits* edits);
-int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out);
-int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* const* rgba_out);
-void render_release_twin(Ctx* c);
 int hit_test(Ctx* c, const gsx_camera* cam, int W, int H, double x, double y, int32_t* label_out, int64_t* index_out);
 int render_debug(Ctx* c, uint8_t* buffer_out, uint32_t* order_out, uint32_t* tex_out, uint32_t* bucket_out);
 int debug_render_scene(Ctx* c, int32_t* labels_out, float* sh_out, int32_t* sh_degree_out);
+// render_pre.hip: the per-view per-splat pass.  ONE place for its launches (gsx_render_view, gsx_render_views and the test hook
+// gsx_debug_render_pre), so that what the hook observes is the product's launch (grid cap, arguments, initial pre[])
+int ensure_pre_set(Ctx* c, PreSet& ps, long long n);
+int launch_pre(Ctx* c, const gsx_camera* cam, int W, int H, const PreSet& to);  // one view: pre[] reset, then pre_kernel
+int launch_pre_multi(Ctx* c, int nv, const gsx_camera* cams, int W, int H, PreSet* const* sets, int slot);  // view v into *sets[v]; arguments in slot `slot`
+void launch_bucket(Ctx* c, const PreSet& ps, uint32_t* bucket, uint32_t* key, uint32_t* idx, int* dropped, int compact);
 int debug_render_pre(Ctx* c, int nv, const gsx_camera* cams, int W, int H, int multi, int compact, const gsx_debug_pre_view* out);
+// render.hip: the frame
+int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out);
+int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* const* rgba_out);
+void render_release_twin(Ctx* c);
 int debug_exclusive_scan(Ctx* c, const uint32_t* in, uint32_t* out, long long n, unsigned long long* grand_dev);  // test hook: exclusive_scan_u32
 int debug_ranges(Ctx* c, const uint32_t* keys, const unsigned long long* total_dev, long long cap, int nlists, int2* ranges);  // test hook: ranges_kernel as a frame launches it
-// test hook: bin_kernel COUNT -> exclusive_scan_u32 -> bin_kernel EMIT of one depth phase as a frame launches them (device pointers)
-struct DebugBinArgs {
+// bin_kernel COUNT -> exclusive_scan_u32 -> bin_kernel EMIT of one depth phase (device pointers): what render_view launches per
+// phase and, through the test hook debug_bin, gsx_debug_bin in the caller's buffers
+struct BinPhaseArgs {
     const unsigned long long* nvis_dev;
     long long div0, div1, m_cap;
     const uint32_t* by_depth;
@@ -451,7 +485,10 @@ struct DebugBinArgs {
     unsigned long long* total_dev;
     unsigned long long pair_cap;
 };
-int debug_bin(Ctx* c, const DebugBinArgs& a);
+int debug_bin(Ctx* c, const BinPhaseArgs& a);
+// blend.hip
+int launch_blend(Ctx* c, const uint32_t* vals, int W, int H, int tiles_x, int tiles_y, const int* dropped_dev,
+                 unsigned long long* consumed_dev, uint8_t* sat, int first_phase, int last_phase);
 // iou.hip
 int iou_masks(Ctx* c, bool device, int n_masks, const void* const* masks, int mask_dtype, int n_gt, const void* const* gts, int gt_dtype,
               int h, int w, int64_t* inter_out, int64_t* area_masks_out, int64_t* area_gt_out, double* iou_out);

@@ -1,4 +1,4 @@
-"""Scenes and expectations for the scene upload (csrc/render.hip: splat_importance_kernel, splat_pack_kernel,
+"""Scenes and expectations for the scene upload (csrc/render_scene.hip: splat_importance_kernel, splat_pack_kernel,
 labels_pack_kernel, sh_pack_kernel) and constructed cases for the hit test (hit_partial_kernel, hit_final_kernel), shared by
 tests/test_pack_model.py (CPU: the cases against the oracle) and tests/test_pack_gpu.py (the kernels against the same
 expectations).  numpy and `oracle` only.

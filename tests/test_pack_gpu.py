@@ -1,4 +1,4 @@
-"""The scene upload and the hit test on the GPU (csrc/render.hip: splat_importance_kernel + the radix sort, splat_pack_kernel,
+"""The scene upload and the hit test on the GPU (csrc/render_scene.hip: splat_importance_kernel + the radix sort, splat_pack_kernel,
 labels_pack_kernel, sh_pack_kernel; hit_partial_kernel, hit_final_kernel) against the expectations of tests/pack_cases.py,
 which tests/test_pack_model.py checks against the oracle on the CPU.
 
@@ -6,7 +6,7 @@ Everything is compared EXACTLY: the 32-byte rows, the importance permutation, th
 SH planes through their uint32 view; (label, row) of every pick.  No tolerance anywhere in this file: the scenes are built so
 that no stored value depends on the last bits of the device's fp64 exp (pack_cases rule 2).
 
-On an MI355X all 65 tests pass, 2.4 s in all.  Mutants of render.hip, each built once and run once against this file (tests that
+On an MI355X all 65 tests pass, 2.4 s in all.  Mutants of the unit (then part of render.hip), each built once and run once against this file (tests that
 failed, of 65):
     hit_final_kernel's label through fp32, (int)(float)labels[idx], the value the texture word holds      3: label_2^24+1 gives
         (16777216, 299) for (16777217, 299), label_-2^24-1, and the scene in importance order

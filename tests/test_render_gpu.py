@@ -223,6 +223,65 @@ def test_render_views_two_frames_in_flight(gsx):
         assert c.render_views([], W, H, to_host=False) is None
 
 
+def test_options_and_scene_reach_every_frame_in_flight(gsx):
+    """With four frames in flight views 1-3 are rendered by twins: contexts of their own that copy the rasterizer options and
+    alias the scene of the context the caller holds.  Every rasterizer option, a scene uploaded anew and a label edit, each set
+    AFTER the twins exist, must reach them: gsx_render_views gives the frames of gsx_render_view bit for bit, and its pair count
+    is the sum of the views' own - a twin that rendered with a stale option or scene would count other pairs (bins instead of
+    tiles, culled or not) or draw another frame."""
+    n, W, H = 20_000, 320, 192
+    cams = scene.make_cameras(5, W, H, convention="c2w")
+    rng = np.random.default_rng(41)
+    defaults = {"render_phases": 2, "render_phase_ratio": 6, "exact_cull": 0, "render_bin32": 1, "render_compact": 1,
+                "render_wide_sort": 1, "blend_pk2": 2, "tile_lpt": 0, "render_share_stream": 1}
+    # (options, the pair count must differ from the defaults': the setting changes what a pair is)
+    settings = [({"render_phases": 1}, False), ({"render_phases": 3, "render_phase_ratio": 2}, False), ({"exact_cull": 1}, True),
+                ({"render_bin32": 0}, True), ({"render_compact": 0}, False), ({"render_wide_sort": 2}, False), ({"blend_pk2": 1}, True),
+                ({"blend_pk2": 0}, False), ({"tile_lpt": 1, "render_bin32": 0}, False), ({"render_share_stream": 0}, False),
+                ({"render_share_stream": 1}, False)]
+    with gsx.Context(0) as c:
+        c.set_option("render_frames", 4)
+
+        def upload(seed):
+            xyz = scene.make_positions(n, seed)
+            a = scene.make_splat_attributes(n, seed, sh_degree=1)
+            c.upload_splats(xyz, a["scale"], a["rot"], a["opacity"], a["f_dc"], rng.integers(0, 8, n).astype(np.int32))
+            c.upload_sh(a["f_rest"], 1)
+
+        def check(what):
+            single, pairs = [], 0
+            for cam in cams:
+                single.append(c.render_view(cam, W, H))
+                pairs += c.render_num_pairs()
+            many = c.render_views(cams, W, H)
+            for k in range(len(cams)):
+                assert np.array_equal(many[k], single[k]), (what, k)
+            assert c.render_num_pairs() == pairs, what
+            return pairs, single
+
+        upload(31)
+        c.render_views(cams, W, H, to_host=False)  # the twins exist from here on
+        base, frames = check("defaults")
+        for i, (opts, differs) in enumerate(settings):
+            if i == 2:  # a new scene behind the twins' aliases
+                upload(32)
+                base, other = check("scene uploaded anew")
+                assert not np.array_equal(other[0], frames[0])
+                frames = other
+            if i == 5:  # a label edit: the twins draw the same state
+                c.set_render_edits(hidden=[3])
+                assert c.render_num_hidden() > 0
+                base, other = check("one label hidden")
+                assert not np.array_equal(other[0], frames[0])
+            for k, v in opts.items():
+                c.set_option(k, v)
+            pairs, _ = check(opts)
+            if differs:
+                assert pairs != base, opts
+            for k in opts:
+                c.set_option(k, defaults[k])
+
+
 @pytest.mark.parametrize("n,bin32", [(300_000, 0), (1_100_000, 1)])
 def test_pair_count_beyond_31_bits_is_an_error_not_a_wrapped_offset(gsx, n, bin32):
     """the (list, splat) pair count of a close-up of a very large scene can pass 2^31 (offsets are 32 bit).

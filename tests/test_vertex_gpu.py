@@ -1,4 +1,4 @@
-"""The rasterizer's per-splat pre pass on the GPU (csrc/render.hip: pre_geom, pre_one, pre_kernel<EDIT>, the twelve
+"""The rasterizer's per-splat pre pass on the GPU (csrc/render_pre.hip: pre_geom, pre_one, pre_kernel<EDIT>, the twelve
 pre_multi_kernel<NV, EDIT> and bucket_kernel) through gsx_debug_render_pre, which issues the product's own launches, against the
 numpy models of tests/vertex_model.py on the scenes of tests/vertex_cases.py.  test_vertex_model.py shows on the CPU that the
 models equal the oracle bit for bit and that every scene enters the branches it names.
@@ -9,7 +9,7 @@ splat a rectangle and at splat 0; every other record must still hold the 0xFF by
 fp32 in the oracle's operation order, compiled without contraction, with correctly rounded division and square root: no
 tolerance anywhere in this file.  On an MI355X every field of every splat is identical (39 tests, 1 048 581 splats at the most).
 
-Mutants of render.hip, each built once and run once (tests of this file that failed / older rasterizer tests that noticed):
+Mutants of the unit (then part of render.hip), each built once and run once (tests of this file that failed / older rasterizer tests that noticed):
     p2[0] > clip -> >=                       the 3 frustum scenes / none       1/64 slack taken off ex       18 / none
     floorf for x0                            31 / 3 (blend lists)              grid stride doubled           the 2 large sizes / none
     depth_range_to without slo[3]            wave3, size_256, 524289 / 10      .. without shi[3]             13 / 8

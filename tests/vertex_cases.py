@@ -1,4 +1,4 @@
-"""Small scenes, each built to enter named branches of the rasterizer's per-splat pre pass (csrc/render.hip: pre_geom, pre_one,
+"""Small scenes, each built to enter named branches of the rasterizer's per-splat pre pass (csrc/render_pre.hip: pre_geom, pre_one,
 pre_kernel, pre_multi_kernel, bucket_kernel), shared by test_vertex_model.py (CPU: the model equals the oracle on them and every
 scene holds what it was built for) and test_vertex_gpu.py.
 

@@ -1,4 +1,4 @@
-"""numpy models of the rasterizer's per-splat pre pass (csrc/render.hip: pre_geom, pre_one, pre_kernel, pre_multi_kernel,
+"""numpy models of the rasterizer's per-splat pre pass (csrc/render_pre.hip: pre_geom, pre_one, pre_kernel, pre_multi_kernel,
 bucket_kernel), no GPU code.
 
 vertex       the vertex shader (gs.js:696-750) as oracle/render_oracle.c:gsxo_vertex evaluates it: float32, ONE numpy operation
