@@ -163,6 +163,7 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
     const std::string k(name);
     if (k == "spatial_sort") c->opt_spatial_sort = value != 0;
     else if (k == "nn_brute") c->opt_nn_brute = value != 0;
+    else if (k == "smooth_search") c->opt_smooth_search = value != 0;
     else if (k == "iou_table_lds") c->opt_iou_table_lds = value != 0;
     else if (k == "xcd_swizzle") {
         if (value < 0 || value > 65536) return gsx::fail(c, GSX_E_INVALID, "set_option: xcd_swizzle must be in [0,65536]");
@@ -630,6 +631,21 @@ int gsx_region_growing(gsx_ctx* ctx, int64_t n, const float* points, int64_t k_n
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::region_growing(c, n, points, k_normals, k, residual_threshold, angle_threshold, labels_out,
                                normals_out, residuals_out, n_regions_out); });
+}
+
+int gsx_smooth_labels(gsx_ctx* ctx, int64_t n, const float* points, const int32_t* labels, int64_t k, int32_t rounds, int32_t min_votes,
+                      int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* support_out, int64_t* changed_out,
+                      int32_t* rounds_done_out) {
+    CTX_OR_FAIL(ctx);
+    const gsx::SmoothArgs a{rounds, min_votes, ignore_label, flags, labels_out, support_out, changed_out, rounds_done_out};
+    return gsx::guard(c, __func__, [&] { return gsx::smooth_labels(c, n, points, labels, k, a); });
+}
+int gsx_smooth_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* knn, const int32_t* labels, int32_t rounds, int32_t min_votes,
+                            int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* support_out, int64_t* changed_out,
+                            int32_t* rounds_done_out) {
+    CTX_OR_FAIL(ctx);
+    const gsx::SmoothArgs a{rounds, min_votes, ignore_label, flags, labels_out, support_out, changed_out, rounds_done_out};
+    return gsx::guard(c, __func__, [&] { return gsx::smooth_labels_lists(c, n, k, knn, labels, a); });
 }
 
 int gsx_iou_masks(gsx_ctx* ctx, int32_t n_masks, const void* const* masks, int32_t mask_dtype, int32_t n_gt, const void* const* gts,

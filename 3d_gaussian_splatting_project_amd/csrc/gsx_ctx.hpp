@@ -346,8 +346,15 @@ struct Ctx {
     int opt_nn_brute = 0;                // 1: a 1 x 1 x 1 grid, i.e. every query visits every point (the search the grid is tested against)
     DevBuf nn_index;                     // int32[n][k]: the lists of the last gsx_knn
     int64_t nn_index_rows = 0;           // 0: none
+    int nn_index_k = 0;                  // ... and their k
     DevBuf nn_pts, nn_cs;                // float4[n] (x, y, z, index) in cell order; u32[cells + 1]
     DevBuf nn_out, nn_flag;              // double normals[3n] | residuals[n] | moments[9n] (before the search: the raw points of the finite check); int
+
+    // label filter (smooth.hip)
+    int opt_smooth_search = 0;           // 1: the search form also for k <= 64 (the form the lists are tested against)
+    DevBuf sm_lab[2];                    // the round's input and output: int32[n] labels (list form) or u16[n] class ids (search form)
+    DevBuf sm_sup, sm_changed;           // int32[n] support; u64: labels the round changed
+    DevBuf sm_lists;                     // int32[n][k]: lists handed over by the caller (gsx_smooth_labels_lists)
 
     // IoU evaluation (iou.hip): buffers only grow
     int opt_iou_table_lds = 1;           // label-map tables of up to 40000 entries are counted in LDS per workgroup (0: on the global table)
@@ -446,10 +453,20 @@ void debug_cull_planes(const gsx_camera* cam, double* out);
 int normals(Ctx* c, int64_t n, const float* points, int64_t k, double* normals_out, double* residuals_out, double* moments_out = nullptr,
             bool checked = false);
 int knn(Ctx* c, int64_t n, const float* points, int k, int32_t* index_out, bool checked = false);
+int knn_lists(Ctx* c, const char* who, int64_t n, const float* points, int k, int32_t* index_out, bool checked);  // knn without its argument checks, k >= 1
 int debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, double* origin_out, double* h_out, int32_t* dims_out,
                   uint32_t* cell_start_out, int32_t* order_out);  // test hook: the grid and the counting sort, host only
 int region_growing(Ctx* c, int64_t n, const float* points, int64_t k_normals, int k, double residual_threshold, double angle_threshold,
                    int32_t* labels_out, double* normals_out, double* residuals_out, int32_t* n_regions_out);
+// smooth.hip: the k-nearest-neighbour majority filter over a label field
+struct SmoothArgs {
+    int32_t rounds, min_votes, ignore_label, flags;
+    int32_t *labels_out, *support_out;
+    int64_t* changed_out;
+    int32_t* rounds_done_out;
+};
+int smooth_labels(Ctx* c, int64_t n, const float* points, const int32_t* labels, int64_t k, const SmoothArgs& a);
+int smooth_labels_lists(Ctx* c, int64_t n, int32_t k, const int32_t* knn, const int32_t* labels, const SmoothArgs& a);
 // render_scene.hip: what exists once per scene
 int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const float* rot, const float* opacity,
                   const float* f_dc, const int32_t* labels);

@@ -326,6 +326,49 @@ class Context:
                                            C.byref(nreg)), self.h)
         return labels, nrm, res, int(nreg.value)
 
+    # -- label clean-up (csrc/smooth.hip): majority filter over the k nearest neighbours, hole filling ----------------------
+    def _smooth(self, call, n, labels, rounds, min_votes, ignore_label, fill_only, return_support):
+        if fill_only and ignore_label is None:
+            raise ValueError("fill_only needs an ignore_label: the label that marks a hole")
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if len(lab) != n:
+            raise ValueError("labels must hold one entry per point")
+        flags = (_lib.GSX_SMOOTH_IGNORE if ignore_label is not None else 0) | (_lib.GSX_SMOOTH_FILL_ONLY if fill_only else 0)
+        out = np.empty(n, np.int32)
+        sup = np.empty(n, np.int32) if return_support else None
+        changed = np.zeros(max(int(rounds), 0), np.int64)
+        done = C.c_int32(0)
+        check(call(lab.ctypes.data, int(rounds), int(min_votes), int(ignore_label or 0), flags, out.ctypes.data,
+                   sup.ctypes.data if return_support else None, changed.ctypes.data, C.byref(done)), self.h)
+        self.smooth_rounds_done = int(done.value)
+        changed = [int(v) for v in changed]
+        return (out, changed, sup) if return_support else (out, changed)
+
+    def smooth_labels(self, points, labels, k=16, rounds=1, min_votes=1, ignore_label=None, fill_only=False, return_support=False):
+        """gsx_smooth_labels (include/gsx.h): `rounds` Jacobi rounds of the majority filter over every point's exact k nearest
+        neighbours.  ignore_label: neighbours with this label cast no vote (None: every neighbour votes); fill_only: only points
+        whose label is ignore_label change.  Returns (labels int32 (n,), changed per round - a list of `rounds` counts, 0 behind
+        the round that changed nothing) plus support int32 (n,) with return_support; self.smooth_rounds_done = rounds executed."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        return self._smooth(lambda *a: self._lib.gsx_smooth_labels(self.h, len(pts), pts.ctypes.data, a[0], int(k), *a[1:]), len(pts), labels,
+                            rounds, min_votes, ignore_label, fill_only, return_support)
+
+    def smooth_labels_lists(self, knn, labels, rounds=1, min_votes=1, ignore_label=None, fill_only=False, return_support=False, k=None):
+        """gsx_smooth_labels_lists: the same rounds over neighbour lists int32 (n, k <= 64) - or, with knn None, over the
+        device lists the last knn / region_growing call left on this context (their k must be given)."""
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if knn is None:
+            if k is None:
+                raise ValueError("knn is None: k of the context's device lists is needed")
+            nb, kk = None, int(k)
+        else:
+            nb = np.ascontiguousarray(knn, np.int32)
+            if nb.ndim != 2 or len(nb) != len(lab):
+                raise ValueError("knn (n, k) and labels (n,) must agree in n")
+            kk = nb.shape[1]
+        return self._smooth(lambda *a: self._lib.gsx_smooth_labels_lists(self.h, len(lab), kk, None if nb is None else nb.ctypes.data, *a),
+                            len(lab), lab, rounds, min_votes, ignore_label, fill_only, return_support)
+
     # -- exchange protocol v4 (see include/gsx.h) ------------------------------------------------------------------------
     def vote_num_views(self):
         return int(self._lib.gsx_vote_num_views(self.h))

@@ -15,6 +15,9 @@ Added flags: --segmap_dir DIR, --n_classes C (default: 150 for the ADE20K models
 (informational).  Several GPUs: `python -m torch.distributed.run --nproc-per-node N deep_learning_segmentation.py
 ...` — every rank segments and stages its contiguous block of the cameras, the packed class maps are all-gathered over
 RCCL and every rank votes its slab of the Gaussians (3d_gaussian_splatting_project_amd/dist.py, protocol v4).
+--smooth_k N [--smooth_rounds R] [--fill_unlabeled] (default off) cleans the finished labels with the majority filter over
+the N nearest neighbours (3D_clustering/smooth_labels.py) before the file is written; --fill_unlabeled only fills the
+Gaussians no view saw.
 """
 import argparse
 import importlib
@@ -222,7 +225,7 @@ def save_labeled_ply(output_file, plydata, labels):
     plydata.write(output_file, labels=np.asarray(labels, dtype=np.int32))
 
 
-def main(argv=None):
+def make_parser():
     parser = argparse.ArgumentParser(description="Add labels to gaussians PLY file")
     parser.add_argument("--ply_file", help="Input PLY file with gaussians data")
     parser.add_argument("--camera_file", help="JSON file with camera data")
@@ -234,7 +237,30 @@ def main(argv=None):
     parser.add_argument("--segmap_dir", default=None, help="read <img_name>_segmap.npy from here instead of running a model")
     parser.add_argument("--n_classes", type=int, default=None, help="number of classes (labels -1..C-1)")
     parser.add_argument("--gpus", type=int, default=1, help="GPUs of this node (N>1: launch with torch.distributed.run)")
+    parser.add_argument("--smooth_k", type=int, default=0, help="clean the labels with a majority filter over this many nearest "
+                        "neighbours (0: off)")
+    parser.add_argument("--smooth_rounds", type=int, default=1, help="rounds of that filter")
+    parser.add_argument("--fill_unlabeled", action="store_true", help="the filter only fills Gaussians no view saw (label -1), "
+                        "from their labelled neighbours")
+    return parser
+
+
+def smooth_labels(gaussians, labels, k, rounds=1, fill_unlabeled=False):
+    """The k-nearest-neighbour majority filter (Context.smooth_labels) over the finished labels; fill_unlabeled: unlabelled
+    neighbours cast no vote and only unlabelled Gaussians change."""
+    with gsx.Context() as ctx:
+        labels, changed = ctx.smooth_labels(gaussians["position"], labels, k=min(int(k), len(labels)), rounds=rounds,
+                                            ignore_label=-1 if fill_unlabeled else None, fill_only=fill_unlabeled)
+    for r, ch in enumerate(changed):
+        print(f"Smoothing round {r + 1}: {ch} labels changed")
+    return labels
+
+
+def main(argv=None):
+    parser = make_parser()
     args = parser.parse_args(argv)
+    if args.fill_unlabeled and args.smooth_k <= 0:
+        parser.error("--fill_unlabeled needs --smooth_k")
 
     print("Loading cameras...")
     cameras = load_cameras(args.camera_file)
@@ -250,6 +276,9 @@ def main(argv=None):
     _shutdown()
     if int(os.environ.get("RANK", "0")) != 0:
         return          # every rank holds the same labels; rank 0 writes the file
+    if args.smooth_k > 0:
+        print("Smoothing labels...")
+        labels = smooth_labels(gaussians, labels, args.smooth_k, args.smooth_rounds, args.fill_unlabeled)
     print("Saving labeled PLY file...")
     save_labeled_ply(args.output_file, plydata, labels)
     print(f"Done! Labeled PLY file saved as {args.output_file}")

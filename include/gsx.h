@@ -187,7 +187,9 @@ int gsx_synchronize(gsx_ctx* ctx);
  *                               n_classes <= 254, unit scale and "seg_tiled"; otherwise the one-level path runs
  *   "iou_table_lds" (default 1) gsx_iou_label_maps*: a table of up to 40000 entries is counted in a u32 copy in LDS per
  *                               workgroup and flushed once; 0 = every add goes to the global u64 table (the path of larger
- *                               tables).  Same tables */
+ *                               tables).  Same tables
+ *   "smooth_search" (default 0) gsx_smooth_labels: 1 = the search form (no stored lists, a class table in LDS) for k <= 64 too,
+ *                               where the default runs over lists.  Same labels, support and changed counts */
 int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value);
 /* the current value of an option that other code overrides for a while and has to put back: "early_vote", "early_vote_at",
  * "early_replay", "seg_tiled", "seg_coarse"; GSX_E_INVALID for any other name */
@@ -692,7 +694,7 @@ int gsx_debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, doub
  * stay on the device. */
 int gsx_knn(gsx_ctx* ctx, int64_t n, const float* points, int32_t k, int32_t* index_out);
 /* device pointer of the int32[n][k] lists of the last successful gsx_knn (NULL: none); valid until the next gsx_knn /
- * gsx_region_growing on the ctx */
+ * gsx_region_growing / gsx_smooth_labels on the ctx (the last builds lists of its own when its k <= 64) */
 void* gsx_knn_device(gsx_ctx* ctx);
 /* segmentation_3D (rg.py:166-226) on the host; needs no ctx and no GPU (errors: gsx_last_error(NULL)).
  * normals double[n][3], residuals double[n], knn int32[n][k] (row i = the neighbours of i in visiting order).
@@ -711,6 +713,48 @@ int gsx_region_grow(int64_t n, const double* normals, const double* residuals, c
 int gsx_region_growing(gsx_ctx* ctx, int64_t n, const float* points, int64_t k_normals, int32_t k, double residual_threshold,
                        double angle_threshold, int32_t* labels_out, double* normals_out, double* residuals_out,
                        int32_t* n_regions_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * label clean-up: a majority filter over the k nearest neighbours, with hole filling.  It repairs a `label` field that one of
+ * the three labelers wrote: the vote projects centres only and knows no occlusion (dls.py:43-82), so a Gaussian behind a wall
+ * takes the wall's class and one that no view sees stays -1.  The reference has no such step; the rule below is the contract,
+ * and it is all integers.
+ * points: n x 3 float32, row-major, on the host; labels int32[n], any values; 1 <= k <= n; rounds >= 1; min_votes >= 1;
+ * flags: GSX_SMOOTH_IGNORE | GSX_SMOOTH_FILL_ONLY.
+ * N(i) = the k nearest points of i by the key (d2, index) - exactly the set gsx_knn / gsx_normals select: d2 is fp64 of the
+ * widened coordinates, (dx*dx + dy*dy) + dz*dz without FMA; nearer first, then lower index.  N(i) holds i itself unless
+ * duplicates with lower indices crowd it out.
+ * One round, L = the labels at its start.  The update is Jacobi: every point reads L, the results go to a second buffer.
+ *   count[c] = number of j in N(i) with L[j] == c; with GSX_SMOOTH_IGNORE the neighbours whose label is ignore_label cast no
+ *   vote.  No neighbour votes: new[i] = L[i].  Otherwise m = the largest count and W = the labels that reach it; the winner
+ *   is L[i] if L[i] is in W, else the smallest value in W (signed compare).  new[i] = the winner, unless m < min_votes: then
+ *   new[i] = L[i].  With GSX_SMOOTH_FILL_ONLY, new[i] = L[i] whenever L[i] != ignore_label (only holes are filled).
+ *   changed_out[r] = number of i with new[i] != L[i] in round r.
+ * A round that changes nothing ends the run; *rounds_done_out = rounds executed, that one included; the later entries of
+ * changed_out[rounds] are 0.  support_out[i] = count of i's final label among N(i) in the input of the last executed round
+ * (0 when that label cast no vote).  labels_out int32[n] is required and may be `labels` itself; support_out, changed_out and
+ * rounds_done_out may be NULL.
+ * k <= 64: the lists are built once (as by gsx_knn: they replace the context's lists, see gsx_knn_device) and every round
+ * runs over them, comparing raw labels: any number of distinct labels.  k > 64: every round searches again and counts dense
+ * class ids in 16 bits: k <= 65535 and at most 4096 distinct labels.  Option "smooth_search" (default 0): 1 = that second
+ * form for k <= 64 too; like "nn_brute" it never changes a result (tests).
+ * Every error returns before any launch.  GSX_E_INVALID: a NULL points, labels or labels_out, n < 1, k < 1, k > n,
+ * rounds < 1, min_votes < 1, unknown flag bits, a non-finite coordinate.  GSX_E_UNSUPPORTED: n > 2^31-1; with k > 64 (or
+ * "smooth_search") k > 65535 or more than 4096 distinct labels.
+ * ------------------------------------------------------------------------------------------- */
+#define GSX_SMOOTH_IGNORE 1
+#define GSX_SMOOTH_FILL_ONLY 2
+int gsx_smooth_labels(gsx_ctx* ctx, int64_t n, const float* points, const int32_t* labels, int64_t k, int32_t rounds,
+                      int32_t min_votes, int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* support_out,
+                      int64_t* changed_out, int32_t* rounds_done_out);
+/* the same rounds over given neighbour lists, 1 <= k <= min(64, n).  knn: host int32[n][k] with every index in [0, n) - the
+ * lists need not come from a search, and a row that names a point twice lets it vote twice - or NULL: the device lists of the
+ * last gsx_knn / gsx_region_growing / gsx_smooth_labels (k <= 64) on the ctx, whose n and k must be these.
+ * GSX_E_INVALID as above, and for k > 64 or a list index outside [0, n) (the text names row and column; nothing is
+ * launched); GSX_E_STATE: knn == NULL without device lists of this n and k; GSX_E_UNSUPPORTED: n > 2^31-1. */
+int gsx_smooth_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* knn, const int32_t* labels, int32_t rounds,
+                            int32_t min_votes, int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* support_out,
+                            int64_t* changed_out, int32_t* rounds_done_out);
 
 /* ---------------------------------------------------------------------------------------------
  * IoU evaluation of 2-D segmentations: Image_Segmentation/evaluation.py ("ev.py").  Everything is counted in
