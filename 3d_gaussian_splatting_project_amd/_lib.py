@@ -13,6 +13,7 @@ GSX_E_INVALID, GSX_E_HIP, GSX_E_STATE, GSX_E_RANGE, GSX_E_UNSUPPORTED, GSX_E_IO 
 GSX_SEG_I32, GSX_SEG_I64, GSX_SEG_U8, GSX_SEG_U8_LABELS = 0, 1, 2, 3
 GSX_MASK_U8, GSX_MASK_I32, GSX_MASK_I64, GSX_MASK_F32, GSX_MASK_F64 = 0, 1, 2, 3, 4
 GSX_F32, GSX_F16, GSX_BF16 = 0, 1, 2
+GSX_QUERIES_SEGMENTS, GSX_QUERIES_LABELS = 0, 1
 GSX_SMOOTH_IGNORE, GSX_SMOOTH_FILL_ONLY = 1, 2
 
 
@@ -177,6 +178,10 @@ _SIGS = {
     "gsx_segmap_from_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_int32, C.c_void_p]),
     "gsx_debug_segmap_constants": (C.c_int, [C.c_void_p]),
+    "gsx_segmap_from_queries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "gsx_debug_queries_constants": (C.c_int, [C.c_void_p]),
     "gsx_debug_segpack_constants": (C.c_int, [C.c_void_p]),
     "gsx_vote_culled": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "gsx_debug_filter_check": (C.c_int, [C.c_void_p, C.c_void_p]),

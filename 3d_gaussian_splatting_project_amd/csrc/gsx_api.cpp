@@ -699,6 +699,21 @@ int gsx_debug_segmap_constants(int32_t* out) {
     gsx::segmap_constants(out);
     return GSX_OK;
 }
+int gsx_segmap_from_queries(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, int32_t Q, int32_t h, int32_t w, int32_t K,
+                            const int32_t* slot_query_dev, const float* slot_score_dev, const int32_t* slot_label_dev, int32_t mid_w,
+                            int32_t mid_h, double threshold, int32_t mode, int32_t out_w, int32_t out_h, int32_t* map_dev,
+                            int32_t* slot_segment_dev, float* slot_pred_score_dev) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] {
+        return gsx::segmap_from_queries(c, masks_dev, dtype, Q, h, w, K, slot_query_dev, slot_score_dev, slot_label_dev, mid_w, mid_h, threshold,
+                                        mode, out_w, out_h, map_dev, slot_segment_dev, slot_pred_score_dev);
+    });
+}
+int gsx_debug_queries_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_queries_constants: NULL argument");
+    gsx::queries_constants(out);
+    return GSX_OK;
+}
 int gsx_debug_segpack_constants(int32_t* out) {
     if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_segpack_constants: NULL argument");
     gsx::segpack_constants(out);

@@ -372,6 +372,10 @@ struct Ctx {
 
     // class maps from network outputs (segmap.hip)
     DevBuf seg_low;                      // int32 [n][h w]: the maps at the network's resolution, between the two kernels of a call
+    // Mask2Former queries (queries.hip): everything between the kernels of one call
+    DevBuf q_bits;                       // u64 [K][mid_h][ceil(mid_w / 64)]: the slot-major bit planes of "v > 0"
+    DevBuf q_parts;                      // QPart [K][workgroups per slot]: sigmoid sum, set count, sampled count, NaN flag
+    DevBuf q_tab;                        // int32 [2][K]: segment id and map value per slot, then the u64 words of the sampled columns and rows
 
     // profiling
     bool prof_on = false;
@@ -519,6 +523,15 @@ int segmap_from_logits(Ctx* c, const void* logits, int dtype, int n, int C, int 
 int segmap_from_masks(Ctx* c, const void* masks, int dtype, int K, int mh, int mw, const float* cls, const float* conf, int out_w, int out_h,
                       int32_t* map);
 void segmap_constants(int32_t out[8]);
+int seg_elem_bytes(int dtype);                    // 0: not a gsx_float_dtype
+bool seg_misaligned(const void* p, int bytes);
+// seg_low (n, h, w) -> out (n, H, W) on the ctx stream; torch_rule: torch's float32 nearest rule instead of OpenCV's
+int seg_launch_resize(Ctx* c, int n, int w, int h, int W, int H, int32_t* out, bool torch_rule = false);
+// queries.hip
+int segmap_from_queries(Ctx* c, const void* masks, int dtype, int Q, int h, int w, int K, const int32_t* slot_query, const float* slot_score,
+                        const int32_t* slot_label, int mid_w, int mid_h, double threshold, int mode, int out_w, int out_h, int32_t* map,
+                        int32_t* slot_segment, float* slot_pred_score);
+void queries_constants(int32_t out[8]);
 // vote.hip
 void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, int img_w, int img_h);
 

@@ -4,12 +4,11 @@
 // thousands of pixels, which stay in L2 - and then gather it to the image size; a nearest resize only copies pixels, so
 // compositing before the resize gives what dls.py:120-121 gives by resizing every mask first.
 // Nothing here rounds: floats are only compared, and the one multiplication of the resize rule is a single fp64 product
-// (this file is built with -ffp-contract=off like its siblings).
-#include <hip/hip_fp16.h>
-
+// (this file is built with -ffp-contract=off like its siblings).  The gather kernel also serves queries.hip, with torch's
+// nearest rule (one fp32 product) instead of OpenCV's; the two producers here keep OpenCV's.
 #include <climits>
 
-#include "gsx_ctx.hpp"
+#include "segmap_device.hpp"
 
 namespace gsx {
 
@@ -21,19 +20,6 @@ static constexpr int kSegPixWg = 64 * kSegVec;           // pixels per workgroup
 static constexpr int kSegBlock = 64 * kSegSlices;
 static constexpr int kSegResizeVec = 4;                  // consecutive output pixels of one lane of the resize kernel: one 16-byte store
 static constexpr int kSegResizeBlock = 256;
-
-template <int DT>
-struct SegBits { using type = uint16_t; };
-template <>
-struct SegBits<GSX_F32> { using type = uint32_t; };
-
-// the value of an element as fp32: exact for all three formats, so comparing the results compares the elements
-template <int DT>
-__device__ __forceinline__ float seg_val(unsigned bits) {
-    if (DT == GSX_F32) return __uint_as_float(bits);
-    if (DT == GSX_F16) return __half2float(__ushort_as_half((unsigned short)bits));
-    return __uint_as_float(bits << 16);
-}
 
 // pixels [i, i + kSegVec) of a plane of n pixels, as one load where the address allows it; pixels past the end read as 0
 template <int DT>
@@ -167,13 +153,15 @@ __global__ __launch_bounds__(kSegBlock) void segmap_masks_kernel(const void* __r
     }
 }
 
-// ---- nearest resize: OpenCV's resizeNN, s(d) = min(floor(d * inv), S - 1) with inv = 1.0 / ((double)D / S) from the host -----------------
-__device__ __forceinline__ int seg_src(int d, double inv, int S) {
-    const int s = (int)floor((double)d * inv);
-    return s < S - 1 ? s : S - 1;
+// ---- nearest resize: OpenCV's rule for the two producers here, torch's for the queries (segmap_device.hpp) -----------------------------
+// inv: OpenCV's 1.0 / ((double)D / S), or torch's (float)S / D widened (exactly) to a double
+template <bool TORCH>
+__device__ __forceinline__ int seg_src_rule(int d, double inv, int S) {
+    return TORCH ? seg_src_torch(d, (float)inv, S) : seg_src(d, inv, S);
 }
 
 // out[img][y][x] = low[img][sy(y)][sx(x)]; a lane owns kSegResizeVec consecutive pixels of one output row
+template <bool TORCH>
 __global__ __launch_bounds__(kSegResizeBlock) void segmap_resize_kernel(const int* __restrict__ low, int w, int h, int W, int H, int qpr,
                                                                         long long nquads, double inv_x, double inv_y, int* __restrict__ out) {
     const long long q = (long long)blockIdx.x * kSegResizeBlock + threadIdx.x;
@@ -182,11 +170,11 @@ __global__ __launch_bounds__(kSegResizeBlock) void segmap_resize_kernel(const in
     const int x0 = (int)(q - row * qpr) * kSegResizeVec;
     const long long img = row / H;
     const int y = (int)(row - img * H);
-    const int* __restrict__ src = low + img * ((long long)h * w) + (long long)seg_src(y, inv_y, h) * w;
+    const int* __restrict__ src = low + img * ((long long)h * w) + (long long)seg_src_rule<TORCH>(y, inv_y, h) * w;
     int* dst = out + row * W + x0;
     int v[kSegResizeVec];
 #pragma unroll
-    for (int j = 0; j < kSegResizeVec; ++j) v[j] = x0 + j < W ? src[seg_src(x0 + j, inv_x, w)] : 0;
+    for (int j = 0; j < kSegResizeVec; ++j) v[j] = x0 + j < W ? src[seg_src_rule<TORCH>(x0 + j, inv_x, w)] : 0;
     static_assert(kSegResizeVec == 4, "the vector store below writes four pixels");
     if (x0 + kSegResizeVec <= W && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
         *reinterpret_cast<int4*>(dst) = make_int4(v[0], v[1], v[2], v[3]);
@@ -198,7 +186,7 @@ __global__ __launch_bounds__(kSegResizeBlock) void segmap_resize_kernel(const in
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
-static int seg_elem_bytes(int dtype) {
+int seg_elem_bytes(int dtype) {
     switch (dtype) {
         case GSX_F32: return 4;
         case GSX_F16: case GSX_BF16: return 2;
@@ -206,15 +194,22 @@ static int seg_elem_bytes(int dtype) {
     return 0;
 }
 
-static bool seg_misaligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0; }
+bool seg_misaligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0; }
 
-static int seg_launch_resize(Ctx* c, int n, int w, int h, int W, int H, int32_t* out) {
+int seg_launch_resize(Ctx* c, int n, int w, int h, int W, int H, int32_t* out, bool torch_rule) {
     const int qpr = (W + kSegResizeVec - 1) / kSegResizeVec;
     const long long nquads = (long long)n * H * qpr;
-    const double inv_x = 1.0 / ((double)W / (double)w), inv_y = 1.0 / ((double)H / (double)h);
+    const dim3 grid((unsigned)((nquads + kSegResizeBlock - 1) / kSegResizeBlock));
     ProfScope ps(c, "segmap_resize");
-    hipLaunchKernelGGL(segmap_resize_kernel, dim3((unsigned)((nquads + kSegResizeBlock - 1) / kSegResizeBlock)), dim3(kSegResizeBlock), 0,
-                       c->stream, c->seg_low.as<int>(), w, h, W, H, qpr, nquads, inv_x, inv_y, out);
+    if (torch_rule) {
+        const double sx = (double)((float)w / (float)W), sy = (double)((float)h / (float)H);
+        hipLaunchKernelGGL(segmap_resize_kernel<true>, grid, dim3(kSegResizeBlock), 0, c->stream, c->seg_low.as<int>(), w, h, W, H, qpr, nquads,
+                           sx, sy, out);
+    } else {
+        const double inv_x = 1.0 / ((double)W / (double)w), inv_y = 1.0 / ((double)H / (double)h);
+        hipLaunchKernelGGL(segmap_resize_kernel<false>, grid, dim3(kSegResizeBlock), 0, c->stream, c->seg_low.as<int>(), w, h, W, H, qpr, nquads,
+                           inv_x, inv_y, out);
+    }
     return GSX_OK;
 }
 

@@ -803,6 +803,43 @@ class Context:
         cur.wait_stream(ext)
         return out
 
+    def segmap_from_queries(self, masks, slot_query, slot_score, size, slot_label=None, mid=(384, 384), threshold=0.5, labels=False,
+                            return_slots=False):
+        """int32 (height, width) map from Mask2Former's query outputs, on the device: what transformers'
+        post_process_instance_segmentation(outputs, target_sizes=[(height, width)]) does after its softmax / top-k
+        (deep_learning_segmentation.py:156-158).  masks (Q, h, w) mask logits; slot_query, slot_score, slot_label (K,): query
+        index, score and class of the selected slots, in the selection's order (select_query_slots); size and mid = (width,
+        height).  The map holds segment ids 0, 1, .. in acceptance order and -1 for the background, as the reference's does;
+        labels=True writes each segment's slot_label instead.  return_slots: also (slot_segment int32 (K,), slot_pred float32
+        (K,)), the segment id (-1: rejected) and the score of every slot - segments_info, on the device.  Nothing is
+        synchronised."""
+        import torch
+        W, H = int(size[0]), int(size[1])
+        mid_w, mid_h = int(mid[0]), int(mid[1])
+        if min(W, H, mid_w, mid_h) <= 0:
+            raise ValueError(f"size and mid must be positive (got {W} x {H}, {mid_w} x {mid_h})")
+        t, dt = self._seg_input(masks, "masks", (3,))
+        Q, h, w = (int(v) for v in t.shape)
+        dev = t.device
+        sq = torch.as_tensor(slot_query, device=dev).to(torch.int32).reshape(-1).contiguous()
+        ss = torch.as_tensor(slot_score, device=dev).to(torch.float32).reshape(-1).contiguous()
+        K = int(sq.numel())
+        if labels and slot_label is None:
+            raise ValueError("labels=True needs slot_label")
+        sl = None if slot_label is None else torch.as_tensor(slot_label, device=dev).to(torch.int32).reshape(-1).contiguous()
+        if ss.numel() != K or (sl is not None and sl.numel() != K):
+            raise ValueError(f"slot_query, slot_score and slot_label must hold one value per slot ({K})")
+        out = torch.empty((H, W), dtype=torch.int32, device=dev)
+        seg = torch.empty(K, dtype=torch.int32, device=dev) if return_slots else None
+        pred = torch.empty(K, dtype=torch.float32, device=dev) if return_slots else None
+        ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+        ext, cur = self._seg_enter()
+        check(self._lib.gsx_segmap_from_queries(self.h, t.data_ptr(), dt, Q, h, w, K, ptr(sq), ptr(ss), ptr(sl), mid_w, mid_h, float(threshold),
+                                                _lib.GSX_QUERIES_LABELS if labels else _lib.GSX_QUERIES_SEGMENTS, W, H, out.data_ptr(),
+                                                ptr(seg), ptr(pred)), self.h)
+        cur.wait_stream(ext)
+        return (out, seg, pred) if return_slots else out
+
     def synchronize(self):
         check(self._lib.gsx_synchronize(self.h), self.h)
         self._keep_alive.clear()
@@ -1073,6 +1110,14 @@ def segmap_constants():
     check(_lib.lib().gsx_debug_segmap_constants(out.ctypes.data))
     return {"pix_wg": int(out[0]), "slices": int(out[1]), "step": int(out[2]), "vec": int(out[3]), "resize_vec": int(out[4]),
             "resize_block": int(out[5]), "block": int(out[6])}
+
+
+def queries_constants():
+    """Test hook, host only: the units the Mask2Former query kernels are built on (gsx_debug_queries_constants)."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_queries_constants(out.ctypes.data))
+    names = ("cols", "rows_wg", "rows_wave", "scan_word", "accept_waves", "max_slots", "block")
+    return dict(zip(names, (int(v) for v in out)))
 
 
 def segpack_constants():

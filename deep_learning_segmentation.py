@@ -9,10 +9,13 @@ they are in the reference (Hugging Face / Ultralytics models, imported lazily): 
 are fetched by name, so `--segmap_dir` lets a run consume the `<image>_segmap.npy` files the reference
 itself writes next to every segmented image (reference line 165) instead of running a network.  What follows the
 network - arg-max and nearest resize of SegFormer's logits, the compositing of YOLO's instances (reference lines 85-124,
-142-144) - runs in HIP kernels too, and the class map goes from the network to the vote without leaving the GPU.
+142-144), Mask2Former's post_process_instance_segmentation (156-158) - runs in HIP kernels too, and the class map goes from
+the network to the vote without leaving the GPU.
 
 Added flags: --segmap_dir DIR, --n_classes C (default: 150 for the ADE20K models, 80 for YOLO), --gpus N
-(informational).  Several GPUs: `python -m torch.distributed.run --nproc-per-node N deep_learning_segmentation.py
+(informational), --mask2former_map {segments,classes} (default segments: a Mask2Former map holds segment ids in acceptance
+order, as the reference's does; classes: each segment's class id instead).
+Several GPUs: `python -m torch.distributed.run --nproc-per-node N deep_learning_segmentation.py
 ...` — every rank segments and stages its contiguous block of the cameras, the packed class maps are all-gathered over
 RCCL and every rank votes its slab of the Gaussians (3d_gaussian_splatting_project_amd/dist.py, protocol v4).
 --smooth_k N [--smooth_rounds R] [--fill_unlabeled] (default off) cleans the finished labels with the majority filter over
@@ -74,11 +77,24 @@ def initialize_model(model_type, device):
     raise ValueError(f"Unknown model type: {model_type}")
 
 
-def _segment_image_device(image, processor, model, device, model_type, ctx):
+def select_query_slots(class_queries_logits):
+    """The selection of transformers' post_process_instance_segmentation, call for call, on the device the logits are on:
+    class_queries_logits (Q, C + 1) -> (slot_query int64 (Q,), slot_score float32 (Q,), slot_label int64 (Q,)), the Q largest
+    of the Q * C class probabilities in torch's own (unsorted) order.  The same query may fill several slots."""
+    import torch
+    num_queries, num_classes = class_queries_logits.shape[-2], class_queries_logits.shape[-1] - 1
+    scores = torch.nn.functional.softmax(class_queries_logits, dim=-1)[:, :-1]
+    scores_per_image, topk_indices = scores.flatten(0, 1).topk(num_queries, sorted=False)
+    return torch.div(topk_indices, num_classes, rounding_mode="floor"), scores_per_image, topk_indices % num_classes
+
+
+def _segment_image_device(image, processor, model, device, model_type, ctx, mask2former_map="segments", n_classes=None):
     """The device half of segment_image: network -> int32 (H, W) class map as a torch tensor on ctx's GPU, -1 = no class.
-    The network's output never leaves the device: SegFormer logits and YOLO instances go through libgsx's own kernels
-    (Context.segmap_from_logits / segmap_from_masks: torch.argmax's rule, OpenCV's nearest resize, the reference's instance
-    loop - reference lines 85-124, 142-144), Mask2Former's post-processed map is taken as it is."""
+    The network's output never leaves the device: SegFormer logits, YOLO instances and Mask2Former queries go through libgsx's
+    own kernels (Context.segmap_from_logits / segmap_from_masks / segmap_from_queries: torch.argmax's rule, OpenCV's nearest
+    resize, the reference's instance loop, transformers' post_process_instance_segmentation - reference lines 85-124, 142-144,
+    156-158).  mask2former_map: "segments" stores segment ids in acceptance order, as the reference does; "classes" stores each
+    segment's class id.  n_classes: what the vote was begun with - a segment id must fit."""
     import torch
     width, height = image.size
     if model_type == "yolo":
@@ -94,10 +110,13 @@ def _segment_image_device(image, processor, model, device, model_type, ctx):
         outputs = model(**inputs)
     if model_type == "segformer":
         return ctx.segmap_from_logits(outputs.logits[0], (width, height))
-    result = processor.post_process_instance_segmentation(outputs, target_sizes=[(height, width)])[0]
-    seg_dev = result["segmentation"].to(torch.int32)
-    ctx.order_after_torch()                   # torch wrote it on its own stream: the vote's stream waits for that, on the device
-    return seg_dev
+    if mask2former_map not in ("segments", "classes"):
+        raise ValueError(f"Unknown Mask2Former map: {mask2former_map}")
+    slot_query, slot_score, slot_label = select_query_slots(outputs.class_queries_logits[0])
+    if mask2former_map == "segments" and n_classes is not None and int(slot_query.numel()) > n_classes:
+        raise ValueError(f"{int(slot_query.numel())} queries may give as many segment ids: --n_classes must be at least that")
+    return ctx.segmap_from_queries(outputs.masks_queries_logits[0], slot_query, slot_score, (width, height), slot_label=slot_label,
+                                   labels=mask2former_map == "classes")
 
 
 def _save_segmap(image_path, output_dir, seg_map):
@@ -105,7 +124,7 @@ def _save_segmap(image_path, output_dir, seg_map):
     np.save(os.path.join(output_dir, f"{base}_segmap.npy"), seg_map)
 
 
-def segment_image(image_path, output_dir, processor, model, device, model_type, ctx=None):
+def segment_image(image_path, output_dir, processor, model, device, model_type, ctx=None, mask2former_map="segments"):
     """int32 (H, W) class map of one image, -1 = no class; also saved as <image>_segmap.npy (reference line 165).
     The map is made on the GPU (_segment_image_device) and copied down here; assign_labels votes the device map instead and
     copies it down afterwards.  The reference's side-by-side PNG (its lines 198-214) is not written."""
@@ -115,7 +134,7 @@ def segment_image(image_path, output_dir, processor, model, device, model_type, 
     own = ctx is None
     ctx = ctx or gsx.Context()
     try:
-        seg_map = _segment_image_device(image, processor, model, device, model_type, ctx).cpu().numpy()
+        seg_map = _segment_image_device(image, processor, model, device, model_type, ctx, mask2former_map).cpu().numpy()
     finally:
         if own:
             ctx.close()
@@ -130,7 +149,7 @@ def _image_size(path):
 
 
 def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2former", segmap_dir=None, n_classes=None,
-                  ctx=None):
+                  ctx=None, mask2former_map="segments"):
     """Majority-vote label per Gaussian (int32, -1 = never visible), bit-identical to the reference.
 
     Cameras whose `<img_name>.png` is missing from input_dir are skipped with a warning, as in the
@@ -172,7 +191,7 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
             from PIL import Image
             os.makedirs(output_dir, exist_ok=True)
             image = Image.open(img_path)
-            seg_dev = _segment_image_device(image, processor, model, device, model_type, ctx)
+            seg_dev = _segment_image_device(image, processor, model, device, model_type, ctx, mask2former_map, n_classes)
             ctx.vote_view(camera, seg_dev, image.size)          # the map goes from the network to the vote on the device ...
             _save_segmap(img_path, output_dir, seg_dev.cpu().numpy())   # ... and is copied down behind it, for the .npy only
         if world > 1:
@@ -235,6 +254,8 @@ def make_parser():
     parser.add_argument("--model", choices=["segformer", "mask2former", "yolo"], default="mask2former",
                         help="Choose segmentation model: mask2former or yolo")
     parser.add_argument("--segmap_dir", default=None, help="read <img_name>_segmap.npy from here instead of running a model")
+    parser.add_argument("--mask2former_map", choices=["segments", "classes"], default="segments",
+                        help="what a Mask2Former map stores: segment ids in acceptance order, as the reference does, or class ids")
     parser.add_argument("--n_classes", type=int, default=None, help="number of classes (labels -1..C-1)")
     parser.add_argument("--gpus", type=int, default=1, help="GPUs of this node (N>1: launch with torch.distributed.run)")
     parser.add_argument("--smooth_k", type=int, default=0, help="clean the labels with a majority filter over this many nearest "
@@ -269,7 +290,7 @@ def main(argv=None):
     print("Assigning labels...")
     try:
         labels = assign_labels(gaussians, cameras, args.input_dir, args.output_dir, model_type=args.model,
-                               segmap_dir=args.segmap_dir, n_classes=args.n_classes)
+                               segmap_dir=args.segmap_dir, n_classes=args.n_classes, mask2former_map=args.mask2former_map)
     except BaseException:
         _shutdown(failed=True)
         raise

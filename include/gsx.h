@@ -842,6 +842,43 @@ int gsx_segmap_from_masks(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, in
  * steps s, s + slices, .. -, elements per load of those kernels, output pixels per lane and threads per workgroup of the
  * resize kernel, threads per workgroup of the other two, 0 */
 int gsx_debug_segmap_constants(int32_t* out);
+/* replaces dls.py:156-158 after the model call: transformers' post_process_instance_segmentation(outputs, target_sizes=[(out_h,
+ * out_w)]) from the selected slots on, op for op (tests/queries_model.py is the specification).  Runs on the ctx stream like
+ * the two calls above, reads nothing back, synchronises nothing and writes only its outputs.
+ * masks_dev: (Q, h, w) mask logits of gsx_float_dtype dtype, fp16 and bf16 widened to fp32 exactly.  The K slots are what
+ * softmax(class logits)[:, :-1].flatten().topk(Q, sorted=False) selected, in that order: slot_query = index / C,
+ * slot_label = index % C, slot_score; the same query may fill several slots.  (The selection stays with the caller: its order
+ * is torch's own.)  All three are device arrays [K]; slot_label_dev may be NULL in mode GSX_QUERIES_SEGMENTS.
+ *  1. bilinear (h, w) -> (mid_h, mid_w), torch's align_corners=False rule in fp32 per axis: scale = (float)S / D,
+ *     src = max(scale * (d + 0.5f) - 0.5f, 0), i0 = (int)src, i1 = i0 + (i0 < S - 1), l1 = src - i0, l0 = 1 - l1,
+ *     v = ly0 * (lx0 * a00 + lx1 * a01) + ly1 * (lx0 * a10 + lx1 * a11), every product and sum rounded to fp32 (no FMA; torch's
+ *     CPU kernel fuses some, so against torch a pixel with |v| <= 2^-20 max|logit| may differ).  A pixel is set iff v > 0.
+ *  2. pred = slot_score * ((float)sum / ((float)count + 1e-6f)): sum of sigmoid(v) over the set mid-grid pixels, accumulated in
+ *     fp64 in a fixed order and rounded once; count of the set pixels.  A NaN anywhere in the slot's upsampled mask makes pred NaN.
+ *  3. a slot is accepted iff a set pixel lies on a mid-grid column and row the target grid reads (step 5) and
+ *     (double)pred >= threshold.  A slot with slot_query outside [0, Q) is rejected, reads nothing and scores 0.  Segment id =
+ *     the number of accepted slots before it.
+ *  4. each mid-grid pixel takes the highest accepted slot whose bit is set: its segment id (GSX_QUERIES_SEGMENTS, the
+ *     reference's map) or its slot_label (GSX_QUERIES_LABELS); -1 without one.
+ *  5. nearest resize to (out_h, out_w) by torch's rule, min((int)floorf(d * scale), S - 1) with scale = (float)S / D in fp32 -
+ *     not OpenCV's rule above.
+ * slot_segment_dev (int32 [K], the segment id or -1) and slot_pred_score_dev (fp32 [K], pred) may be NULL; together they stand
+ * in for segments_info.  K == 0 writes an all -1 map.
+ * Errors, before anything touches the device: GSX_E_INVALID for a NULL ctx, masks_dev or map_dev, a NULL slot array when K > 0,
+ * a size <= 0, K < 0, an unknown dtype or mode, a pointer not aligned to its element, a non-finite threshold;
+ * GSX_E_UNSUPPORTED for K > 1024 and for Q * h * w, mid_h * mid_w, out_h * out_w or K * mid_h * ceil(mid_w / 64) >= 2^31. */
+typedef enum gsx_queries_mode {
+    GSX_QUERIES_SEGMENTS = 0,
+    GSX_QUERIES_LABELS = 1
+} gsx_queries_mode;
+int gsx_segmap_from_queries(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, int32_t Q, int32_t h, int32_t w,
+                            int32_t K, const int32_t* slot_query_dev, const float* slot_score_dev, const int32_t* slot_label_dev,
+                            int32_t mid_w, int32_t mid_h, double threshold, int32_t mode, int32_t out_w, int32_t out_h,
+                            int32_t* map_dev, int32_t* slot_segment_dev, float* slot_pred_score_dev);
+/* test hook, host only: the units the query kernels are built on, out[8] = mid-grid columns per wave (one bit word), rows per
+ * workgroup of the mask kernel (one partial sum), rows per wave, slots per ballot word of the segment-id scan, waves of the
+ * accept kernel (wave s reduces the slots s, s + waves, ..), the most slots of a call, threads per workgroup of the mask kernel, 0 */
+int gsx_debug_queries_constants(int32_t* out);
 /* test hook, host only: the units the device map pack (gsx_vote_view_device, gsx_vote_views_device, "host_pack" = 0) is built on,
  * out[8] = cells (threads) per workgroup, maps per launch, pixel columns per strip and pixel rows per band of the full-resolution
  * level, cells per strip and cell rows per band of the coarse level, 0, 0 */
@@ -858,7 +895,7 @@ const char* gsx_profile_name(gsx_ctx* ctx, int32_t index);
 int gsx_host_threads(gsx_ctx* ctx);
 /* the pool size a context would choose on its own in this process right now (no context, no GPU needed) */
 int gsx_default_host_threads(void);
-/* name: "vote_fused_labels", "seg_pack", "iou_pack", "iou_pairs", "iou_table", "iou_top_index", "segmap_argmax", "segmap_masks", "segmap_resize", ...; returns launches and total milliseconds since reset */
+/* name: "vote_fused_labels", "seg_pack", "iou_pack", "iou_pairs", "iou_table", "iou_top_index", "segmap_argmax", "segmap_masks", "segmap_resize", "queries_sampled", "queries_mask", "queries_accept", "queries_compose", ...; returns launches and total milliseconds since reset */
 int gsx_profile_get(gsx_ctx* ctx, const char* name, int64_t* launches, double* total_ms);
 
 #ifdef __cplusplus
