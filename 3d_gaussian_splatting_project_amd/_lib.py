@@ -15,6 +15,7 @@ GSX_MASK_U8, GSX_MASK_I32, GSX_MASK_I64, GSX_MASK_F32, GSX_MASK_F64 = 0, 1, 2, 3
 GSX_F32, GSX_F16, GSX_BF16 = 0, 1, 2
 GSX_QUERIES_SEGMENTS, GSX_QUERIES_LABELS = 0, 1
 GSX_SMOOTH_IGNORE, GSX_SMOOTH_FILL_ONLY = 1, 2
+GSX_SPLIT_IGNORE = 1
 
 
 class GsxError(RuntimeError):
@@ -161,6 +162,12 @@ _SIGS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "gsx_smooth_labels_lists": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "gsx_split_labels": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int64)]),
+    "gsx_split_labels_lists": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int64,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "gsx_iou_masks": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsx_iou_masks_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

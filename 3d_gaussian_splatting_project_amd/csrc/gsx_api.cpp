@@ -648,6 +648,25 @@ int gsx_smooth_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* k
     return gsx::guard(c, __func__, [&] { return gsx::smooth_labels_lists(c, n, k, knn, labels, a); });
 }
 
+int gsx_split_labels(gsx_ctx* ctx, int64_t n, const float* points, const int32_t* labels, int32_t k, double max_dist, int64_t min_size,
+                     int32_t max_instances, int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* component_out,
+                     int32_t* instance_label_out, int64_t* instance_size_out, int32_t* instance_rep_out, int32_t* n_instances_out,
+                     int64_t* n_components_out) {
+    CTX_OR_FAIL(ctx);
+    const gsx::SplitArgs a{max_dist, min_size, max_instances, ignore_label, flags, labels_out, component_out, instance_label_out,
+                           instance_size_out, instance_rep_out, n_instances_out, n_components_out};
+    return gsx::guard(c, __func__, [&] { return gsx::split_labels(c, n, points, labels, k, a); });
+}
+int gsx_split_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* knn, const float* points, const int32_t* labels, double max_dist,
+                           int64_t min_size, int32_t max_instances, int32_t ignore_label, int32_t flags, int32_t* labels_out,
+                           int32_t* component_out, int32_t* instance_label_out, int64_t* instance_size_out, int32_t* instance_rep_out,
+                           int32_t* n_instances_out, int64_t* n_components_out) {
+    CTX_OR_FAIL(ctx);
+    const gsx::SplitArgs a{max_dist, min_size, max_instances, ignore_label, flags, labels_out, component_out, instance_label_out,
+                           instance_size_out, instance_rep_out, n_instances_out, n_components_out};
+    return gsx::guard(c, __func__, [&] { return gsx::split_labels_lists(c, n, k, knn, points, labels, a); });
+}
+
 int gsx_iou_masks(gsx_ctx* ctx, int32_t n_masks, const void* const* masks, int32_t mask_dtype, int32_t n_gt, const void* const* gts,
                   int32_t gt_dtype, int32_t h, int32_t w, int64_t* inter_out, int64_t* area_masks_out, int64_t* area_gt_out, double* iou_out) {
     CTX_OR_FAIL(ctx);

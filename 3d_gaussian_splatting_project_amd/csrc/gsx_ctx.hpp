@@ -356,6 +356,12 @@ struct Ctx {
     DevBuf sm_sup, sm_changed;           // int32[n] support; u64: labels the round changed
     DevBuf sm_lists;                     // int32[n][k]: lists handed over by the caller (gsx_smooth_labels_lists)
 
+    // label split (split.hip): buffers only grow
+    DevBuf sp_lab, sp_parent, sp_rep;    // int32[n]: the labels (in the end the instance ids); the union-find forest; rep, -1 = ignored
+    DevBuf sp_size, sp_id, sp_kept;      // u32[n] points per root; int32[n] rep -> instance id, -1 = none; int32[M] the kept reps by rank
+    DevBuf sp_trip, sp_cnt;              // int32[3][n] (rep, size, label) of the roots that reach min_size; u32[2]: triples, roots
+    DevBuf sp_pts, sp_lists;             // float[n][3] in the caller's order (finite max_dist only); int32[n][k] lists handed over by the caller
+
     // IoU evaluation (iou.hip): buffers only grow
     int opt_iou_table_lds = 1;           // label-map tables of up to 40000 entries are counted in LDS per workgroup (0: on the global table)
     DevBuf iou_planes;                   // u64 [masks + ground truths][ceil(h w / 64)]: the bit planes
@@ -471,6 +477,18 @@ struct SmoothArgs {
 };
 int smooth_labels(Ctx* c, int64_t n, const float* points, const int32_t* labels, int64_t k, const SmoothArgs& a);
 int smooth_labels_lists(Ctx* c, int64_t n, int32_t k, const int32_t* knn, const int32_t* labels, const SmoothArgs& a);
+// split.hip: connected components of every label over the k-nearest-neighbour graph
+struct SplitArgs {
+    double max_dist;
+    int64_t min_size;
+    int32_t max_instances, ignore_label, flags;
+    int32_t *labels_out, *component_out, *instance_label_out;
+    int64_t* instance_size_out;
+    int32_t *instance_rep_out, *n_instances_out;
+    int64_t* n_components_out;
+};
+int split_labels(Ctx* c, int64_t n, const float* points, const int32_t* labels, int32_t k, const SplitArgs& a);
+int split_labels_lists(Ctx* c, int64_t n, int32_t k, const int32_t* knn, const float* points, const int32_t* labels, const SplitArgs& a);
 // render_scene.hip: what exists once per scene
 int upload_splats(Ctx* c, int64_t n, const float* xyz, const float* scale, const float* rot, const float* opacity,
                   const float* f_dc, const int32_t* labels);

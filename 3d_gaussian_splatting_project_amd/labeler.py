@@ -369,6 +369,59 @@ class Context:
         return self._smooth(lambda *a: self._lib.gsx_smooth_labels_lists(self.h, len(lab), kk, None if nb is None else nb.ctypes.data, *a),
                             len(lab), lab, rounds, min_votes, ignore_label, fill_only, return_support)
 
+    # -- classes into objects (csrc/split.hip): connected components of every label over the k-nearest-neighbour graph --------
+    def _split(self, call, n, labels, max_dist, min_size, max_instances, ignore_label, return_components):
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if len(lab) != n:
+            raise ValueError("labels must hold one entry per point")
+        flags = _lib.GSX_SPLIT_IGNORE if ignore_label is not None else 0
+        out, comp = np.empty(n, np.int32), np.empty(n, np.int32) if return_components else None
+        t_label, t_size, t_rep = np.empty(n, np.int32), np.empty(n, np.int64), np.empty(n, np.int32)
+        m, ncomp = C.c_int32(0), C.c_int64(0)
+        check(call(lab.ctypes.data, float("inf") if max_dist is None else float(max_dist), int(min_size), int(max_instances),
+                   int(ignore_label or 0), flags, out.ctypes.data, comp.ctypes.data if return_components else None, t_label.ctypes.data,
+                   t_size.ctypes.data, t_rep.ctypes.data, C.byref(m), C.byref(ncomp)), self.h)
+        self.split_components = int(ncomp.value)
+        m = int(m.value)
+        table = {"label": t_label[:m].copy(), "size": t_size[:m].copy(), "rep": t_rep[:m].copy()}
+        return (out, table, comp) if return_components else (out, table)
+
+    def split_labels(self, points, labels, k=16, max_dist=None, min_size=1, max_instances=0, ignore_label=None, return_components=False):
+        """gsx_split_labels (include/gsx.h): the connected components of every label over the exact k-nearest-neighbour graph,
+        as instance ids - the largest component is 0; components below min_size or behind max_instances, and points whose label
+        is ignore_label, get -1.  max_dist: neighbours farther apart are not joined (None: no cut).  Returns (labels int32 (n,),
+        table) - table = {"label", "size", "rep"}, one entry per instance - plus the representatives int32 (n,) with
+        return_components; self.split_components = components before the size filter."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        return self._split(lambda *a: self._lib.gsx_split_labels(self.h, len(pts), pts.ctypes.data, a[0], int(k), *a[1:]), len(pts), labels,
+                           max_dist, min_size, max_instances, ignore_label, return_components)
+
+    def split_labels_lists(self, knn, labels, points=None, max_dist=None, min_size=1, max_instances=0, ignore_label=None,
+                           return_components=False, k=None):
+        """gsx_split_labels_lists: the same over neighbour lists int32 (n, k <= 64) - or, with knn None, over the device lists
+        the last knn / region_growing / smooth_labels / split_labels call left on this context (their k must be given).  points
+        are needed only with a max_dist."""
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if knn is None:
+            if k is None:
+                raise ValueError("knn is None: k of the context's device lists is needed")
+            nb, kk = None, int(k)
+        else:
+            nb = np.ascontiguousarray(knn, np.int32)
+            if nb.ndim != 2 or len(nb) != len(lab):
+                raise ValueError("knn (n, k) and labels (n,) must agree in n")
+            kk = nb.shape[1]
+        pts = None
+        if points is not None:
+            pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            if len(pts) != len(lab):
+                raise ValueError("points (n, 3) and labels (n,) must agree in n")
+        elif max_dist is not None and np.isfinite(max_dist):
+            raise ValueError("max_dist needs points")
+        return self._split(lambda *a: self._lib.gsx_split_labels_lists(self.h, len(lab), kk, None if nb is None else nb.ctypes.data,
+                                                                       None if pts is None else pts.ctypes.data, *a),
+                           len(lab), lab, max_dist, min_size, max_instances, ignore_label, return_components)
+
     # -- exchange protocol v4 (see include/gsx.h) ------------------------------------------------------------------------
     def vote_num_views(self):
         return int(self._lib.gsx_vote_num_views(self.h))

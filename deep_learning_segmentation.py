@@ -21,6 +21,9 @@ RCCL and every rank votes its slab of the Gaussians (3d_gaussian_splatting_proje
 --smooth_k N [--smooth_rounds R] [--fill_unlabeled] (default off) cleans the finished labels with the majority filter over
 the N nearest neighbours (3D_clustering/smooth_labels.py) before the file is written; --fill_unlabeled only fills the
 Gaussians no view saw.
+--split_k N [--split_max_dist D] [--split_min_size S] [--split_max_instances M] (default off) then turns the classes into
+objects: the connected components of every label over the N nearest neighbours (3D_clustering/split_labels.py), -1 ignored;
+the largest object gets id 0 and the instance table is printed.
 """
 import argparse
 import importlib
@@ -263,7 +266,24 @@ def make_parser():
     parser.add_argument("--smooth_rounds", type=int, default=1, help="rounds of that filter")
     parser.add_argument("--fill_unlabeled", action="store_true", help="the filter only fills Gaussians no view saw (label -1), "
                         "from their labelled neighbours")
+    parser.add_argument("--split_k", type=int, default=0, help="split every label into its connected components over this many "
+                        "nearest neighbours, largest first (0: off)")
+    parser.add_argument("--split_max_dist", type=float, default=None, help="neighbours farther apart than this are not joined")
+    parser.add_argument("--split_min_size", type=int, default=1, help="components of fewer Gaussians become -1")
+    parser.add_argument("--split_max_instances", type=int, default=0, help="keep only this many of the largest components (0: all)")
     return parser
+
+
+def split_labels(gaussians, labels, k, max_dist=None, min_size=1, max_instances=0):
+    """Classes into objects (Context.split_labels) over the finished labels, the unlabelled Gaussians (-1) left out; prints
+    the instance table."""
+    with gsx.Context() as ctx:
+        labels, table = ctx.split_labels(gaussians["position"], labels, k=min(int(k), len(labels)), max_dist=max_dist, min_size=min_size,
+                                         max_instances=max_instances, ignore_label=-1)
+    print(f"{len(table['size'])} instances:")
+    for m, (lab, size) in enumerate(zip(table["label"], table["size"])):
+        print(f"Instance {m}: label {lab}, {size} gaussians")
+    return labels
 
 
 def smooth_labels(gaussians, labels, k, rounds=1, fill_unlabeled=False):
@@ -282,6 +302,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.fill_unlabeled and args.smooth_k <= 0:
         parser.error("--fill_unlabeled needs --smooth_k")
+    if args.split_k <= 0 and (args.split_max_dist is not None or args.split_min_size != 1 or args.split_max_instances != 0):
+        parser.error("--split_max_dist, --split_min_size and --split_max_instances need --split_k")
 
     print("Loading cameras...")
     cameras = load_cameras(args.camera_file)
@@ -300,6 +322,9 @@ def main(argv=None):
     if args.smooth_k > 0:
         print("Smoothing labels...")
         labels = smooth_labels(gaussians, labels, args.smooth_k, args.smooth_rounds, args.fill_unlabeled)
+    if args.split_k > 0:
+        print("Splitting labels into instances...")
+        labels = split_labels(gaussians, labels, args.split_k, args.split_max_dist, args.split_min_size, args.split_max_instances)
     print("Saving labeled PLY file...")
     save_labeled_ply(args.output_file, plydata, labels)
     print(f"Done! Labeled PLY file saved as {args.output_file}")

@@ -694,7 +694,8 @@ int gsx_debug_nn_grid(int64_t n, const float* points, int64_t k, int brute, doub
  * stay on the device. */
 int gsx_knn(gsx_ctx* ctx, int64_t n, const float* points, int32_t k, int32_t* index_out);
 /* device pointer of the int32[n][k] lists of the last successful gsx_knn (NULL: none); valid until the next gsx_knn /
- * gsx_region_growing / gsx_smooth_labels on the ctx (the last builds lists of its own when its k <= 64) */
+ * gsx_region_growing / gsx_smooth_labels / gsx_split_labels on the ctx (gsx_smooth_labels builds lists of its own when its
+ * k <= 64, gsx_split_labels always: they replace the context's lists) */
 void* gsx_knn_device(gsx_ctx* ctx);
 /* segmentation_3D (rg.py:166-226) on the host; needs no ctx and no GPU (errors: gsx_last_error(NULL)).
  * normals double[n][3], residuals double[n], knn int32[n][k] (row i = the neighbours of i in visiting order).
@@ -755,6 +756,56 @@ int gsx_smooth_labels(gsx_ctx* ctx, int64_t n, const float* points, const int32_
 int gsx_smooth_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* knn, const int32_t* labels, int32_t rounds,
                             int32_t min_votes, int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* support_out,
                             int64_t* changed_out, int32_t* rounds_done_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * class labels into object instances: connected components of every label over the k-nearest-neighbour graph.  The viewer
+ * works on one label value at a time (gsx_render_set_edits, gsx_hit_test, GSX_EDIT_TABLE_MAX entries), but SegFormer and
+ * `--mask2former_map classes` give semantic classes: every chair of a scene carries one value, and a k-means cluster can hold
+ * pieces that do not touch.  The reference has no step that turns a class into objects; the rule below is the contract.  It
+ * is all integers plus one fp64 compare.
+ * points: n x 3 float32, row-major, on the host; labels int32[n], any values; flags: GSX_SPLIT_IGNORE.
+ * N(i) = the k nearest points of i, exactly the set and order gsx_knn returns.
+ * Edge: points i and j (i != j) are joined iff all of
+ *   - j is in N(i) or i is in N(j) (the closure is symmetric: one direction is enough);
+ *   - labels[i] == labels[j];
+ *   - neither label is ignored - a label is ignored only with GSX_SPLIT_IGNORE set and label == ignore_label;
+ *   - d2(i, j) <= r2, with d2 = (dx*dx + dy*dy) + dz*dz in fp64 of the widened coordinates without FMA (the expression of
+ *     gsx_knn's search, symmetric in i and j) and r2 = max_dist * max_dist, one fp64 product taken on the host.
+ *     max_dist = +inf means no cut.
+ * Component: a connected component of that graph over the non-ignored points; an isolated point is a component of size 1.
+ * rep(i) = the smallest index in i's component, size = its number of points.  component_out[i] = rep(i), -1 for an ignored
+ * point.
+ * Instances: the components with size >= min_size, ranked by size descending, then rep ascending; with max_instances > 0 only
+ * the first max_instances of them.  Instance id = rank, 0 .. M-1.
+ * labels_out[i] = the instance id of i's component; -1 for ignored points, for components below min_size and for components
+ * cut by max_instances (gsx_smooth_labels with GSX_SMOOTH_IGNORE | GSX_SMOOTH_FILL_ONLY repairs those).  labels_out int32[n] is
+ * required and may be `labels` itself.  instance_label_out[m], instance_size_out[m], instance_rep_out[m] = the original
+ * label, size and rep of instance m < M; the caller sizes each for n entries (int32[n] / int64[n] / int32[n]); each may be
+ * NULL, as may component_out.  *n_instances_out = M; *n_components_out = the number of components before the size filter.
+ * The result is a pure function of the inputs: it does not depend on the order in which the GPU joins things.
+ * gsx_split_labels: 2 <= k <= min(64, n); the lists are built as by gsx_knn and replace the context's lists (see
+ * gsx_knn_device).
+ * Every error returns before any launch.  GSX_E_INVALID: a NULL points, labels or labels_out, n < 1, k out of range,
+ * min_size < 1, max_instances < 0, max_dist NaN or <= 0, unknown flag bits, a non-finite coordinate.
+ * GSX_E_UNSUPPORTED: n > 2^31-1.
+ * ------------------------------------------------------------------------------------------- */
+#define GSX_SPLIT_IGNORE 1
+int gsx_split_labels(gsx_ctx* ctx, int64_t n, const float* points, const int32_t* labels, int32_t k, double max_dist,
+                     int64_t min_size, int32_t max_instances, int32_t ignore_label, int32_t flags, int32_t* labels_out,
+                     int32_t* component_out, int32_t* instance_label_out, int64_t* instance_size_out,
+                     int32_t* instance_rep_out, int32_t* n_instances_out, int64_t* n_components_out);
+/* the same over given neighbour lists, 1 <= k <= min(64, n).  knn: host int32[n][k] with every index in [0, n) - the lists
+ * need not come from a search: a row may repeat an index, and may name the point itself (a self loop is no edge) - or NULL:
+ * the device lists of the last gsx_knn / gsx_region_growing / gsx_smooth_labels (k <= 64) / gsx_split_labels on the ctx, whose
+ * n and k must be these.  points may be NULL iff max_dist is +inf; given points are checked for finiteness either way.
+ * GSX_E_INVALID as above (NULL points only with a finite max_dist), and for a list index outside [0, n) (the text names row
+ * and column; nothing is launched); GSX_E_STATE: knn == NULL without device lists of this n and k; GSX_E_UNSUPPORTED:
+ * n > 2^31-1. */
+int gsx_split_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* knn, const float* points, const int32_t* labels,
+                           double max_dist, int64_t min_size, int32_t max_instances, int32_t ignore_label, int32_t flags,
+                           int32_t* labels_out, int32_t* component_out, int32_t* instance_label_out,
+                           int64_t* instance_size_out, int32_t* instance_rep_out, int32_t* n_instances_out,
+                           int64_t* n_components_out);
 
 /* ---------------------------------------------------------------------------------------------
  * IoU evaluation of 2-D segmentations: Image_Segmentation/evaluation.py ("ev.py").  Everything is counted in
