@@ -137,7 +137,15 @@ _SIGS = {
     "gsx_render_debug": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4),
     "gsx_debug_render_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "gsx_debug_render_pre": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "gsx_ply_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "gsx_lift_begin": (C.c_int, [C.c_void_p, C.c_int32]),
+    "gsx_lift_view": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "gsx_lift_view_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "gsx_lift_num_views": (C.c_int32, [C.c_void_p]),
+    "gsx_lift_num_atomics": (C.c_int64, [C.c_void_p]),
+    "gsx_lift_finalize": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "gsx_lift_table": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gsx_debug_lift_constants": (C.c_int, [C.c_void_p]),
+    "gsx_ply_open":(C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "gsx_ply_close": (None, [C.c_void_p]),
     "gsx_ply_num_vertices": (C.c_int64, [C.c_void_p]),
     "gsx_ply_num_properties": (C.c_int32, [C.c_void_p]),

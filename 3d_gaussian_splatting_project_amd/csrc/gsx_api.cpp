@@ -539,6 +539,7 @@ int gsx_vote_debug_planes(gsx_ctx* ctx, uint16_t* counts_out, uint16_t* first_ou
 int gsx_upload_splats(gsx_ctx* ctx, int64_t n, const float* xyz, const float* scale, const float* rot,
                       const float* opacity, const float* f_dc, const int32_t* labels) {
     CTX_OR_FAIL(ctx);
+    gsx::lift_end(c);  // a lift run's table belongs to the splats that go away here
     return gsx::guard(c, __func__, [&] { return gsx::upload_splats(c, n, xyz, scale, rot, opacity, f_dc, labels); });
 }
 int gsx_upload_sh(gsx_ctx* ctx, const float* f_rest, int32_t sh_degree) {
@@ -731,6 +732,39 @@ int gsx_segmap_from_queries(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, 
 int gsx_debug_queries_constants(int32_t* out) {
     if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_queries_constants: NULL argument");
     gsx::queries_constants(out);
+    return GSX_OK;
+}
+int gsx_lift_begin(gsx_ctx* ctx, int32_t n_classes) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::lift_begin(c, n_classes); });
+}
+int gsx_lift_view(gsx_ctx* ctx, const gsx_camera* cam, const void* seg, int32_t seg_dtype, int32_t width, int32_t height) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::lift_view(c, cam, seg, seg_dtype, width, height, false); });
+}
+int gsx_lift_view_device(gsx_ctx* ctx, const gsx_camera* cam, const void* seg_dev, int32_t seg_dtype, int32_t width, int32_t height) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::lift_view(c, cam, seg_dev, seg_dtype, width, height, true); });
+}
+int32_t gsx_lift_num_views(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c && c->lift.begun ? c->lift.views : 0;
+}
+int64_t gsx_lift_num_atomics(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c ? (int64_t)c->lift.atomics : 0;
+}
+int gsx_lift_finalize(gsx_ctx* ctx, double min_weight, int32_t* labels_out, double* share_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::lift_finalize(c, min_weight, labels_out, share_out); });
+}
+int gsx_lift_table(gsx_ctx* ctx, uint64_t* table_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::lift_table(c, table_out); });
+}
+int gsx_debug_lift_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_lift_constants: NULL argument");
+    gsx::lift_constants(out);
     return GSX_OK;
 }
 int gsx_debug_segpack_constants(int32_t* out) {

@@ -115,6 +115,27 @@ static constexpr int kLabelChunks = 4;
 static constexpr int kConsumedSlots = 64;  // rasterizer statistics: the blend kernels' "pairs staged" counter, one slot per 128-B line
 static constexpr int kNoBadView = 0x7f7f7f7f;  // errflag value meaning "every device-side map was in range"
 
+// A frame's counters (RenderFrame::small), zeroed when the frame starts and read back when it ends.  The kernels get pointers
+// into it; the layout is what it has always been.
+constexpr int kMaxPhases = 8;
+struct FrameCounters {
+    int unused0[2];
+    int dropped;                          // bucket_kernel: splats outside the 16-bit bucket range (the blend's epilogue draws them)
+    int unused1[3];
+    unsigned long long pairs[kMaxPhases]; // the scan's grand total of phase p: its (list, splat) pairs
+    unsigned long long unused2;
+    unsigned long long nvis;              // splats the level-1 sort kept (those with a rectangle in this view)
+    unsigned long long unused3[19];
+    struct alignas(128) Slot {
+        unsigned long long n;
+        unsigned long long atomics;       // lift_kernel: global atomics it issued (same line, same spreading)
+    } consumed[kConsumedSlots];           // pairs the blend kernels staged: one counter per 128-B line (summed at the end of the frame)
+};
+static_assert(offsetof(FrameCounters, dropped) == 8 && offsetof(FrameCounters, pairs) == 24 && offsetof(FrameCounters, nvis) == 96 &&
+                  offsetof(FrameCounters, consumed) == 256 && sizeof(FrameCounters::Slot) == 128 &&
+                  sizeof(FrameCounters) == 256 + (size_t)kConsumedSlots * 128,
+              "FrameCounters layout");
+
 struct ProfEvent {
     int name_id;
     hipEvent_t start, stop;
@@ -231,6 +252,31 @@ struct RenderFrame {
     int pre_ext = -1;                  // >= 0: this frame's pre pass has been run for it into sets[pre_ext] (render_view skips its own)
 };
 
+// A frame up to and including its per-list ranges (render.hip: frame_plan / frame_depth_order / frame_phase_lists): what
+// gsx_render_view and a lift frame (lift.hip) share.  Plain data, filled by frame_plan.
+struct FramePlan {
+    int W = 0, H = 0, tiles_x = 0, tiles_y = 0, ntiles = 0;
+    int nlists = 0;                    // lists the pairs are sorted into: tiles, or 32x32-pixel bins
+    int tile_bits = 1, K = 1;          // key bits of a list index; depth phases
+    bool bin32 = false, wide = false, ext_pre = false;
+    size_t sat_bytes = 0;
+    long long n = 0;
+    long long divs[kMaxPhases + 1] = {};  // phase p = [nvis / divs[p], nvis / divs[p + 1]); divs[0] = 0 stands for the start
+    const uint32_t* by_depth = nullptr;   // the splats front to back (frame_depth_order)
+};
+
+// State of a lift run (lift.hip): gsx_lift_begin .. the next gsx_upload_splats
+struct LiftState {
+    bool begun = false;
+    int n_classes = 0, views = 0;
+    DevBuf table;                      // u64 [n][n_classes + 1], rows in importance order
+    DevBuf bins;                       // u8 [H][W]: the view's map, bin = label + 1
+    DevBuf raw;                        // a host map on its way to the narrowing kernel
+    DevBuf flag;                       // int: smallest view whose device map held a label out of range (kNoBadView: none)
+    DevBuf out;                        // finalize: int32 labels [n] | double shares [n], upload order
+    unsigned long long atomics = 0;    // global atomics lift_kernel issued for the last view
+};
+
 struct Ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -334,6 +380,7 @@ struct Ctx {
     RenderScene scene;
     RenderOpts ropt;
     RenderFrame frame;
+    LiftState lift;
     // gsx_render_views: further streams + per-frame buffers.  A twin is a whole Ctx because sort.hip, ProfScope and fail take
     // one; what it uses of it is stream, sort_hist, err, scene (aliases of this context's), ropt (a copy) and frame
     Ctx* twins[kMaxFrames - 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -508,6 +555,11 @@ int debug_render_pre(Ctx* c, int nv, const gsx_camera* cams, int W, int H, int m
 int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out);
 int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* const* rgba_out);
 void render_release_twin(Ctx* c);
+// the frame's shared front: geometry + buffers; then per attempt the pre pass, buckets and level-1 sort; then per depth phase
+// bin COUNT -> scan -> EMIT, the pair sort and the ranges (*vals_sorted: the list entries the ranges index)
+int frame_plan(Ctx* c, int W, int H, bool allow_bin32, int phases, FramePlan& fp);
+int frame_depth_order(Ctx* c, const gsx_camera* cam, FramePlan& fp);
+int frame_phase_lists(Ctx* c, const FramePlan& fp, int p, int first_phase, const uint32_t** vals_sorted);
 int debug_exclusive_scan(Ctx* c, const uint32_t* in, uint32_t* out, long long n, unsigned long long* grand_dev);  // test hook: exclusive_scan_u32
 int debug_ranges(Ctx* c, const uint32_t* keys, const unsigned long long* total_dev, long long cap, int nlists, int2* ranges);  // test hook: ranges_kernel as a frame launches it
 // bin_kernel COUNT -> exclusive_scan_u32 -> bin_kernel EMIT of one depth phase (device pointers): what render_view launches per
@@ -528,6 +580,13 @@ int debug_bin(Ctx* c, const BinPhaseArgs& a);
 // blend.hip
 int launch_blend(Ctx* c, const uint32_t* vals, int W, int H, int tiles_x, int tiles_y, const int* dropped_dev,
                  unsigned long long* consumed_dev, uint8_t* sat, int first_phase, int last_phase);
+// lift.hip: per-splat, per-class blend weights of class maps, and their arg-max
+int lift_begin(Ctx* c, int n_classes);
+int lift_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int W, int H, bool device);
+int lift_finalize(Ctx* c, double min_weight, int32_t* labels_out, double* share_out);
+int lift_table(Ctx* c, uint64_t* table_out);
+void lift_end(Ctx* c);             // a new upload ends the run
+void lift_constants(int32_t out[8]);
 // iou.hip
 int iou_masks(Ctx* c, bool device, int n_masks, const void* const* masks, int mask_dtype, int n_gt, const void* const* gts, int gt_dtype,
               int h, int w, int64_t* inter_out, int64_t* area_masks_out, int64_t* area_gt_out, double* iou_out);

@@ -1,0 +1,447 @@
+// lift.hip - the lifting labeler: 2-D class maps lifted onto the splats through the rasterizer's own blend.
+//
+// For a view (cam, W, H) and an H x W class map the frame is walked exactly as gsx_render_view walks it - the same pre pass,
+// depth order and per-tile lists (render.hip: frame_plan / frame_depth_order / frame_phase_lists, one depth phase, 16x16 tiles),
+// the same `discard` rule and ONE_MINUS_DST_ALPHA, ONE blend (blend.hip: blend_one, whose operation order lift_fragment keeps;
+// compiled with -ffp-contract=off like it).  The k-th fragment at pixel p, made by splat i, raises the frame's alpha by
+//     w = (1 - dst.a) * B,   B = exp(A) * alpha
+// and the view adds q = rint(w * 2^20) to table[i][map[p] + 1].  The table is u64 [n][n_classes + 1]; integer sums do not
+// depend on the order in which they arrive, so a table is reproducible bit for bit and two views accumulated together are the
+// sum of their tables (float atomics give neither: a float sum depends on the order of arrival).
+//
+// On-chip reduction.  A record (one splat in one tile's list) would cost up to 256 atomics, one per pixel.  lift_kernel sums a
+// record's q over the tile's pixels per class first - a wave reduction, then LDS adds across the four waves - and issues at
+// most ONE 64-bit global atomic per (record, class present in the tile), none for a zero sum.  The classes present in the tile
+// are found once per tile; a wave whose 64 pixels share a class (the common case of a real segmentation) takes one full-wave
+// reduction per record and no per-class loop.  The rate of 64-bit integer atomics on this GPU is not measured anywhere we know
+// of (published figures are for float atomics); tools/lift_bench.py reports how many a view issues next to its time.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "gsx_ctx.hpp"
+#include "render_device.hpp"
+
+namespace gsx {
+
+static constexpr int kLiftShift = 20;
+static constexpr int kLiftOne = 1 << kLiftShift;  // GSX_LIFT_ONE: the fixed-point weight 1.0
+static constexpr int kLiftTile = 16;
+static constexpr int kLiftThreads = kLiftTile * kLiftTile;
+static constexpr int kLiftChunk = 256;   // records staged through LDS at a time, and between two opacity votes (blend_kernel's)
+static constexpr int kLiftCells = 2048;  // LDS accumulators: (records of a round) x (classes present in the tile)
+static constexpr int kLiftLoopMax = 4;   // a mixed wave with up to this many classes reduces per class; with more, its lanes add to LDS
+static constexpr int kLiftMaxBins = 256;
+static_assert(kLiftCells >= kLiftMaxBins && kLiftCells % kLiftThreads == 0, "a round holds at least one record");
+static_assert(kLiftThreads == 256 && kLiftChunk == kLiftThreads, "one staged record per thread; four waves");
+
+void lift_constants(int32_t out[8]) {
+    const int32_t v[8] = {kLiftOne, kLiftShift, kLiftTile, kLiftChunk, kLiftCells, kLiftLoopMax, kLiftMaxBins - 1, 0};
+    for (int k = 0; k < 8; ++k) out[k] = v[k];
+}
+
+// ---- the view's map as one u8 bin per pixel ---------------------------------------------------------------------------------
+// bin = label + 1 (0 = label -1).  A label outside [-1, n_classes - 1] becomes bin 0 and records the view in *flag (host maps
+// are checked before anything is launched and never get here with one).
+template <typename T, int DTYPE>
+__global__ __launch_bounds__(kRB) void lift_narrow_kernel(const T* __restrict__ seg, long long npix, int n_classes, int view,
+                                                           uint8_t* __restrict__ bins, int* __restrict__ flag) {
+    const long long p = (long long)blockIdx.x * kRB + threadIdx.x;
+    if (p >= npix) return;
+    const long long v = (long long)seg[p];
+    const long long b = DTYPE == GSX_SEG_U8 ? v : v + 1;
+    const long long lo = DTYPE == GSX_SEG_U8_LABELS ? 1 : 0;
+    const bool ok = b >= lo && b <= (long long)n_classes;
+    bins[p] = ok ? (uint8_t)b : (uint8_t)0;
+    if (!ok) atomicMin(flag, view);
+}
+
+template <typename T, int DTYPE>
+static long long host_first_bad(const void* seg, long long npix, int n_classes) {
+    const T* s = static_cast<const T*>(seg);
+    const long long lo = DTYPE == GSX_SEG_U8_LABELS ? 1 : 0;
+    for (long long p = 0; p < npix; ++p) {
+        const long long b = DTYPE == GSX_SEG_U8 ? (long long)s[p] : (long long)s[p] + 1;
+        if (b < lo || b > (long long)n_classes) return p;
+    }
+    return -1;
+}
+
+// ---- the kernel -------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// blend_one's alpha channel, operation for operation: -> the fragment's weight (0: discarded), dst.a updated
+__device__ __forceinline__ float lift_fragment(float& a, float fxp, float fyp, const float4 r0, const float4 r1, float alpha) {
+    const float dx = fxp - r0.x;
+    const float dy = fyp - r0.y;
+    const float vx = dx * r0.z + dy * r0.w;
+    const float vy = dx * r1.x + dy * r1.y;
+    const float A = -(vx * vx + vy * vy);
+    float w = 0.0f;
+    if (!(A < -4.0f)) {  // `if (A < -4.0) discard;`
+        const float B = __expf(A) * alpha;
+        const float om = 1.0f - a;  // ONE_MINUS_DST_ALPHA, ONE
+        w = om * B;
+        a = __builtin_fmaf(om, B, a);
+    }
+    return w;
+}
+
+// rank of bit v among the set bits of the 256-bit mask pw
+__device__ __forceinline__ uint32_t rank256(const uint32_t pw[8], uint32_t v) {
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) {
+        const uint32_t m = j < (v >> 5) ? 0xffffffffu : j == (v >> 5) ? ((1u << (v & 31u)) - 1u) : 0u;
+        r += (uint32_t)__popc(pw[j] & m);
+    }
+    return r;
+}
+
+// One workgroup per 16x16 tile, modelled on blend_kernel: 256 records staged through LDS at a time, every pixel walks them
+// carrying only dst.a; the opacity vote falls after every staged chunk.  Pixels outside the frame contribute 0 and count as
+// opaque.  A chunk is walked in ROUNDS of `sub` records, sub * (classes in the tile) <= kLiftCells accumulators: up to 8
+// classes in a tile a round is the whole chunk; the worst case (255 classes in 256 pixels) walks 8 records per round - correct,
+// slow.  No lane leaves before the last barrier: a tile without a list returns as a whole, before the first one.
+__global__ __launch_bounds__(kLiftThreads) void lift_kernel(const int2* __restrict__ ranges, const uint32_t* __restrict__ vals,
+                                                            const float4* __restrict__ rec, const uint8_t* __restrict__ bins,
+                                                            int W, int H, int tiles_x, int nbins,
+                                                            unsigned long long* __restrict__ table,
+                                                            unsigned long long* __restrict__ consumed) {
+    __shared__ float4 s0[kLiftChunk];
+    __shared__ float4 s1[kLiftChunk];
+    __shared__ float sa[kLiftChunk];
+    __shared__ uint32_t sid[kLiftChunk];
+    __shared__ uint32_t cells[kLiftCells];
+    __shared__ uint32_t present[8];
+    __shared__ uint8_t tile_bin[kLiftMaxBins];  // class index in the tile -> bin
+    __shared__ uint8_t wlist[4][64];            // a mixed wave's class indices
+    __shared__ uint32_t natom;
+    const int tile = (int)blockIdx.x;
+    const int2 range = ranges[tile];
+    if (range.y <= range.x) return;  // (workgroup-uniform)
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int px = tx * kLiftTile + (tid & (kLiftTile - 1));
+    const int py = ty * kLiftTile + (tid >> 4);
+    const bool inside = px < W && py < H;
+    const float fxp = (float)px + 0.5f;               // pixel centre, GL window coordinates
+    const float fyp = (float)H - ((float)py + 0.5f);  // window y is up; image row py counts from the top
+    if (tid < 8) present[tid] = 0u;
+    if (tid == 0) natom = 0u;
+    for (int i = tid; i < kLiftCells; i += kLiftThreads) cells[i] = 0u;
+    __syncthreads();
+    // the tile's classes, once: a 256-bit mask of the bins present, a pixel's class index = the rank of its bin
+    const uint32_t b = inside ? (uint32_t)bins[(size_t)py * W + px] : 0u;
+    if (inside) atomicOr(&present[b >> 5], 1u << (b & 31u));
+    __syncthreads();
+    uint32_t pw[8];
+    int D = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        pw[j] = present[j];
+        D += __popc(pw[j]);
+    }
+    if ((present[tid >> 5] >> (tid & 31)) & 1u) tile_bin[rank256(pw, (uint32_t)tid)] = (uint8_t)tid;
+    // the wave's classes, once: lanes outside the frame never add anything and take the class of the wave's first pixel inside
+    uint32_t ci = inside ? rank256(pw, b) : 0u;
+    const unsigned long long in_mask = __ballot(inside);
+    const uint32_t wc = in_mask ? (uint32_t)__shfl((int)ci, __ffsll((long long)in_mask) - 1) : 0u;
+    if (!inside) ci = wc;
+    const bool uniform = __all(ci == wc) != 0;
+    int wcount = 1;
+    if (!uniform) {  // (wave-uniform)
+        wcount = 0;
+        unsigned long long left = ~0ull;
+        while (left) {
+            const uint32_t d = (uint32_t)__shfl((int)ci, __ffsll((long long)left) - 1);
+            left &= ~__ballot(ci == d);
+            if (lane == 0) wlist[wave][wcount] = (uint8_t)d;
+            ++wcount;
+        }
+    }
+    const int sub = min(kLiftChunk, kLiftCells / D);  // D >= 1: the tile has a pixel inside the frame
+    float a = 0.0f;                                   // gl.clear to (0,0,0,0): only dst.a is carried
+    uint32_t my_atoms = 0u;
+    int staged = 0;
+    for (int base = range.x; base < range.y; base += kLiftChunk) {
+        const int cnt = min(kLiftChunk, range.y - base);
+        __syncthreads();
+        if (tid < cnt) {
+            const uint32_t id = vals[base + tid];
+            s0[tid] = rec[3 * (size_t)id];
+            s1[tid] = rec[3 * (size_t)id + 1];
+            sa[tid] = reinterpret_cast<const float2*>(rec + 3 * (size_t)id + 2)->y;
+            sid[tid] = id;
+        }
+        __syncthreads();
+        for (int r0 = 0; r0 < cnt; r0 += sub) {
+            const int r1 = min(cnt, r0 + sub);
+            for (int k = r0; k < r1; ++k) {
+                const float w = lift_fragment(a, fxp, fyp, s0[k], s1[k], sa[k]);
+                const uint32_t q = inside && w > 0.0f ? (uint32_t)rintf(w * (float)kLiftOne) : 0u;  // <= 2^20: w <= 1
+                if (__ballot(q != 0u) == 0ull) continue;  // (wave-uniform) the record puts nothing on this wave's pixels
+                uint32_t* row = cells + (k - r0) * D;
+                if (uniform) {
+                    const uint32_t s = wave_sum_u32(q);  // <= 2^26 per wave, <= 2^28 per cell
+                    if (lane == 0) atomicAdd(&row[wc], s);
+                } else if (wcount <= kLiftLoopMax) {
+                    for (int j = 0; j < wcount; ++j) {
+                        const uint32_t d = wlist[wave][j];
+                        const uint32_t s = wave_sum_u32(ci == d ? q : 0u);
+                        if (lane == 0 && s) atomicAdd(&row[d], s);
+                    }
+                } else if (q) {
+                    atomicAdd(&row[ci], q);
+                }
+            }
+            __syncthreads();
+            // the round's sums leave the chip: one atomic per (record, class) that got anything
+            const int ncell = (r1 - r0) * D;
+            for (int i = tid; i < ncell; i += kLiftThreads) {
+                const uint32_t v = cells[i];
+                if (v) {
+                    cells[i] = 0u;
+                    const int r = i / D, d = i - r * D;
+                    atomicAdd(&table[(size_t)sid[r0 + r] * (size_t)nbins + tile_bin[d]], (unsigned long long)v);
+                    ++my_atoms;
+                }
+            }
+            __syncthreads();
+        }
+        staged += cnt;
+        // every further fragment is weighted by (1 - dst.a): the frame's rule, a tile stops once that is < 1e-5 on all of it
+        if (__syncthreads_and(!inside || a > 1.0f - 1.0e-5f)) break;
+    }
+    // statistics, spread over kConsumedSlots lines like the blend kernels': records staged, global atomics issued
+    if (my_atoms) atomicAdd(&natom, my_atoms);
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long* slot = consumed + (blockIdx.x & (kConsumedSlots - 1)) * 16;
+        atomicAdd(slot, (unsigned long long)staged);
+        if (natom) atomicAdd(slot + 1, (unsigned long long)natom);
+    }
+}
+
+// ---- the arg-max --------------------------------------------------------------------------------------------------------------
+// Per splat: total < threshold -> -1; else the largest bin, the lowest on a tie (bin 0 = label -1 can win).  Integers only; the
+// share is one fp64 division.  Row j of the table is importance-order slot j, order[j] its index in the upload.
+__global__ __launch_bounds__(kRB) void lift_argmax_kernel(const unsigned long long* __restrict__ table, const uint32_t* __restrict__ order,
+                                                           long long n, int nbins, unsigned long long threshold,
+                                                           int32_t* __restrict__ labels, double* __restrict__ share) {
+    const long long j = (long long)blockIdx.x * kRB + threadIdx.x;
+    if (j >= n) return;
+    const unsigned long long* row = table + (size_t)j * nbins;
+    unsigned long long total = 0, best = 0;
+    int arg = 0;
+    for (int k = 0; k < nbins; ++k) {
+        const unsigned long long v = row[k];
+        total += v;
+        if (v > best) best = v, arg = k;
+    }
+    const uint32_t i = order[j];
+    labels[i] = total < threshold ? -1 : arg - 1;
+    share[i] = total ? (double)best / (double)total : 0.0;
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+void lift_end(Ctx* c) {
+    c->lift.begun = false;
+    c->lift.views = 0;
+}
+
+int lift_begin(Ctx* c, int n_classes) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    if (n_classes < 1 || n_classes > kLiftMaxBins - 1)
+        return fail(c, GSX_E_INVALID, "lift_begin: n_classes = %d must be in [1, %d]", n_classes, kLiftMaxBins - 1);
+    if (c->scene.rn <= 0) return fail(c, GSX_E_STATE, "lift_begin: no splats uploaded (gsx_upload_splats)");
+    LiftState& L = c->lift;
+    lift_end(c);
+    const size_t bytes = sizeof(unsigned long long) * (size_t)c->scene.rn * (size_t)(n_classes + 1);
+    if (L.table.ensure(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, GSX_E_HIP, "lift_begin: could not allocate %zu bytes for the table of %lld splats x %d bins", bytes,
+                    (long long)c->scene.rn, n_classes + 1);
+    }
+    GSX_HIP(c, L.flag.ensure(sizeof(int)));
+    GSX_HIP(c, hipMemsetAsync(L.table.p, 0, bytes, c->stream));
+    GSX_HIP(c, hipMemsetAsync(L.flag.p, 0x7f, sizeof(int), c->stream));  // kNoBadView
+    L.n_classes = n_classes;
+    L.atomics = 0;
+    L.begun = true;
+    return GSX_OK;
+}
+
+static int lift_narrow(Ctx* c, const void* seg_dev, int seg_dtype, long long npix) {
+    LiftState& L = c->lift;
+    uint8_t* bins = L.bins.as<uint8_t>();
+    int* flag = L.flag.as<int>();
+    const dim3 grid(grid_for(npix)), block(kRB);
+    ProfScope ps(c, "lift_narrow");
+    switch (seg_dtype) {
+        case GSX_SEG_I32:
+            hipLaunchKernelGGL((lift_narrow_kernel<int32_t, GSX_SEG_I32>), grid, block, 0, c->stream, (const int32_t*)seg_dev, npix,
+                               L.n_classes, L.views, bins, flag);
+            break;
+        case GSX_SEG_I64:
+            hipLaunchKernelGGL((lift_narrow_kernel<long long, GSX_SEG_I64>), grid, block, 0, c->stream, (const long long*)seg_dev, npix,
+                               L.n_classes, L.views, bins, flag);
+            break;
+        case GSX_SEG_U8:
+            hipLaunchKernelGGL((lift_narrow_kernel<uint8_t, GSX_SEG_U8>), grid, block, 0, c->stream, (const uint8_t*)seg_dev, npix,
+                               L.n_classes, L.views, bins, flag);
+            break;
+        default:
+            hipLaunchKernelGGL((lift_narrow_kernel<uint8_t, GSX_SEG_U8_LABELS>), grid, block, 0, c->stream, (const uint8_t*)seg_dev, npix,
+                               L.n_classes, L.views, bins, flag);
+            break;
+    }
+    GSX_HIP(c, hipGetLastError());
+    return GSX_OK;
+}
+
+// One view.  The frame's front is render_view's; what differs is WHEN the host learns the pair count.  render_view reads it at
+// the end of the frame and redoes a frame whose lists overflowed the pair buffers - a lift view must never count a frame twice
+// or count a truncated list, so the counters are read back once the lists stand (one host wait) and lift_kernel only runs on
+// lists that fit; until then the buffers grow and the lists are rebuilt.  A second read at the end fetches the statistics.
+int lift_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int W, int H, bool device) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    LiftState& L = c->lift;
+    const char* who = device ? "lift_view_device" : "lift_view";
+    if (!L.begun) return fail(c, GSX_E_STATE, "%s: call gsx_lift_begin first", who);
+    if (c->scene.edits_on) return fail(c, GSX_E_STATE, "%s: a render edit state is set (gsx_render_set_edits): lifting through an edited frame is not defined", who);
+    if (!cam || !seg || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "%s: bad arguments", who);
+    if (seg_dtype != GSX_SEG_I32 && seg_dtype != GSX_SEG_I64 && seg_dtype != GSX_SEG_U8 && seg_dtype != GSX_SEG_U8_LABELS)
+        return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
+    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
+    if (tiles_x > 256 || tiles_y > 256) return fail(c, GSX_E_UNSUPPORTED, "%s: %dx%d exceeds 4096 pixels per side", who, W, H);
+    if (c->frame.pre_ext >= 0 || c->frame.in_flight) return fail(c, GSX_E_STATE, "%s: gsx_render_views is running on this context", who);
+    const size_t elem = seg_elem_size(seg_dtype);
+    if (seg_misaligned(seg, (int)elem)) return fail(c, GSX_E_INVALID, "%s: the map is not aligned to its element", who);
+    const long long npix = (long long)W * H;
+    if (!device) {  // the label range, before anything is launched
+        long long bad = -1;
+        switch (seg_dtype) {
+            case GSX_SEG_I32: bad = host_first_bad<int32_t, GSX_SEG_I32>(seg, npix, L.n_classes); break;
+            case GSX_SEG_I64: bad = host_first_bad<long long, GSX_SEG_I64>(seg, npix, L.n_classes); break;
+            case GSX_SEG_U8: bad = host_first_bad<uint8_t, GSX_SEG_U8>(seg, npix, L.n_classes); break;
+            default: bad = host_first_bad<uint8_t, GSX_SEG_U8_LABELS>(seg, npix, L.n_classes); break;
+        }
+        if (bad >= 0)
+            return fail(c, GSX_E_RANGE, "%s: view %d: the label at row %lld, column %lld is outside [-1, %d]", who, L.views, bad / W, bad % W,
+                        L.n_classes - 1);
+    }
+    GSX_HIP(c, L.bins.ensure((size_t)npix));
+    const void* seg_dev = seg;
+    if (!device) {
+        GSX_HIP(c, L.raw.ensure(elem * (size_t)npix));
+        GSX_HIP(c, hipMemcpyAsync(L.raw.p, seg, elem * (size_t)npix, hipMemcpyHostToDevice, c->stream));
+        seg_dev = L.raw.p;
+    }
+    int rc = lift_narrow(c, seg_dev, seg_dtype, npix);
+    if (rc) return rc;
+    if (!device) GSX_HIP(c, hipStreamSynchronize(c->stream));  // the caller's map has been read when the call returns
+    RenderFrame& f = c->frame;
+    FramePlan fp;
+    if ((rc = frame_plan(c, W, H, false, 1, fp))) return rc;
+    FrameCounters* fc = f.small.as<FrameCounters>();
+    FrameCounters stats;
+    for (int attempt = 0;; ++attempt) {
+        const size_t cap = f.pair_cap;
+        if ((rc = frame_depth_order(c, cam, fp))) return rc;
+        const uint32_t* vals = nullptr;
+        if ((rc = frame_phase_lists(c, fp, 0, 1, &vals))) return rc;
+        GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(c, hipStreamSynchronize(c->stream));
+        const unsigned long long P = stats.pairs[0];
+        if (P > 0x7fffffffull)
+            return fail(c, GSX_E_RANGE, "%s: %llu (tile, splat) pairs exceed 2^31-1 (a close-up of a very large scene)", who, P);
+        if (P > cap) {  // EMIT wrote nothing and the ranges are empty: grow, rebuild the lists
+            if (attempt >= 2) return fail(c, GSX_E_STATE, "%s: pair buffers overflowed three times in a row", who);
+            f.pair_cap = (size_t)(P + P / 4 + 4096);
+            continue;
+        }
+        f.P = P;
+        {
+            ProfScope ps(c, "lift");
+            hipLaunchKernelGGL(lift_kernel, dim3(fp.ntiles), dim3(kLiftThreads), 0, c->stream, f.ranges.as<int2>(), vals,
+                               f.cur->rec.as<float4>(), L.bins.as<uint8_t>(), W, H, tiles_x, L.n_classes + 1,
+                               L.table.as<unsigned long long>(), &fc->consumed[0].n);
+        }
+        GSX_HIP(c, hipGetLastError());
+        break;
+    }
+    GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    f.consumed = 0;
+    L.atomics = 0;
+    for (const FrameCounters::Slot& slot : stats.consumed) {
+        f.consumed += slot.n;
+        L.atomics += slot.atomics;
+    }
+    ++L.views;
+    return GSX_OK;
+}
+
+static int lift_check_maps(Ctx* c, const char* who) {
+    int flag = kNoBadView;
+    GSX_HIP(c, hipMemcpyAsync(&flag, c->lift.flag.p, sizeof flag, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    if (flag != kNoBadView)
+        return fail(c, GSX_E_RANGE, "%s: the device map of view %d held a label outside [-1, %d]", who, flag, c->lift.n_classes - 1);
+    return GSX_OK;
+}
+
+int lift_finalize(Ctx* c, double min_weight, int32_t* labels_out, double* share_out) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    LiftState& L = c->lift;
+    if (!L.begun) return fail(c, GSX_E_STATE, "lift_finalize: call gsx_lift_begin first");
+    if (!labels_out) return fail(c, GSX_E_INVALID, "lift_finalize: labels_out is NULL");
+    if (!(min_weight >= 0.0) || !(min_weight <= 1.0e300)) return fail(c, GSX_E_INVALID, "lift_finalize: min_weight must be finite and >= 0");
+    int rc = lift_check_maps(c, "lift_finalize");
+    if (rc) return rc;
+    const double scaled = std::ceil(min_weight * (double)kLiftOne);
+    const unsigned long long threshold = scaled >= 18446744073709551615.0 ? ~0ull : (unsigned long long)scaled;
+    const size_t n = (size_t)c->scene.rn;
+    GSX_HIP(c, L.out.ensure(12 * n + 8));
+    double* share = L.out.as<double>();
+    int32_t* labels = reinterpret_cast<int32_t*>(share + n);
+    {
+        ProfScope ps(c, "lift_argmax");
+        hipLaunchKernelGGL(lift_argmax_kernel, dim3(grid_for((long long)n)), dim3(kRB), 0, c->stream, L.table.as<unsigned long long>(),
+                           c->scene.order.as<uint32_t>(), (long long)n, L.n_classes + 1, threshold, labels, share);
+    }
+    GSX_HIP(c, hipGetLastError());
+    GSX_HIP(c, hipMemcpyAsync(labels_out, labels, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    if (share_out) GSX_HIP(c, hipMemcpyAsync(share_out, share, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    return GSX_OK;
+}
+
+int lift_table(Ctx* c, uint64_t* table_out) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    LiftState& L = c->lift;
+    if (!L.begun) return fail(c, GSX_E_STATE, "lift_table: call gsx_lift_begin first");
+    if (!table_out) return fail(c, GSX_E_INVALID, "lift_table: table_out is NULL");
+    int rc = lift_check_maps(c, "lift_table");
+    if (rc) return rc;
+    const size_t n = (size_t)c->scene.rn, nb = (size_t)L.n_classes + 1;
+    std::vector<uint32_t> order(n);
+    std::vector<uint64_t> rows(n * nb);  // importance order, as on the device
+    GSX_HIP(c, hipMemcpyAsync(order.data(), c->scene.order.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(rows.data(), L.table.p, 8 * n * nb, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t j = 0; j < n; ++j) {
+        if (order[j] >= n) return fail(c, GSX_E_STATE, "lift_table: the scene's permutation is damaged");
+        std::copy(rows.begin() + j * nb, rows.begin() + (j + 1) * nb, table_out + (size_t)order[j] * nb);
+    }
+    return GSX_OK;
+}
+
+}  // namespace gsx

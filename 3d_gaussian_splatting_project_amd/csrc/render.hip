@@ -313,26 +313,6 @@ static int launch_bin_phase(Ctx* c, const BinPhaseArgs& a) {
 // test hook (gsx_debug_bin): a depth phase as a frame launches it, in the caller's buffers
 int debug_bin(Ctx* c, const BinPhaseArgs& a) { return launch_bin_phase(c, a); }
 
-// A frame's counters (RenderFrame::small), zeroed when the frame starts and read back when it ends.  The kernels get pointers
-// into it; the layout is what it has always been.
-constexpr int kMaxPhases = 8;
-struct FrameCounters {
-    int unused0[2];
-    int dropped;                          // bucket_kernel: splats outside the 16-bit bucket range (the blend's epilogue draws them)
-    int unused1[3];
-    unsigned long long pairs[kMaxPhases]; // the scan's grand total of phase p: its (list, splat) pairs
-    unsigned long long unused2;
-    unsigned long long nvis;              // splats the level-1 sort kept (those with a rectangle in this view)
-    unsigned long long unused3[19];
-    struct alignas(128) Slot {
-        unsigned long long n;
-    } consumed[kConsumedSlots];           // pairs the blend kernels staged: one counter per 128-B line (summed at the end of the frame)
-};
-static_assert(offsetof(FrameCounters, dropped) == 8 && offsetof(FrameCounters, pairs) == 24 && offsetof(FrameCounters, nvis) == 96 &&
-                  offsetof(FrameCounters, consumed) == 256 && sizeof(FrameCounters::Slot) == 128 &&
-                  sizeof(FrameCounters) == 256 + (size_t)kConsumedSlots * 128,
-              "FrameCounters layout");
-
 // One frame.  Per view: pre_kernel (depth keys, vertex shader, colours, tile rectangles), bucket_kernel, the level-1
 // sort of the splats by depth bucket; then the splats are rasterized FRONT TO BACK IN DEPTH PHASES (the nearest
 // n/r^(K-1) splats, the next ones up to n/r^(K-2), .., the rest): each phase bins its splats into the tiles that are not
@@ -344,40 +324,33 @@ static_assert(offsetof(FrameCounters, dropped) == 8 && offsetof(FrameCounters, p
 // The host never waits inside a frame: the pair count of a phase stays on the device, the sort / ranges kernels are
 // launched for the CAPACITY of the pair buffers and read the count themselves.  Only the end-of-frame read-back tells
 // the host whether a phase overflowed the buffers; then they are enlarged and the frame is redone (first frame of a
-// scene, or a much closer view).
-int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out) {
-    GSX_HIP(c, hipSetDevice(c->device));
-    if (!cam || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "render_view: bad arguments");
+// scene, or a much closer view).  (render_view is below its three steps.)
+//
+// The front of a frame, shared with the lift frame (lift.hip), in three steps.  frame_plan: the frame's geometry, the forms the
+// options select and the per-frame buffers (allow_bin32 = false, phases = 1: per-tile lists of ALL pairs, what lift_kernel walks).
+int frame_plan(Ctx* c, int W, int H, bool allow_bin32, int phases, FramePlan& fp) {
     const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
-    if (tiles_x > 256 || tiles_y > 256)
-        return fail(c, GSX_E_UNSUPPORTED, "render_view: %dx%d exceeds 4096 pixels per side", W, H);
     RenderFrame& f = c->frame;
     const RenderOpts& o = c->ropt;
-    const size_t img_bytes = sizeof(float) * 4 * (size_t)W * H;
-    GSX_HIP(c, f.image.ensure(img_bytes));
     const int ntiles = tiles_x * tiles_y;
     const long long n = c->scene.rn;
     // 32x32-pixel bins (see bin_kernel): the one-wave blend kernel reads the masks; a value's top four bits are the mask
-    const bool bin32 = o.bin32 && o.blend_pk2 == 2 && !o.exact_cull && n < (1ll << 28);
+    const bool bin32 = allow_bin32 && o.bin32 && o.blend_pk2 == 2 && !o.exact_cull && n < (1ll << 28);
     f.bin32 = bin32;
     const int bins_x = (tiles_x + 1) / 2, bins_y = (tiles_y + 1) / 2;
     const int nlists = bin32 ? bins_x * bins_y : ntiles;          // lists the pairs are sorted into
     const size_t sat_bytes = bin32 ? 4 * (size_t)nlists : (size_t)ntiles;
+    fp.W = W, fp.H = H, fp.tiles_x = tiles_x, fp.tiles_y = tiles_y, fp.ntiles = ntiles, fp.nlists = nlists;
+    fp.bin32 = bin32, fp.sat_bytes = sat_bytes, fp.n = n;
     GSX_HIP(c, f.ranges.ensure(sizeof(int2) * (size_t)nlists));
     GSX_HIP(c, f.sat.ensure(sat_bytes));
     GSX_HIP(c, f.small.ensure(sizeof(FrameCounters)));
-    FrameCounters* fc = f.small.as<FrameCounters>();
     f.P = 0;
     f.consumed = 0;
-    if (n <= 0) {  // no splats at all: the cleared canvas
-        GSX_HIP(c, hipMemsetAsync(f.image.p, 0, img_bytes, c->stream));
-        if (rgba_out) GSX_HIP(c, hipMemcpyAsync(rgba_out, f.image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
-        GSX_HIP(c, hipStreamSynchronize(c->stream));
-        return GSX_OK;
-    }
+    if (n <= 0) return GSX_OK;  // no splats at all: nothing else is needed
     const size_t n4 = 4 * (size_t)n;
-    const bool ext_pre = f.pre_ext >= 0;  // gsx_render_views ran this frame's pre pass (pre_multi_kernel) into one of the rotating sets
-    f.cur = &f.sets[ext_pre ? f.pre_ext : 0];  // a frame on its own uses set 0
+    fp.ext_pre = f.pre_ext >= 0;  // gsx_render_views ran this frame's pre pass (pre_multi_kernel) into one of the rotating sets
+    f.cur = &f.sets[fp.ext_pre ? f.pre_ext : 0];  // a frame on its own uses set 0
     int rc = ensure_pre_set(c, *f.cur, n);
     if (rc) return rc;
     GSX_HIP(c, f.bucket.ensure(n4));
@@ -390,9 +363,9 @@ int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out) {
     GSX_HIP(c, f.rects.ensure(n4));
     // depth phases: boundaries nvis / r^(K-1), nvis / r^(K-2), .., nvis / r, nvis of the depth order, nvis = the splats the
     // level-1 sort keeps (on the device); the host sizes a phase's launches for n instead
-    const int K = std::max(1, std::min(o.phases, kMaxPhases));
+    const int K = std::max(1, std::min(phases, kMaxPhases));
     const long long ratio = std::max(2, std::min(o.phase_ratio, 64));
-    long long divs[kMaxPhases + 1];  // phase p = [nvis / divs[p], nvis / divs[p + 1]); divs[0] = 0 stands for the start
+    long long* divs = fp.divs;  // phase p = [nvis / divs[p], nvis / divs[p + 1]); divs[0] = 0 stands for the start
     divs[0] = 0;
     for (int p = 1; p <= K; ++p) {
         long long div = 1;
@@ -405,58 +378,113 @@ int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out) {
     // several frames in flight its scattered stores cost the other streams more than the saved launches give (option value 2: always)
     const bool wide = tile_bits <= 11 && (o.wide_sort == 2 || (o.wide_sort == 1 && !f.in_flight));
     if (f.pair_cap == 0) f.pair_cap = std::max<size_t>((size_t)1 << 20, 2 * (size_t)n);
+    fp.K = K, fp.tile_bits = tile_bits, fp.wide = wide;
+    return GSX_OK;
+}
+
+// frame_depth_order, once per attempt at a frame: the pair buffers at their current capacity, the opacity bytes and the counters
+// zeroed, the pre pass (unless gsx_render_views ran it), the depth buckets and the level-1 sort.  -> fp.by_depth
+int frame_depth_order(Ctx* c, const gsx_camera* cam, FramePlan& fp) {
+    RenderFrame& f = c->frame;
+    const RenderOpts& o = c->ropt;
+    FrameCounters* fc = f.small.as<FrameCounters>();
+    const long long n = fp.n;
+    int rc;
+    const size_t cap = f.pair_cap;
+    GSX_HIP(c, f.keys0.ensure(4 * cap));
+    GSX_HIP(c, f.keys1.ensure(4 * cap));
+    GSX_HIP(c, f.vals0.ensure(4 * cap));
+    GSX_HIP(c, f.vals1.ensure(4 * cap));
+    GSX_HIP(c, hipMemsetAsync(f.sat.p, 0, fp.sat_bytes, c->stream));
+    GSX_HIP(c, hipMemsetAsync(fc, 0, sizeof(FrameCounters), c->stream));
+    // (a frame that is redone because a phase overflowed the pair buffers keeps an external pre pass's records)
+    if (!fp.ext_pre && (rc = launch_pre(c, cam, fp.W, fp.H, *f.cur))) return rc;
+    launch_bucket(c, *f.cur, f.bucket.as<uint32_t>(), f.d0.as<uint32_t>(), f.d1.as<uint32_t>(), &fc->dropped, o.compact);
+    GSX_HIP(c, hipGetLastError());
+    // level 1: splats by depth bucket (stable)
+    int dwhere = 0;
+    // (its first pass leaves out the splats bucket_kernel marked: fc->nvis = the ones that remain, sorted, in front)
+    rc = radix_sort_pairs_drop(c, f.d0.as<uint32_t>(), f.d1.as<uint32_t>(), f.d2.as<uint32_t>(), f.d3.as<uint32_t>(), n, nullptr, 16,
+                               &dwhere, &fc->nvis);
+    if (rc) return rc;
+    fp.by_depth = dwhere ? f.d3.as<uint32_t>() : f.d1.as<uint32_t>();
+    return GSX_OK;
+}
+
+// frame_phase_lists, once per depth phase: bin the phase's splats (COUNT -> scan -> EMIT), sort the pairs by list, write the
+// lists' ranges.  *vals_sorted: the sorted list entries f.ranges indexes.  The caller has checked that the phase is due
+// (n / divs[p + 1] > 0 or the last phase).
+int frame_phase_lists(Ctx* c, const FramePlan& fp, int p, int first_phase, const uint32_t** vals_sorted) {
+    RenderFrame& f = c->frame;
+    const RenderOpts& o = c->ropt;
+    FrameCounters* fc = f.small.as<FrameCounters>();
+    const size_t cap = f.pair_cap;
+    const int nlists = fp.nlists;
+    const bool wide = fp.wide;
+    int rc;
+    const long long m = fp.n / fp.divs[p + 1];  // >= the phase's length nvis / divs[p + 1] - nvis / divs[p]
+    unsigned long long* pairs_dev = &fc->pairs[p];
+    int where = 0;
+    if (m > 0) {
+        const BinPhaseArgs bin = {&fc->nvis, fp.divs[p], fp.divs[p + 1], m, fp.by_depth, f.cur->rect.as<uint32_t>(), f.cur->rec.as<float4>(),
+                                  fp.H, fp.tiles_x, fp.bin32, o.exact_cull, first_phase ? nullptr : f.sat.as<uint8_t>(),
+                                  f.count.as<uint32_t>(), f.offset.as<uint32_t>(), f.rects.as<uint32_t>(), f.keys0.as<uint32_t>(),
+                                  f.vals0.as<uint32_t>(), pairs_dev, (unsigned long long)cap};
+        if ((rc = launch_bin_phase(c, bin))) return rc;
+        if (wide) {  // one pass over the whole key; the digits' bases are the lists' ranges (sort.hip)
+            rc = radix_sort_values_wide(c, f.keys0.as<uint32_t>(), f.vals0.as<uint32_t>(), f.vals1.as<uint32_t>(), (long long)cap,
+                                        pairs_dev, fp.tile_bits, f.ranges.as<int2>(), nlists);
+            where = 1;
+        } else {
+            rc = radix_sort_pairs_dev(c, f.keys0.as<uint32_t>(), f.vals0.as<uint32_t>(), f.keys1.as<uint32_t>(), f.vals1.as<uint32_t>(),
+                                      (long long)cap, pairs_dev, fp.tile_bits, &where);
+        }
+        if (rc) return rc;
+    }
+    if (!(wide && m > 0)) GSX_HIP(c, hipMemsetAsync(f.ranges.p, 0, sizeof(int2) * (size_t)nlists, c->stream));
+    if (m > 0 && !wide) {
+        ProfScope ps(c, "render_ranges");
+        hipLaunchKernelGGL(ranges_kernel, dim3(grid_for((long long)cap)), dim3(kRB), 0, c->stream,
+                           where ? f.keys1.as<uint32_t>() : f.keys0.as<uint32_t>(), pairs_dev, (unsigned long long)cap, nlists,
+                           f.ranges.as<int2>());
+        GSX_HIP(c, hipGetLastError());
+    }
+    *vals_sorted = where ? f.vals1.as<uint32_t>() : f.vals0.as<uint32_t>();
+    return GSX_OK;
+}
+
+int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out) {
+    GSX_HIP(c, hipSetDevice(c->device));
+    if (!cam || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "render_view: bad arguments");
+    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
+    if (tiles_x > 256 || tiles_y > 256)
+        return fail(c, GSX_E_UNSUPPORTED, "render_view: %dx%d exceeds 4096 pixels per side", W, H);
+    RenderFrame& f = c->frame;
+    const size_t img_bytes = sizeof(float) * 4 * (size_t)W * H;
+    GSX_HIP(c, f.image.ensure(img_bytes));
+    FramePlan fp;
+    int rc = frame_plan(c, W, H, true, c->ropt.phases, fp);
+    if (rc) return rc;
+    FrameCounters* fc = f.small.as<FrameCounters>();
+    const long long n = fp.n;
+    if (n <= 0) {  // no splats at all: the cleared canvas
+        GSX_HIP(c, hipMemsetAsync(f.image.p, 0, img_bytes, c->stream));
+        if (rgba_out) GSX_HIP(c, hipMemcpyAsync(rgba_out, f.image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(c, hipStreamSynchronize(c->stream));
+        return GSX_OK;
+    }
+    const int K = fp.K;
 
     for (int attempt = 0;; ++attempt) {
         const size_t cap = f.pair_cap;
-        GSX_HIP(c, f.keys0.ensure(4 * cap));
-        GSX_HIP(c, f.keys1.ensure(4 * cap));
-        GSX_HIP(c, f.vals0.ensure(4 * cap));
-        GSX_HIP(c, f.vals1.ensure(4 * cap));
-        GSX_HIP(c, hipMemsetAsync(f.sat.p, 0, sat_bytes, c->stream));
-        GSX_HIP(c, hipMemsetAsync(fc, 0, sizeof(FrameCounters), c->stream));
-        // (a frame that is redone because a phase overflowed the pair buffers keeps an external pre pass's records)
-        if (!ext_pre && (rc = launch_pre(c, cam, W, H, *f.cur))) return rc;
-        launch_bucket(c, *f.cur, f.bucket.as<uint32_t>(), f.d0.as<uint32_t>(), f.d1.as<uint32_t>(), &fc->dropped, o.compact);
-        GSX_HIP(c, hipGetLastError());
-        // level 1: splats by depth bucket (stable)
-        int dwhere = 0;
-        // (its first pass leaves out the splats bucket_kernel marked: fc->nvis = the ones that remain, sorted, in front)
-        rc = radix_sort_pairs_drop(c, f.d0.as<uint32_t>(), f.d1.as<uint32_t>(), f.d2.as<uint32_t>(), f.d3.as<uint32_t>(), n, nullptr, 16,
-                                   &dwhere, &fc->nvis);
-        if (rc) return rc;
-        const uint32_t* by_depth = dwhere ? f.d3.as<uint32_t>() : f.d1.as<uint32_t>();
+        if ((rc = frame_depth_order(c, cam, fp))) return rc;
         int first_phase = 1;
         for (int p = 0; p < K; ++p) {
-            const long long m = n / divs[p + 1];  // >= the phase's length nvis / divs[p + 1] - nvis / divs[p]
             const bool last = p == K - 1;
-            if (m <= 0 && !last) continue;
-            unsigned long long* pairs_dev = &fc->pairs[p];
-            int where = 0;
-            if (m > 0) {
-                const BinPhaseArgs bin = {&fc->nvis, divs[p], divs[p + 1], m, by_depth, f.cur->rect.as<uint32_t>(), f.cur->rec.as<float4>(),
-                                          H, tiles_x, bin32, o.exact_cull, first_phase ? nullptr : f.sat.as<uint8_t>(),
-                                          f.count.as<uint32_t>(), f.offset.as<uint32_t>(), f.rects.as<uint32_t>(), f.keys0.as<uint32_t>(),
-                                          f.vals0.as<uint32_t>(), pairs_dev, (unsigned long long)cap};
-                if ((rc = launch_bin_phase(c, bin))) return rc;
-                if (wide) {  // one pass over the whole key; the digits' bases are the lists' ranges (sort.hip)
-                    rc = radix_sort_values_wide(c, f.keys0.as<uint32_t>(), f.vals0.as<uint32_t>(), f.vals1.as<uint32_t>(), (long long)cap,
-                                                pairs_dev, tile_bits, f.ranges.as<int2>(), nlists);
-                    where = 1;
-                } else {
-                    rc = radix_sort_pairs_dev(c, f.keys0.as<uint32_t>(), f.vals0.as<uint32_t>(), f.keys1.as<uint32_t>(), f.vals1.as<uint32_t>(),
-                                              (long long)cap, pairs_dev, tile_bits, &where);
-                }
-                if (rc) return rc;
-            }
-            if (!(wide && m > 0)) GSX_HIP(c, hipMemsetAsync(f.ranges.p, 0, sizeof(int2) * (size_t)nlists, c->stream));
-            if (m > 0 && !wide) {
-                ProfScope ps(c, "render_ranges");
-                hipLaunchKernelGGL(ranges_kernel, dim3(grid_for((long long)cap)), dim3(kRB), 0, c->stream,
-                                   where ? f.keys1.as<uint32_t>() : f.keys0.as<uint32_t>(), pairs_dev, (unsigned long long)cap, nlists,
-                                   f.ranges.as<int2>());
-                GSX_HIP(c, hipGetLastError());
-            }
-            rc = launch_blend(c, where ? f.vals1.as<uint32_t>() : f.vals0.as<uint32_t>(), W, H, tiles_x, tiles_y, &fc->dropped,
+            if (n / fp.divs[p + 1] <= 0 && !last) continue;
+            const uint32_t* vals = nullptr;
+            if ((rc = frame_phase_lists(c, fp, p, first_phase, &vals))) return rc;
+            rc = launch_blend(c, vals, W, H, tiles_x, tiles_y, &fc->dropped,
                               &fc->consumed[0].n, f.sat.as<uint8_t>(), first_phase, last ? 1 : 0);
             if (rc) return rc;
             first_phase = 0;

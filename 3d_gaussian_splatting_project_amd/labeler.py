@@ -47,6 +47,7 @@ class Context:
         self.device = int(device)
         self._keep_alive = []   # device maps handed to vote_view until the ctx stream has consumed them
         self._ext = None        # the ctx stream as torch sees it (segmap_from_*)
+        self._lift_bins, self._lift_keep = 1, []   # columns of the lift table; the device map a lift view may still read
 
     def close(self):
         if getattr(self, "h", None):
@@ -590,6 +591,73 @@ class Context:
 
     def render_num_pairs_consumed(self):
         return self._lib.gsx_render_num_pairs_consumed(self.h)
+
+    # -- lifting labeler (include/gsx.h: gsx_lift_*) ------------------------------------------------
+    def lift_begin(self, n_classes):
+        """Start a lift run on the splats of upload_splats: a zeroed n x (n_classes + 1) table of blend weights."""
+        self._lift_keep = []
+        self._lift_bins = int(n_classes) + 1
+        check(self._lib.gsx_lift_begin(self.h, int(n_classes)), self.h)
+
+    def lift_view(self, camera, seg_map, image_size=None, packed_u8=False):
+        """Lift one class map (2-D, labels -1..n_classes-1; a numpy array on the host or a torch tensor on this GPU) through
+        the frame gsx_render_view draws from `camera` at the MAP's size.  image_size: (width, height) the camera's fx, fy
+        refer to (default: the camera's own width, height); they are scaled by map size / image size, which is the caller's
+        job at the C level.  Host maps are range-checked here (ValueError); device maps when the table is fetched."""
+        cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
+        device = type(seg_map) is not np.ndarray and hasattr(seg_map, "data_ptr")
+        if device:
+            seg = seg_map.contiguous()
+            if not seg.is_cuda:
+                raise ValueError("tensor seg maps must live on the GPU; pass numpy arrays for host maps")
+            dt = self._TORCH_DT.get(str(seg.dtype))
+            if dt is None:
+                import torch
+                seg, dt = seg.to(torch.int32), _lib.GSX_SEG_I32
+        else:
+            seg = np.asarray(seg_map)
+            dt = self._NP_DT.get(seg.dtype)
+            if dt is None:
+                seg, dt = seg.astype(np.int32), _lib.GSX_SEG_I32
+            seg = np.ascontiguousarray(seg)
+        if seg.ndim != 2:
+            raise ValueError("seg_map must be 2-D")
+        if packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
+            dt = _lib.GSX_SEG_U8
+        h, w = (int(v) for v in seg.shape)
+        iw, ih = (cam.width, cam.height) if image_size is None else (int(image_size[0]), int(image_size[1]))
+        if (iw, ih) != (w, h) and iw > 0 and ih > 0:
+            scaled = Camera()
+            C.memmove(C.byref(scaled), C.byref(cam), C.sizeof(Camera))
+            scaled.fx, scaled.fy, scaled.width, scaled.height = cam.fx * (w / iw), cam.fy * (h / ih), w, h
+            cam = scaled
+        if device:
+            check(self._lib.gsx_lift_view_device(self.h, C.byref(cam), seg.data_ptr(), dt, w, h), self.h)
+            self._lift_keep = [seg]          # the call waits for the frame: the previous map has been read
+        else:
+            check(self._lib.gsx_lift_view(self.h, C.byref(cam), seg.ctypes.data, dt, w, h), self.h)
+
+    def lift_num_views(self):
+        return self._lib.gsx_lift_num_views(self.h)
+
+    def lift_num_atomics(self):
+        """64-bit global atomics the lifting kernel issued for the last view"""
+        return self._lib.gsx_lift_num_atomics(self.h)
+
+    def lift_finalize(self, min_weight=0.0, return_share=False):
+        """-> int32 labels in upload order (and the winner's share of each row as float64)"""
+        n = self._lib.gsx_num_splats(self.h)
+        labels = np.empty(n, np.int32)
+        share = np.empty(n, np.float64) if return_share else None
+        check(self._lib.gsx_lift_finalize(self.h, float(min_weight), labels.ctypes.data, None if share is None else share.ctypes.data),
+              self.h)
+        return (labels, share) if return_share else labels
+
+    def lift_table(self):
+        """-> uint64 (n, n_classes + 1), rows in upload order, column = label + 1, in units of 1 / 2^20"""
+        table = np.empty((self._lib.gsx_num_splats(self.h), self._lift_bins), np.uint64)
+        check(self._lib.gsx_lift_table(self.h, table.ctypes.data), self.h)
+        return table
 
     def hit_test(self, camera, width, height, x, y):
         """performHitTesting (gs.js:361-395) -> (label or -999999, importance-order row or -1)."""
@@ -1186,4 +1254,12 @@ def iou_constants():
     out = np.zeros(8, np.int32)
     check(_lib.lib().gsx_debug_iou_constants(out.ctypes.data))
     names = ("load_bytes", "word_bits", "wave_tile", "block_tile", "pair_tile", "pair_chunk_words", "table_lds_max", "table_run")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def lift_constants():
+    """Test hook, host only: the units the lifting kernel is built on (gsx_debug_lift_constants); one = GSX_LIFT_ONE."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_lift_constants(out.ctypes.data))
+    names = ("one", "shift", "tile", "chunk", "cells", "loop_max", "max_classes")
     return dict(zip(names, (int(v) for v in out)))

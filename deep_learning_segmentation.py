@@ -24,6 +24,11 @@ Gaussians no view saw.
 --split_k N [--split_max_dist D] [--split_min_size S] [--split_max_instances M] (default off) then turns the classes into
 objects: the connected components of every label over the N nearest neighbours (3D_clustering/split_labels.py), -1 ignored;
 the largest object gets id 0 and the instance table is printed.
+--labeler {vote,lift} (default vote).  lift: instead of projecting each Gaussian's centre, every class map is lifted through
+the rasterizer's own blend (Context.lift_view): a splat takes the class of the pixels it actually colours, weighted by its
+blend weight T * alpha * G, so a splat behind a wall no longer takes the wall's class.  Needs the PLY's splat attributes
+(scale_*, rot_*, opacity, f_dc_*); uses the VIEWER's camera convention, not the reference labeler's; single GPU.
+--lift_min_weight W (default 0): splats whose summed weight over all views stays below W are labelled -1.
 """
 import argparse
 import importlib
@@ -57,6 +62,21 @@ def load_gaussians(ply_file):
     for axis, name in enumerate("xyz"):
         gaussians["position"][:, axis] = vertices.column_f32(name)
     return gaussians, plydata
+
+
+def load_splat_attributes(plydata):
+    """The attributes Context.upload_splats takes, from the PLY's vertex element: (xyz, scale, rot, opacity, f_dc); scale, rot
+    and opacity are None where the file has none (the viewer's fallback)."""
+    vertices = plydata["vertex"]
+    names = set(vertices.properties)
+    cols = lambda group: np.stack([vertices.column_f32(name) for name in group], axis=1)
+    missing = [name for name in ("f_dc_0", "f_dc_1", "f_dc_2") if name not in names]
+    if missing:
+        raise ValueError(f"--labeler lift needs the splat attributes of the PLY: {', '.join(missing)} missing")
+    full = all(name in names for name in ("scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3", "opacity"))
+    return (cols("xyz"), cols(("scale_0", "scale_1", "scale_2")) if full else None,
+            cols(("rot_0", "rot_1", "rot_2", "rot_3")) if full else None, vertices.column_f32("opacity") if full else None,
+            cols(("f_dc_0", "f_dc_1", "f_dc_2")))
 
 
 def project_gaussian(position, camera):
@@ -152,11 +172,20 @@ def _image_size(path):
 
 
 def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2former", segmap_dir=None, n_classes=None,
-                  ctx=None, mask2former_map="segments"):
+                  ctx=None, mask2former_map="segments", labeler="vote", splats=None, lift_min_weight=0.0):
     """Majority-vote label per Gaussian (int32, -1 = never visible), bit-identical to the reference.
 
     Cameras whose `<img_name>.png` is missing from input_dir are skipped with a warning, as in the
-    reference; the remaining ones are voted in order (the order decides ties)."""
+    reference; the remaining ones are voted in order (the order decides ties).
+
+    labeler="lift": the maps are lifted through the rasterizer's blend instead (Context.lift_view, each at the map's own
+    size with fx, fy scaled by map size / image size); splats = load_splat_attributes(plydata); a splat whose summed weight
+    stays below lift_min_weight gets -1."""
+    if labeler not in ("vote", "lift"):
+        raise ValueError(f"Unknown labeler: {labeler}")
+    lift = labeler == "lift"
+    if lift and splats is None:
+        raise ValueError("labeler='lift' needs the splat attributes (load_splat_attributes)")
     if model_type not in N_CLASSES:
         raise ValueError(f"Unknown model type: {model_type}")
     n_classes = n_classes or N_CLASSES[model_type]
@@ -173,6 +202,8 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         processor, model = initialize_model(model_type, device)
     world, rank = _world()
+    if lift and world > 1:
+        raise ValueError("--labeler lift runs on one GPU")
     own = ctx is None
     ctx = ctx or gsx.Context()
     if own:
@@ -183,23 +214,29 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
         # may end up without any camera (more GPUs than images): it still takes part in every collective.
         lo, hi = gsx.dist.view_range(len(todo), rank, world) if world > 1 else (0, len(todo))
         total = max(1, len(todo))
-        ctx.upload_positions(gaussians)
-        ctx.vote_begin(n_classes, min(lo, total - 1), total)
+        if lift:
+            ctx.upload_splats(*splats)
+            ctx.lift_begin(n_classes)
+            view = lambda camera, seg_map, size: ctx.lift_view(camera, seg_map)   # fx, fy scaled by map size / camera size
+        else:
+            ctx.upload_positions(gaussians)
+            ctx.vote_begin(n_classes, min(lo, total - 1), total)
+            view = ctx.vote_view
         for camera, img_path in todo[lo:hi]:
             print(f"Processing image {os.path.basename(img_path)}...")
             if segmap_dir is not None:
                 seg_map = np.load(os.path.join(segmap_dir, camera["img_name"] + "_segmap.npy"))
-                ctx.vote_view(camera, seg_map, _image_size(img_path))
+                view(camera, seg_map, _image_size(img_path))
                 continue
             from PIL import Image
             os.makedirs(output_dir, exist_ok=True)
             image = Image.open(img_path)
             seg_dev = _segment_image_device(image, processor, model, device, model_type, ctx, mask2former_map, n_classes)
-            ctx.vote_view(camera, seg_dev, image.size)          # the map goes from the network to the vote on the device ...
+            view(camera, seg_dev, image.size)                   # the map goes from the network to the vote on the device ...
             _save_segmap(img_path, output_dir, seg_dev.cpu().numpy())   # ... and is copied down behind it, for the .npy only
         if world > 1:
             return gsx.dist.exchange_labels_gather(gsx.dist.GpuGatherShard(ctx), cap_views=total)
-        return ctx.vote_finalize()
+        return ctx.lift_finalize(lift_min_weight) if lift else ctx.vote_finalize()
     finally:
         if own:
             ctx.close()
@@ -271,6 +308,10 @@ def make_parser():
     parser.add_argument("--split_max_dist", type=float, default=None, help="neighbours farther apart than this are not joined")
     parser.add_argument("--split_min_size", type=int, default=1, help="components of fewer Gaussians become -1")
     parser.add_argument("--split_max_instances", type=int, default=0, help="keep only this many of the largest components (0: all)")
+    parser.add_argument("--labeler", choices=["vote", "lift"], default="vote", help="vote: the reference's majority vote over projected "
+                        "centres; lift: class maps lifted through the rasterizer's blend (occlusion-aware, the viewer's camera convention)")
+    parser.add_argument("--lift_min_weight", type=float, default=0.0, help="lift: splats whose summed blend weight stays below this "
+                        "are labelled -1")
     return parser
 
 
@@ -312,7 +353,9 @@ def main(argv=None):
     print("Assigning labels...")
     try:
         labels = assign_labels(gaussians, cameras, args.input_dir, args.output_dir, model_type=args.model,
-                               segmap_dir=args.segmap_dir, n_classes=args.n_classes, mask2former_map=args.mask2former_map)
+                               segmap_dir=args.segmap_dir, n_classes=args.n_classes, mask2former_map=args.mask2former_map,
+                               labeler=args.labeler, splats=load_splat_attributes(plydata) if args.labeler == "lift" else None,
+                               lift_min_weight=args.lift_min_weight)
     except BaseException:
         _shutdown(failed=True)
         raise

@@ -525,6 +525,61 @@ int gsx_debug_render_pre(gsx_ctx* ctx, int32_t num_views, const gsx_camera* cams
                          int32_t compact, const gsx_debug_pre_view* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * lifting labeler — class maps lifted onto the splats through the rasterizer's blend.  A second producer of the label
+ * field next to the vote: where assign_labels (dls.py:252-308) projects a Gaussian's centre and knows nothing of extent,
+ * opacity or occlusion, this one gives every splat the class of the pixels it actually colours.
+ *
+ * The rule.  For a view (cam, width, height) and a height x width class map with values in [-1, n_classes-1], take the frame
+ * exactly as gsx_render_view(ctx, cam, width, height) walks it: same pre pass, quantisation, depth order, tile lists,
+ * `discard` rule and ONE_MINUS_DST_ALPHA, ONE blend.  For a pixel p and the k-th fragment at p, made by splat i,
+ *     w = (1 - dst.a) * B,   dst.a = the alpha before this fragment,   B = exp(A) * alpha
+ * is exactly the increment of the frame's alpha channel, and the view adds w to table[i][map[p] + 1].
+ *   - A splat runSort drops gets nothing from that view, and the epilogue's repeated draws of splat 0 (gs.js:453-457) add
+ *     nothing either: a viewer quirk that comes last and changes nobody else's transmittance.
+ *   - Fixed point: each (pixel, fragment) weight is added as q = rint(w * 2^20), GSX_LIFT_ONE = 1 << 20
+ *     (gsx_debug_lift_constants).  Partial sums on the chip are uint32 (a 16x16 tile gives at most 2^28 per record), the table
+ *     is uint64, n x (n_classes + 1).  Integer sums do not depend on arrival order: a table is reproducible bit for bit from
+ *     run to run, and two views accumulated together equal the sum of their separate tables exactly.
+ *   - A lift frame runs as ONE depth phase whatever the option "render_phases" says; the frame's opacity cut stays: a tile
+ *     stops once every pixel has 1 - dst.a < 1e-5, so what is left out is below 1e-5 per pixel in total.
+ *   - The camera is used as gsx_render_view uses it (the viewer's convention, R^T (x - p), fx and fy against width x height),
+ *     NOT as the vote uses it (R (x - p)).  Scaling fx, fy when the map is smaller than the camera's image is the caller's
+ *     job (labeler.py does it).
+ *   - With a render edit state set (gsx_render_set_edits) the lift calls fail with GSX_E_STATE.
+ *   - Finalize, per splat i in the order of the arrays given to gsx_upload_splats (not importance order): total = the sum
+ *     of the row; total < ceil(min_weight * 2^20) -> label -1; else the bin with the largest sum, the lowest bin winning a
+ *     tie (label -1 is bin 0 and can win like any class, as in the vote).  share = winner / total as a double, 0 where
+ *     total is 0.  All comparisons are on the integers.
+ * A new gsx_upload_splats (or gsx_destroy) ends a lift run; lift calls before gsx_lift_begin return GSX_E_STATE.
+ * ------------------------------------------------------------------------------------------- */
+/* 1 <= n_classes <= 255, else GSX_E_INVALID.  Needs gsx_upload_splats (GSX_E_STATE).  Allocates and zeroes the table; a
+ * failed allocation is GSX_E_HIP with a message naming the bytes asked for. */
+int gsx_lift_begin(gsx_ctx* ctx, int32_t n_classes);
+/* seg: HOST pointer, height x width row-major, any gsx_seg_dtype.  The label range is checked on the host before anything
+ * is launched: GSX_E_RANGE fails THIS call and adds nothing.  The map has been read when the call returns.  The host waits
+ * for the frame's pair count before the lifting kernel runs (a frame whose lists overflow the pair buffers is never counted
+ * truncated or twice: the buffers grow first). */
+int gsx_lift_view(gsx_ctx* ctx, const gsx_camera* cam, const void* seg, int32_t seg_dtype, int32_t width, int32_t height);
+/* same, seg_dev is a DEVICE pointer read on the ctx stream, under the ordering rule of gsx_vote_view_device.  A label out of
+ * range is recorded on the device (it counts as -1) and fails gsx_lift_finalize / gsx_lift_table with GSX_E_RANGE, naming
+ * the view. */
+int gsx_lift_view_device(gsx_ctx* ctx, const gsx_camera* cam, const void* seg_dev, int32_t seg_dtype, int32_t width,
+                         int32_t height);
+/* views lifted since gsx_lift_begin (0 outside a run) */
+int32_t gsx_lift_num_views(const gsx_ctx* ctx);
+/* 64-bit global atomics the lifting kernel issued for the last view (statistics, like gsx_render_num_pairs_consumed, which
+ * after a lift view reports the records that kernel staged) */
+int64_t gsx_lift_num_atomics(const gsx_ctx* ctx);
+/* labels_out: n int32; share_out: n doubles or NULL; both in upload order.  min_weight: finite, >= 0.  May be called more
+ * than once, and more views may follow. */
+int gsx_lift_finalize(gsx_ctx* ctx, double min_weight, int32_t* labels_out, double* share_out);
+/* table_out: n x (n_classes + 1) uint64, rows in upload order: for tests and for callers who want soft labels */
+int gsx_lift_table(gsx_ctx* ctx, uint64_t* table_out);
+/* test hook: out[8] = GSX_LIFT_ONE, its shift, the tile side, records per staged chunk, LDS accumulators per round, classes a
+ * mixed wave reduces one by one, the largest n_classes, 0 */
+int gsx_debug_lift_constants(int32_t* out);
+
+/* ---------------------------------------------------------------------------------------------
  * PLY files — replaces the plyfile calls of the reference: PlyData.read (dls.py:29, ply_handler.py:
  * 44-45) and PlyData([vertex], text=False).write (dls.py:331-332, ply_handler.py:35-37).
  * Only the vertex element (scalar properties) is kept, as save_labeled_ply does.  ascii and
