@@ -45,27 +45,31 @@ void lift_constants(int32_t out[8]) {
 // ---- the view's map as one u8 bin per pixel ---------------------------------------------------------------------------------
 // bin = label + 1 (0 = label -1).  A label outside [-1, n_classes - 1] becomes bin 0 and records the view in *flag (host maps
 // are checked before anything is launched and never get here with one).
+// The stored value v is compared with the range of stored values itself, [lo - off, n_classes - off], and the bin v + off is
+// formed only for a value inside it: no sum that could leave 64 bits (v + 1 at 2^63 - 1), nothing narrowed before the test.
+template <int DTYPE>
+__host__ __device__ __forceinline__ bool lift_value_ok(long long v, int n_classes) {
+    const long long off = DTYPE == GSX_SEG_U8 ? 0 : 1;  // a packed u8 map holds the bin itself
+    const long long lo = DTYPE == GSX_SEG_U8_LABELS ? 1 : 0;  // u8 labels cannot say -1
+    return v >= lo - off && v <= (long long)n_classes - off;
+}
+
 template <typename T, int DTYPE>
 __global__ __launch_bounds__(kRB) void lift_narrow_kernel(const T* __restrict__ seg, long long npix, int n_classes, int view,
                                                            uint8_t* __restrict__ bins, int* __restrict__ flag) {
     const long long p = (long long)blockIdx.x * kRB + threadIdx.x;
     if (p >= npix) return;
     const long long v = (long long)seg[p];
-    const long long b = DTYPE == GSX_SEG_U8 ? v : v + 1;
-    const long long lo = DTYPE == GSX_SEG_U8_LABELS ? 1 : 0;
-    const bool ok = b >= lo && b <= (long long)n_classes;
-    bins[p] = ok ? (uint8_t)b : (uint8_t)0;
+    const bool ok = lift_value_ok<DTYPE>(v, n_classes);
+    bins[p] = ok ? (uint8_t)(v + (DTYPE == GSX_SEG_U8 ? 0 : 1)) : (uint8_t)0;
     if (!ok) atomicMin(flag, view);
 }
 
 template <typename T, int DTYPE>
 static long long host_first_bad(const void* seg, long long npix, int n_classes) {
     const T* s = static_cast<const T*>(seg);
-    const long long lo = DTYPE == GSX_SEG_U8_LABELS ? 1 : 0;
-    for (long long p = 0; p < npix; ++p) {
-        const long long b = DTYPE == GSX_SEG_U8 ? (long long)s[p] : (long long)s[p] + 1;
-        if (b < lo || b > (long long)n_classes) return p;
-    }
+    for (long long p = 0; p < npix; ++p)
+        if (!lift_value_ok<DTYPE>((long long)s[p], n_classes)) return p;
     return -1;
 }
 

@@ -13,11 +13,19 @@ min_weight = 1e-3 labels every record behind a wall -1 and every one in front wi
 all of them the class at their centre.
 
 Leave-one-out (lengths, needles, edges; the map with 255 classes, own row, closed form): the removed record's own cells lose
-its weights; the best cell lies at least 223 x its GPU tolerance away (lengths; needles 336 x, edges 522 .. 2277 x)."""
+its weights; the best cell lies at least 223 x its GPU tolerance away (lengths; needles 336 x, edges 522 .. 2277 x).
+
+The constructed maps of tests/lift_cases.py (test_lift_edges_gpu.py holds lift_kernel's reduction paths and round lengths to
+them bit for bit): D, the classes per wave and the round length of every pattern are computed from the pattern alone and are
+what the kernel's constants say; and with q = rint(w * 2^20) of the model, every edge is reached by at least 10 records with
+q > 0 - the loop path at loop_max classes and the per-lane path one above (1150 .. 2866 records on `lengths`), remainder rounds
+in the first and second chunk (d_9: 827 and 222, d_100: 196 and 29), waves the frame cuts with two or more classes inside
+(23 .. 54 on the edge frames, 365 .. 396 on walls_65x53), tiles with a wave wholly outside the frame (32 .. 84)."""
 import numpy as np
 import pytest
 
 import blend_cases
+import lift_cases
 import lift_model
 from blend_model import BlendModel
 
@@ -165,3 +173,141 @@ def test_finalize_rule():
     assert lift_model.finalize(t, 12 / lift_model.ONE)[0].tolist() == [-1, -1, 0, -1, 1]
     assert lift_model.finalize(t, 15.5 / lift_model.ONE)[0].tolist() == [-1, -1, -1, -1, 1]
     assert lift_model.threshold(1e-3) == 1049 and lift_model.threshold(0.0) == 0 and lift_model.threshold(1.0) == lift_model.ONE
+
+
+# ---- the constructed maps of lift_cases.py: the cases are what they claim, and every edge carries weight -------------------
+def test_patterns_are_what_they_claim(gsx):
+    K = gsx.lift_constants()
+    R, Lm = lift_cases.units(K)
+    chunk, cells = K["chunk"], K["cells"]
+    P = lift_cases.patterns(K)
+    for name, p in P.items():
+        D, waves, sub = lift_cases.structure(p.bins, K)
+        print(f"{name}: D {D}, classes per wave {waves} ({', '.join(lift_cases.path_of(K, c) for c in waves)}), sub {sub}, n_classes {p.n_classes}")
+        assert (D, waves, sub) == p.want and sub == min(chunk, cells // D) and sub * D <= cells, name
+        assert p.n_classes == (255 if name.endswith("_c255") else p.bins.max()), name        # the smallest that fits
+        assert np.array_equal(p.f[P["pos256"].bins], p.bins) and np.array_equal(P["pos256"].bins.reshape(-1), np.arange(256))
+    assert P["pos256"].want == (256, (64,) * 4, cells // 256) and P["pos256"].bins.min() == 0
+    for j in (1, 2, Lm - 1, Lm, Lm + 1):
+        assert P[f"wave_{j}"].want == (j, (j,) * 4, chunk)
+    path = lambda name: [lift_cases.path_of(K, c) for c in P[name].want[1]]
+    assert path("wave_1") == ["uniform"] * 4 and path(f"wave_{Lm}") == ["loop"] * 4 and path(f"wave_{Lm + 1}") == ["lanes"] * 4
+    assert path("mixed_waves") == ["uniform", "loop", "loop", "lanes"] and P["mixed_waves"].want[1] == (1, 2, Lm, Lm + 1)
+    rows = [set(P["mixed_waves"].bins[4 * w:4 * w + 4].reshape(-1)) for w in range(4)]
+    assert sum(len(s) for s in rows) == len(set.union(*rows)) == P["mixed_waves"].want[0]      # disjoint between the waves
+    assert P[f"d_{R}"].want[2] == chunk and R * chunk == cells                                 # the last whole-chunk round
+    sub = P[f"d_{R + 1}"].want[2]
+    assert sub == cells // (R + 1) < chunk and 0 < chunk - sub < sub                           # one full round, one remainder round
+    assert path(f"d_{R}") == ["lanes"] * 4 and path(f"d_{R + 1}") == ["lanes"] * 4
+    loop = P[f"d{R + 1}_loop"]
+    assert loop.want[0] == R + 1 and loop.want[2] == sub and path(loop.name) == ["loop"] * 4
+    rows = [set(loop.bins[4 * w:4 * w + 4].reshape(-1)) for w in range(4)]
+    assert sum(len(s) for s in rows) == R + 1 == len(set.union(*rows))
+    assert P["d_16"].want == (16, (16,) * 4, cells // 16)
+    assert P["d_100"].want[2] == cells // 100 and chunk % (cells // 100) != 0                  # a sub that does not divide the chunk
+    assert P["d_255"].want == (255, (64,) * 4, cells // 255) and P["d_255"].n_classes == 254
+    we = P["word_edges"]
+    assert sorted(set(we.bins.reshape(-1))) == sorted(lift_cases.WORD_EDGES) and we.want[0] == 16 and (we.bins == we.bins[0]).all()
+    assert {b // 32 for b in lift_cases.WORD_EDGES} == set(range(8)) and {0, 31, 255} <= set(lift_cases.WORD_EDGES)
+    assert all({32 * j - 1, 32 * j} <= set(lift_cases.WORD_EDGES) for j in range(1, 7))       # both sides of six word boundaries
+    for name in (f"wave_{Lm + 1}", "d_100"):
+        assert np.array_equal(P[name + "_c255"].bins, P[name].bins) and P[name].n_classes < 255
+    # the map: the pattern repeated, cut at the border, minus 1 - and a function of the fine map pixel by pixel
+    fine = P["pos256"].map(33, 45)
+    for p in P.values():
+        seg = p.map(33, 45)
+        assert seg.shape == (45, 33) and seg.dtype == np.int32 and seg.min() >= -1 and seg.max() < p.n_classes
+        assert np.array_equal(seg[16:32, 16:32] + 1, p.bins) and np.array_equal(seg[32:45, 32:33] + 1, p.bins[:13, :1])
+        assert np.array_equal(p.f[fine + 1] - 1, seg)
+
+
+def test_the_pair_that_is_not_periodic(gsx):
+    K = gsx.lift_constants()
+    R, _ = lift_cases.units(K)
+    for W, H in ((96, 48), (65, 53), (47, 47)):
+        (fine, C), (coarse, n), f = lift_cases.halves_pair(W, H)
+        assert C == 255 and n == lift_cases.HALVES_N == f.max() and np.array_equal(f[fine + 1] - 1, coarse) and coarse.min() == -1
+        assert np.array_equal(fine, lift_model.maps(W, H)["c255"][0])
+        Ds = np.array([s[0] for s in lift_cases.tile_structures(coarse, K)]).reshape((H + 15) // 16, (W + 15) // 16)
+        print(f"{W}x{H}: classes per tile\n{Ds}")
+        assert (Ds[:, 1:] != Ds[:, :-1]).any() and (Ds[1:] != Ds[:-1]).any() and len(np.unique(Ds)) >= 4
+        assert (Ds <= R).any() and (Ds > R).any()                         # whole-chunk rounds and shorter ones in one frame
+    whole = np.array([s[0] for s in lift_cases.tile_structures(lift_model.maps(96, 48)["c255"][0], K)])
+    assert (whole == 121).all()                                          # 121 consecutive bins in every whole tile of the fine map
+
+
+def staged_q(m, t, K):
+    """q = rint(w * ONE) of tile t's records on its pixels, (L,16,16) ints - of the records the kernel stages: the list up to the
+    chunk after which every pixel inside is opaque"""
+    L = m.consumed(t, K["chunk"])[0]
+    return np.rint(lift_model.tile_weights(m, t)[:L] * lift_model.ONE).astype(np.int64)
+
+
+def loaded(m, seg, K, pick, positions=None):
+    """how many records (tile, list position) put q > 0 on a pixel of pick(D, waves, inside) -> 16x16 mask or None; positions:
+    (list length) -> the list positions that count"""
+    count = 0
+    for t, (D, waves, sub, inside, _) in enumerate(lift_cases.tile_structures(seg, K)):
+        if len(m.lists[t]) == 0:
+            continue
+        mask = pick(D, waves, inside)
+        if mask is None:
+            continue
+        q = staged_q(m, t, K)
+        hit = (q * (mask & inside)[None] > 0).any((1, 2))
+        if positions is not None:
+            keep = np.zeros(len(hit), bool)
+            keep[[k for k in positions(len(m.lists[t]), sub) if k < len(hit)]] = True
+            hit &= keep
+        count += int(hit.sum())
+    return count
+
+
+def waves_with(cond):
+    """pick: the pixel rows of the waves for which cond(class count, pixels inside) holds"""
+    def pick(D, waves, inside):
+        rows = [w for w in range(4) if cond(waves[w], int(inside[4 * w:4 * w + 4].sum()))]
+        if not rows:
+            return None
+        mask = np.zeros((16, 16), bool)
+        for w in rows:
+            mask[4 * w:4 * w + 4] = True
+        return mask
+    return pick
+
+
+def remainder_positions(chunk, which):
+    """list positions of chunk `which` that fall into its remainder round: position within the chunk >= sub * (cnt // sub)"""
+    def positions(L, sub):
+        cnt = min(chunk, L - which * chunk)
+        return [] if cnt <= 0 else [which * chunk + k for k in range(sub * (cnt // sub), cnt)]
+    return positions
+
+
+def test_every_edge_carries_weight(gsx):
+    """conditions, not measurements: each structural edge is reached by at least 10 records with q > 0"""
+    K = gsx.lift_constants()
+    R, Lm = lift_cases.units(K)
+    P = lift_cases.patterns(K)
+    m = blend_cases.prepared("lengths").model
+    seen = {}
+    for name in (f"wave_{Lm}", "mixed_waves"):
+        seen[f"loop path at {Lm} classes, {name}, lengths"] = loaded(m, P[name].map(m.W, m.H), K, waves_with(lambda c, n: c == Lm))
+    for name in (f"wave_{Lm + 1}", "mixed_waves"):
+        seen[f"per-lane path at {Lm + 1} classes, {name}, lengths"] = loaded(m, P[name].map(m.W, m.H), K, waves_with(lambda c, n: c == Lm + 1))
+    assert max(blend_cases.LENGTHS) > 2 * K["chunk"] and sorted(blend_cases.LENGTHS)[-4] > K["chunk"]
+    for name in (f"d_{R + 1}", f"d{R + 1}_loop", "d_100"):
+        for which in (0, 1):
+            seen[f"remainder round of chunk {which}, {name}, lengths"] = loaded(m, P[name].map(m.W, m.H), K, lambda D, w, i: i,
+                                                                             remainder_positions(K["chunk"], which))
+    for scene in ("edges_33x33", "edges_17x17", "walls_65x53"):
+        m = blend_cases.prepared(scene).model
+        assert m.W % 16 and m.H % 16
+        for name in ("pos256", "wave_2", f"wave_{Lm + 1}", "mixed_waves"):
+            seen[f"wave cut by the frame with >= 2 classes inside, {name}, {scene}"] = loaded(
+                m, P[name].map(m.W, m.H), K, waves_with(lambda c, n: c >= 2 and 0 < n < 64))
+        seen[f"tile with a wave wholly outside the frame, pos256, {scene}"] = loaded(
+            m, P["pos256"].map(m.W, m.H), K, lambda D, w, i: i if any(not i[4 * k:4 * k + 4].any() for k in range(4)) else None)
+    for what, count in seen.items():
+        print(f"{count:6d} records with q > 0: {what}")
+    assert all(count >= 10 for count in seen.values()), {k: v for k, v in seen.items() if v < 10}
