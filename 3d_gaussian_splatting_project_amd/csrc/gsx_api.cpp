@@ -142,8 +142,10 @@ void gsx_destroy(gsx_ctx* ctx) {
     for (auto ev : c->event_pool) (void)hipEventDestroy(ev);
     gsx::render_release_twin(c);
     gsx::vote_release_host(c);
-    gsx::iou_release(c);
     (void)hipStreamDestroy(c->stream);
+    // ~Ctx frees the pinned buffers and destroys the events (PinBuf, Event) after the streams are gone.  Legal: both streams were
+    // synchronised above and nothing was queued since, so no copy reads a pinned block and no event is waited for any more; and
+    // neither hipHostFree nor hipEventDestroy takes a stream.
     delete c;
 }
 
@@ -161,15 +163,15 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
     CTX_OR_FAIL(ctx);
     if (!name) return gsx::fail(c, GSX_E_INVALID, "set_option: name is NULL");
     const std::string k(name);
-    if (k == "spatial_sort") c->opt_spatial_sort = value != 0;
+    if (k == "spatial_sort") c->vopt.spatial_sort = value != 0;
     else if (k == "nn_brute") c->opt_nn_brute = value != 0;
     else if (k == "smooth_search") c->opt_smooth_search = value != 0;
     else if (k == "iou_table_lds") c->opt_iou_table_lds = value != 0;
     else if (k == "xcd_swizzle") {
         if (value < 0 || value > 65536) return gsx::fail(c, GSX_E_INVALID, "set_option: xcd_swizzle must be in [0,65536]");
-        c->opt_xcd_swizzle = (int)value;
+        c->vopt.xcd_swizzle = (int)value;
     }
-    else if (k == "seg_tiled") c->opt_seg_tiled = value != 0;
+    else if (k == "seg_tiled") c->vopt.seg_tiled = value != 0;
     else if (k == "tile_lpt") c->ropt.tile_lpt = value != 0;
     else if (k == "exact_cull") c->ropt.exact_cull = value != 0;
     else if (k == "render_phases") {
@@ -194,41 +196,38 @@ int gsx_set_option(gsx_ctx* ctx, const char* name, int64_t value) {
     else if (k == "blend_pk2") c->ropt.blend_pk2 = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
     else if (k == "exchange_slabs") {
         if (value < 1 || value > 64) return gsx::fail(c, GSX_E_INVALID, "set_option: exchange_slabs must be in [1,64]");
-        c->opt_slabs = (int)value;
-    } else if (k == "exchange_local") c->opt_local_codes = value != 0;
-    else if (k == "flat_project") c->opt_flat_project = value != 0;
-    else if (k == "seg_coarse") c->opt_seg_coarse = value != 0;
-    else if (k == "batched_counts") c->opt_batched_counts = value != 0;
-    else if (k == "wave_cull") c->opt_wave_cull = value != 0;
-    else if (k == "filter_project") c->opt_filter_project = value != 0;
-    else if (k == "host_pack") c->opt_host_pack = value != 0;
-    else if (k == "labels_u8") c->opt_labels_u8 = value != 0;
-    else if (k == "host_compact") c->opt_host_compact = value != 0;
+        c->vopt.slabs = (int)value;
+    } else if (k == "exchange_local") c->vopt.local_codes = value != 0;
+    else if (k == "flat_project") c->vopt.flat_project = value != 0;
+    else if (k == "seg_coarse") c->vopt.seg_coarse = value != 0;
+    else if (k == "batched_counts") c->vopt.batched_counts = value != 0;
+    else if (k == "wave_cull") c->vopt.wave_cull = value != 0;
+    else if (k == "filter_project") c->vopt.filter_project = value != 0;
+    else if (k == "host_pack") c->vopt.host_pack = value != 0;
+    else if (k == "labels_u8") c->vopt.labels_u8 = value != 0;
+    else if (k == "host_compact") c->vopt.host_compact = value != 0;
     else if (k == "early_vote") {
         if (value < 0 || value > 2) return gsx::fail(c, GSX_E_INVALID, "set_option: early_vote must be 0, 1 or 2");
-        c->opt_early_vote = (int)value;
-    } else if (k == "early_replay") c->opt_early_replay = value != 0;
+        c->vopt.early_vote = (int)value;
+    } else if (k == "early_replay") c->vopt.early_replay = value != 0;
     else if (k == "early_vote_at") {
         if (value < 0 || value > 1000) return gsx::fail(c, GSX_E_INVALID, "set_option: early_vote_at must be in [0,1000] (permille of the announced views; 0 = from the hand-over rate)");
-        c->opt_early_at = (int)value;
+        c->vopt.early_at = (int)value;
     }
     else if (k == "host_prefetch") gsx::set_host_prefetch((int)value);
     else if (k == "host_prefetch_burst") gsx::set_host_prefetch_burst(value != 0);
 #ifdef GSX_EXPERIMENTS
-    else if (k == "ablate") c->opt_ablate = (int)value;
+    else if (k == "ablate") c->vopt.ablate = (int)value;
 #endif
     else if (k == "host_threads") {
         if (value < 0 || value > 256) return gsx::fail(c, GSX_E_INVALID, "set_option: host_threads must be in [0,256]");
-        if ((int)value != c->opt_host_threads) {
-            delete c->ho.workers;  // re-created with the new size at the next host-side hand-over
-            c->ho.workers = nullptr;
-        }
-        c->opt_host_threads = (int)value;
+        if ((int)value != c->vopt.host_threads) c->ho.workers.reset();  // re-created with the new size at the next host-side hand-over
+        c->vopt.host_threads = (int)value;
     }
     else if (k == "vote_unroll") {
         if (value != 2 && value != 4 && value != 8)
             return gsx::fail(c, GSX_E_INVALID, "set_option: vote_unroll must be 2, 4 or 8");
-        c->opt_vote_unroll = (int)value;
+        c->vopt.vote_unroll = (int)value;
     } else
         return gsx::fail(c, GSX_E_INVALID, "set_option: unknown option '%s'", name);
     return GSX_OK;
@@ -238,11 +237,11 @@ int gsx_get_option(gsx_ctx* ctx, const char* name, int64_t* value) {
     CTX_OR_FAIL(ctx);
     if (!name || !value) return gsx::fail(c, GSX_E_INVALID, "get_option: NULL argument");
     const std::string k(name);
-    if (k == "early_vote") *value = c->opt_early_vote;
-    else if (k == "early_vote_at") *value = c->opt_early_at;
-    else if (k == "early_replay") *value = c->opt_early_replay ? 1 : 0;
-    else if (k == "seg_tiled") *value = c->opt_seg_tiled ? 1 : 0;
-    else if (k == "seg_coarse") *value = c->opt_seg_coarse ? 1 : 0;
+    if (k == "early_vote") *value = c->vopt.early_vote;
+    else if (k == "early_vote_at") *value = c->vopt.early_at;
+    else if (k == "early_replay") *value = c->vopt.early_replay ? 1 : 0;
+    else if (k == "seg_tiled") *value = c->vopt.seg_tiled ? 1 : 0;
+    else if (k == "seg_coarse") *value = c->vopt.seg_coarse ? 1 : 0;
     else
         return gsx::fail(c, GSX_E_INVALID, "get_option: option '%s' cannot be read back", name);
     return GSX_OK;
@@ -267,9 +266,9 @@ static int alloc_positions(Ctx* c, int64_t n) {
     GSX_HIP(c, c->y.ensure(bytes));
     GSX_HIP(c, c->z.ensure(bytes));
     c->n = n;
-    c->n_pad = (n + 255) / 256 * 256;
-    c->vote_begun = false;  // planes are sized by n: a new scene needs a new vote_begin
-    c->labels_valid = false;
+    c->run.n_pad = (n + 255) / 256 * 256;
+    c->run.begun = false;  // planes are sized by n: a new scene needs a new vote_begin
+    c->run.labels_valid = false;
     return GSX_OK;
 }
 
@@ -285,7 +284,7 @@ int gsx_upload_positions(gsx_ctx* ctx, int64_t n, const float* x, const float* y
     GSX_HIP(c, hipMemcpyAsync(c->z.p, z, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
     GSX_HIP(c, hipStreamSynchronize(c->stream));
     c->sorted = false;
-    if (c->opt_spatial_sort) return gsx::spatial_sort_positions(c);
+    if (c->vopt.spatial_sort) return gsx::spatial_sort_positions(c);
     return GSX_OK;
 }
 
@@ -393,7 +392,7 @@ int gsx_debug_host_pack(const void* seg, int32_t seg_dtype, int32_t w, int32_t h
 }
 int32_t gsx_vote_num_views(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return c ? (int32_t)c->views.size() : 0;
+    return c ? (int32_t)c->run.views.size() : 0;
 }
 int gsx_vote_rewind(gsx_ctx* ctx) {
     CTX_OR_FAIL(ctx);
@@ -405,7 +404,7 @@ int gsx_vote_finalize(gsx_ctx* ctx, int32_t* labels_out) {
 }
 void* gsx_vote_labels_device(gsx_ctx* ctx) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    return (c && c->labels_valid) ? c->labels.p : nullptr;
+    return (c && c->run.labels_valid) ? c->planes.labels.p : nullptr;
 }
 int gsx_vote_flush(gsx_ctx* ctx) {
     CTX_OR_FAIL(ctx);
@@ -413,9 +412,9 @@ int gsx_vote_flush(gsx_ctx* ctx) {
 }
 void* gsx_vote_counts_device(gsx_ctx* ctx, int64_t* n_int32_words) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !c->vote_begun) return nullptr;
-    if (n_int32_words) *n_int32_words = (int64_t)c->bins * c->n_pad * (c->wide ? 2 : 1) / 4;
-    return c->cnt.p;
+    if (!c || !c->run.begun) return nullptr;
+    if (n_int32_words) *n_int32_words = (int64_t)c->run.bins * c->run.n_pad * (c->run.wide ? 2 : 1) / 4;
+    return c->planes.cnt.p;
 }
 int gsx_vote_tiebreak_keys(gsx_ctx* ctx) {
     CTX_OR_FAIL(ctx);
@@ -423,9 +422,9 @@ int gsx_vote_tiebreak_keys(gsx_ctx* ctx) {
 }
 void* gsx_vote_keys_device(gsx_ctx* ctx, int64_t* n_int32_words) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !c->vote_begun) return nullptr;
-    if (n_int32_words) *n_int32_words = c->n_pad;
-    return c->keys.p;
+    if (!c || !c->run.begun) return nullptr;
+    if (n_int32_words) *n_int32_words = c->run.n_pad;
+    return c->planes.keys.p;
 }
 int gsx_vote_labels_from_keys(gsx_ctx* ctx, int32_t* labels_out) {
     CTX_OR_FAIL(ctx);
@@ -433,13 +432,13 @@ int gsx_vote_labels_from_keys(gsx_ctx* ctx, int32_t* labels_out) {
 }
 void* gsx_vote_first_device(gsx_ctx* ctx, int64_t* n_int32_words) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !c->vote_begun) return nullptr;
-    if (n_int32_words) *n_int32_words = (int64_t)c->bins * c->n_pad * (c->wide ? 2 : 1) / 4;
-    return c->fv.p;
+    if (!c || !c->run.begun) return nullptr;
+    if (n_int32_words) *n_int32_words = (int64_t)c->run.bins * c->run.n_pad * (c->run.wide ? 2 : 1) / 4;
+    return c->planes.fv.p;
 }
 int64_t gsx_vote_slab_size(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return (c && c->vote_begun) ? c->sn : 0;
+    return (c && c->run.begun) ? c->run.sn : 0;
 }
 int gsx_vote_slab_reduce(gsx_ctx* ctx, const void* recv_counts_dev, const void* recv_first_dev) {
     CTX_OR_FAIL(ctx);
@@ -455,9 +454,9 @@ int gsx_vote_slab_totals(gsx_ctx* ctx, const void* recv_counts_dev) {
 }
 void* gsx_vote_cand_device(gsx_ctx* ctx, int64_t* n_int32_words) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !c->vote_begun) return nullptr;
-    if (n_int32_words) *n_int32_words = 8 * c->sn;
-    return c->cand.p;
+    if (!c || !c->run.begun) return nullptr;
+    if (n_int32_words) *n_int32_words = 8 * c->run.sn;
+    return c->planes.cand.p;
 }
 int gsx_vote_tie_codes(gsx_ctx* ctx, const void* cand_all_dev) {
     CTX_OR_FAIL(ctx);
@@ -465,9 +464,9 @@ int gsx_vote_tie_codes(gsx_ctx* ctx, const void* cand_all_dev) {
 }
 void* gsx_vote_codes_device(gsx_ctx* ctx, int64_t* n_int32_words) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !c->vote_begun) return nullptr;
-    if (n_int32_words) *n_int32_words = c->n_pad / 2;
-    return c->codes.p;
+    if (!c || !c->run.begun) return nullptr;
+    if (n_int32_words) *n_int32_words = c->run.n_pad / 2;
+    return c->planes.codes.p;
 }
 int gsx_vote_tie_resolve(gsx_ctx* ctx, const void* recv_codes_dev) {
     CTX_OR_FAIL(ctx);
@@ -483,15 +482,15 @@ int gsx_vote_export(gsx_ctx* ctx, int64_t reserve_bytes, void* blobs_out, void**
 }
 int64_t gsx_vote_pool_bytes(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return (c && c->vote_begun && !c->pool_base) ? (int64_t)((c->seg_used + 255) / 256 * 256) : 0;
+    return (c && c->run.begun && !c->run.pool_base) ? (int64_t)((c->run.seg_used + 255) / 256 * 256) : 0;
 }
 int64_t gsx_vote_link_bytes(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return (c && c->vote_begun) ? (int64_t)c->ho.compact_bytes : 0;
+    return (c && c->run.begun) ? (int64_t)c->ho.compact_bytes : 0;
 }
 int64_t gsx_vote_early_views(const gsx_ctx* ctx) {
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    return c && (c->early_state == 1 || c->early_batches > 0) ? c->early_done : 0;
+    return c && (c->early.phase == gsx::EarlyPhase::Started || c->early.batches > 0) ? c->early.done : 0;
 }
 int gsx_vote_import(gsx_ctx* ctx, int32_t n_parts, const int32_t* part_views, const int64_t* part_offsets, const void* blobs,
                     const void* pool_all_dev, int64_t pool_all_bytes) {

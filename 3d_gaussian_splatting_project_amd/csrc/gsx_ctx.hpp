@@ -6,7 +6,9 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
+#include <memory>
 #include <cstddef>
 #include <string>
 #include <vector>
@@ -77,6 +79,90 @@ struct DevBuf {
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// ---- pinned host buffer: grows, never shrinks ------------------------------------------------------
+struct PinBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p;
+            cap = o.cap;
+            o.p = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~PinBuf() { release(); }
+    // contents are NOT preserved on growth; reserve: the caller's growth rule (what a buffer that has to grow is given, at least need).
+    // Nothing may still be copying out of or into the old block: the caller waits for the event that guards it first.
+    hipError_t ensure(size_t need, size_t reserve = 0) {
+        if (need <= cap) return hipSuccess;
+        release();
+        const size_t bytes = need > reserve ? need : reserve;
+        hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// ---- event without timing, created at its first record ----------------------------------------------
+struct Event {
+    hipEvent_t e = nullptr;
+    bool pending = false;  // recorded, and the host has not waited for it since
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(o.e), pending(o.pending) { o.e = nullptr; o.pending = false; }
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) {
+            destroy();
+            e = o.e;
+            pending = o.pending;
+            o.e = nullptr;
+            o.pending = false;
+        }
+        return *this;
+    }
+    ~Event() { destroy(); }
+    hipError_t record(hipStream_t stream) {
+        if (!e) {
+            const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+            if (r != hipSuccess) {
+                e = nullptr;
+                return r;
+            }
+        }
+        const hipError_t r = hipEventRecord(e, stream);
+        if (r == hipSuccess) pending = true;
+        return r;
+    }
+    hipError_t wait() {  // the host waits for the last record, once
+        if (!pending) return hipSuccess;
+        const hipError_t r = hipEventSynchronize(e);
+        if (r == hipSuccess) pending = false;
+        return r;
+    }
+    hipError_t stream_wait(hipStream_t stream) const { return hipStreamWaitEvent(stream, e, 0); }  // after a record only
+    void destroy() {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+        pending = false;
+    }
+};
+
 // ---- per-view descriptor read by the kernels through scalar (wave-uniform) loads ------------------
 struct alignas(64) ViewDesc {
     // ---- core, 128 B = two s_load_dwordx16: everything that differs from view to view in an ordinary capture ----
@@ -102,10 +188,8 @@ static_assert(sizeof(ViewDesc) == 256 && offsetof(ViewDesc, wscale) == 192, "Vie
 
 // one slot of the pinned staging ring of gsx_vote_view (host maps): packed by the host workers, DMA'd to the pool
 struct PinSlot {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;  // recorded after the slot's H2D copy
-    bool busy = false;
+    PinBuf buf;
+    Event ev;  // recorded after the slot's H2D copy
 };
 static constexpr int kPinSlots = 4;
 static constexpr int kDmaBatch = 4;    // packed host maps per H2D copy (one hipMemcpyAsync + event record costs ~6 us of host time)
@@ -150,16 +234,15 @@ constexpr size_t seg_elem_size(int seg_dtype) { return seg_dtype == GSX_SEG_I32 
 // State of the segmentation-map hand-over (handover.hip): worker pool, the pinned rings of the three transfer forms and the
 // packed maps that wait for their DMA.  Plain data; only handover.hip (and the option "host_threads") writes it.
 struct HandOver {
-    Workers* workers = nullptr;
+    std::unique_ptr<Workers> workers;  // created at first use (host_workers), dropped by the option "host_threads"
     DevBuf dstage[kPinSlots];  // host_pack = 0: device-side landing zone of the raw map of each ring slot
     PinSlot ring[kPinSlots];   // host_pack = 0: raw maps
     int ring_next = 0;
     // host_pack = 1: ONE pinned buffer of kDmaGroups * kDmaBatch slots, a slot = the pool stride of the map geometry, so that
     // consecutive packed maps are consecutive both here and in the pool and a whole group goes up in one DMA
-    void* hring = nullptr;
-    size_t hring_bytes = 0, hring_slot = 0;
-    hipEvent_t hring_ev[kDmaGroups] = {nullptr, nullptr, nullptr};
-    bool hring_busy[kDmaGroups] = {false, false, false};
+    PinBuf hring;
+    size_t hring_slot = 0;
+    Event hring_ev[kDmaGroups];  // recorded behind a group's DMA; pending: the group's slots may not be rewritten yet
     int hring_next = 0;
     int pend_first = 0, pend_count = 0;  // packed maps of the filling group whose DMA has not been queued yet
     size_t pend_dst = 0;
@@ -173,13 +256,148 @@ struct HandOver {
     int pend_group = 0;                  // group of the pending records
     MapLayout pend_L;                    // their geometry (one expansion launch = one geometry)
     DevBuf cstage;                       // device staging of one group of records
-    void* h_scratch = nullptr;           // host: the narrowed strips of the map being packed (ordinary memory)
+    struct Free {
+        void operator()(void* p) const { std::free(p); }
+    };
+    std::unique_ptr<uint8_t, Free> h_scratch;  // host: the narrowed strips of the map being packed (ordinary memory, page aligned)
     size_t h_scratch_cap = 0;
     long long compact_bytes = 0;         // statistics: bytes of host maps sent over PCIe since vote_begin (compact records or pool form)
     void begin_run() {  // vote_begin: packed maps of an abandoned run that never went up are forgotten with it
         pend_count = 0;
         compact_bytes = 0;
     }
+};
+
+// ---- state of the vote: plain data, members of Ctx ---------------------------------------------------------------------------
+// The options the vote, the hand-over and the early stage read (gsx_set_option writes them, nothing else does).
+struct VoteOpts {
+    int spatial_sort = 1;    // Morton-order the Gaussians at upload (results do not depend on it)
+    int xcd_swizzle = 32;    // 0: off, 1: contiguous eighths of the Morton curve per XCD, C: chunks of C workgroups round-robin
+    int vote_unroll = 8;     // views whose seg gathers are in flight together: 1, 2, 4 or 8
+    int slabs = 1;           // see VoteRun::slabs (takes effect at the next vote_begin)
+    int local_codes = 0;     // see VoteRun::local_codes
+    int seg_tiled = 1;       // store seg maps as 16x8-pixel tiles of 128 B
+    int batched_counts = 1;  // > 255 views on one GPU: per-batch count planes + sparse tie pass instead of 16-bit planes
+    int seg_coarse = 1;      // keep a 4x4-coarsened level of every tiled map (views staged after the call)
+    int flat_project = 1;    // branchless projection block (exact divisions, one predicate at the end)
+    int wave_cull = 1;       // skip (wave, view) pairs whose 64 Gaussians provably all miss the frame
+    int filter_project = 1;  // fp32 filter in front of the two fp64 divisions of the projection (vote.hip: project_filtered); exact by construction
+    int host_threads = 0;    // 0: default_host_threads()
+    int host_compact = 1;    // host maps cross PCIe in the compact form (coarse level + the mixed cells' blocks), expanded on the GPU
+    int labels_u8 = 1;       // 1: the labels cross PCIe as one byte each (bin = label + 1) and are widened by the workers; 0: as int32
+    int host_pack = 1;       // 1: host maps are narrowed to u8 by the workers (2.2 MB/map over PCIe); 0: raw copy + GPU pack kernel (8.3 MB/map)
+    int early_vote = 1;      // 0: off, 1: for runs worth it (one rank holds all <= 255 views, a large scene), 2: whenever possible (tests)
+    int early_at = 0;        // the stage starts when this many permille of the announced views are staged; 0: chosen from the run's own hand-over rate
+    int early_replay = 1;    // 1 (default since round 3): the early stage only records the votes, the last stage replays them (vote_record_kernel / vote_fused_replay_kernel); 0: count + first-view planes and the fold
+#ifdef GSX_EXPERIMENTS  // `make experiments` only (libgsx_experiments.so, used by tools/): timing-only switches, results invalid
+    int ablate = 0;          // 1 = host maps are packed but not copied, 2 = copied but not packed (handover.hip); << 4: last-stage ablations (vote.hip)
+#else
+    static constexpr int ablate = 0;  // the product library has no such option: every branch on it folds away
+#endif
+};
+
+// One run, gsx_vote_begin .. the next one.
+struct VoteRun {
+    // fixed by vote_begin (begin_run)
+    bool begun = false;
+    int n_classes = 0, bins = 0;
+    int first_view = 0, total_views = 0;
+    bool wide = false;         // 16-bit plane counters (total_views > 255)
+    bool local_codes = false;  // planes hold per-rank u8 counters and LOCAL first-view codes (all-to-all exchange)
+    int slabs = 1;             // planes are [slab][bins][sn]; one slab per rank of the all-to-all exchange
+    int64_t sn = 0;            // Gaussians per slab (multiple of 256)
+    int64_t n_pad = 0;         // slabs * sn: row pitch of the vote planes (after an upload: n rounded up to 256)
+    // filled by the hand-over (handover.hip); sync_views (vote.hip) derives the device copies from it
+    std::vector<ViewDesc> views;
+    bool views_dirty = true;    // host views newer than d_views
+    bool views_simple = false;  // every staged view: unit scale + tiled map (set by sync_views)
+    bool views_coarse = false;  // ... and a coarse level (set by sync_views)
+    size_t seg_used = 0;
+    const void* pool_base = nullptr;  // gsx_vote_import: the maps live in a caller-owned gathered pool, not in segpool
+    std::vector<ViewDesc> own_views;  // gsx_vote_import: this rank's own views, for gsx_vote_import_undo
+    int own_first_view = 0;
+    int n_flushed = 0;          // views [0, n_flushed) are already in the planes
+    bool labels_valid = false;
+    // on the device
+    DevBuf d_views;
+    DevBuf d_cull;              // double[25][cull_pitch]: five world-space culling planes per staged view
+    int cull_pitch = 0;
+    DevBuf d_cull_tally;        // u64: (wave, view) pairs skipped by the culling since the last reset
+    DevBuf segpool;
+    DevBuf errflag;             // int: smallest view index whose device-side map held a label out of range (kNoBadView: none)
+    void begin_run(const VoteOpts& o, int64_t n, int classes, int first, int total) {
+        n_classes = classes;
+        bins = classes + 1;
+        first_view = first;
+        total_views = total;
+        local_codes = o.local_codes != 0;
+        wide = total > 255 && !local_codes;
+        slabs = o.slabs > 0 ? o.slabs : 1;
+        sn = ((n + slabs - 1) / slabs + 255) / 256 * 256;
+        if (sn == 0) sn = 256;
+        n_pad = sn * slabs;
+        views.clear();
+        views_dirty = true;
+        pool_base = nullptr;
+        seg_used = 0;
+        n_flushed = 0;
+        labels_valid = false;
+    }
+};
+
+// What cnt / fv hold.  Stale: a rewound run's votes; the next fresh flush overwrites them (vote.hip: clear_stale_planes)
+enum class PlaneState { None, Zero, Votes, Stale };
+// The layout gsx_vote_flush_counts / gsx_vote_tie_codes last wrote into cnt / codes: their kernels write the Gaussians (whole
+// workgroups of them) only, so the pad entries behind them are zero as long as the layout is still this one.  Default: none.
+struct PlaneLayout {
+    long long n = -1, npad = -1, sn = -1;
+    int bins = -1;
+    bool operator==(const PlaneLayout& o) const { return n == o.n && npad == o.npad && sn == o.sn && bins == o.bins; }
+};
+struct VotePlanes {
+    DevBuf cnt, fv;             // [bins][n_pad] counters / first-view codes (u8 or u16)
+    DevBuf keys, labels;        // [n_pad] int32
+    DevBuf labels8;             // [n] u8: bin = label + 1, what labels_to_host sends over PCIe
+    DevBuf bcnt, bcodes;        // > 255 views on one GPU: per-batch u8 count planes [S][bins][n_pad], tie codes u16 [S][n_pad]
+    DevBuf cand, codes;         // exchange v3: candidate masks u32[8][sn] of this slab; tie codes u16[n_pad]
+    PlaneState state = PlaneState::None;
+    PlaneLayout counts, tie_codes;  // of cnt and of codes (u16 [n_pad]: neither slabs nor bins shape them, so only n and npad are set)
+    bool holds() const { return state != PlaneState::None; }  // cnt / fv are allocated for this run and defined
+    void begin_run() { state = PlaneState::None; }
+};
+
+// Early vote (vote.hip: early_vote_stage): the views [0, done) are voted on the second stream while the host is still handing
+// over the rest of the run; vote_finalize then only walks the views behind them.
+enum class EarlyPhase { Idle, Started, Off };  // not started in this run; started; not available any more (rewind, pool moved)
+struct EarlyVote {
+    EarlyPhase phase = EarlyPhase::Idle;
+    int done = 0;               // views [0, done) are in ecnt / efv (or, > 255 announced views, in the first `batches` planes of bcnt)
+    int batches = 0;            // > 255 announced views: batches of labels_batched() whose count kernels already ran on stream2
+    bool replayed = false;      // this run's early stage was a record-only one
+    bool inflight = false;      // done_ev was recorded on stream2 and the context's stream has not been ordered behind it yet (early_join)
+    std::chrono::steady_clock::time_point t0;  // first gsx_vote_view of the run
+    Event maps_ev, done_ev, up_ev;  // stream2 behind the maps; the stage's end; the staging buffer's last upload
+    DevBuf ecnt, efv;           // u8 [wave][bin][64]: counts / first-view codes of the early views
+    DevBuf erec;                // u8 [wave][view][64]: bin + 1 voted by each Gaussian in each early view
+    DevBuf e_views, e_cull;     // descriptors and culling planes (pitch kEarlyPitch) of the run's views, filled stage by stage
+    PinBuf h_stage;             // pinned staging of both
+    void begin_run() {
+        phase = EarlyPhase::Idle;
+        done = 0;
+        batches = 0;
+    }
+    void drop() {  // this run is voted in one piece
+        phase = EarlyPhase::Off;
+        batches = 0;
+    }
+};
+
+// Pinned staging between the vote and the host (vote.hip): each buffer is guarded by the events recorded behind its copies.
+struct VoteStaging {
+    PinBuf labels;  // n u8 bins (label + 1) + one int (the error flag) land here before the caller's array (labels_to_host)
+    Event labels_ev[kLabelChunks];
+    PinBuf views;   // view descriptors + culling planes on their way to d_views / d_cull (sync_views)
+    Event views_ev;
 };
 
 // ---- state of the rasterizer: plain data, three members of Ctx ------------------------------------------------------------
@@ -284,97 +502,20 @@ struct Ctx {
 
     // scene
     int64_t n = 0;
-    int64_t n_pad = 0;  // n rounded up to 256: row pitch of the vote planes
     DevBuf x, y, z;     // SoA f32 positions (Morton order when `sorted`)
     DevBuf perm;        // u32[n]: original index of slot i (valid when `sorted`)
     bool sorted = false;
     DevBuf sort_hist;   // radix-sort scratch
 
-    // options (gsx_set_option)
-    int opt_spatial_sort = 1;  // Morton-order the Gaussians at upload (results do not depend on it)
-    int opt_xcd_swizzle = 32;  // 0: off, 1: contiguous eighths of the Morton curve per XCD, C: chunks of C workgroups round-robin
-    int opt_vote_unroll = 8;   // views whose seg gathers are in flight together: 1, 2, 4 or 8
-    int opt_slabs = 1;         // see Ctx::slabs (takes effect at the next vote_begin)
-    int opt_local_codes = 0;   // see Ctx::local_codes
-    int opt_seg_tiled = 1;     // store seg maps as 16x8-pixel tiles of 128 B
-    int opt_batched_counts = 1; // > 255 views on one GPU: per-batch count planes + sparse tie pass instead of 16-bit planes
-    int opt_seg_coarse = 1;    // keep a 4x4-coarsened level of every tiled map (views staged after the call)
-    int opt_flat_project = 1;  // branchless projection block (exact divisions, one predicate at the end)
-
-    // vote
-    bool vote_begun = false;
-    int n_classes = 0, bins = 0;
-    int first_view = 0, total_views = 0;
-    bool wide = false;  // 16-bit plane counters (total_views > 255)
-    bool local_codes = false;  // planes hold per-rank u8 counters and LOCAL first-view codes (all-to-all exchange)
-    int slabs = 1;             // planes are [slab][bins][sn]; one slab per rank of the all-to-all exchange
-    int64_t sn = 0;            // Gaussians per slab (multiple of 256); n_pad = slabs * sn
-    std::vector<ViewDesc> views;
-    DevBuf d_cull;               // double[25][cull_pitch]: five world-space culling planes per staged view
-    int cull_pitch = 0;
-    DevBuf d_cull_tally;         // u64: (wave, view) pairs skipped by the culling since the last reset
-    int opt_wave_cull = 1;       // skip (wave, view) pairs whose 64 Gaussians provably all miss the frame
-    bool views_dirty = true;  // host views newer than d_views
-    bool views_coarse = false;  // ... and a coarse level (set by sync_views)
-    bool views_simple = false;  // every staged view: unit scale + tiled map (set by sync_views)
-    DevBuf d_views;
-    DevBuf segpool;
-    size_t seg_used = 0;
-    DevBuf errflag;  // int: smallest view index whose device-side map held a label out of range (kNoBadView: none)
-    // host hand-over: the maps' way in (handover.hip), then the pinned landing zone for the labels (vote.hip: labels_to_host)
+    // the vote (vote.hip, handover.hip): options, the run since vote_begin, the planes, the early stage, the host staging
+    VoteOpts vopt;
+    VoteRun run;
     HandOver ho;
-    int opt_host_threads = 0;  // 0: default_host_threads()
-    int opt_host_compact = 1;  // host maps cross PCIe in the compact form (coarse level + the mixed cells' blocks), expanded on the GPU
-#ifdef GSX_EXPERIMENTS  // `make experiments` only (libgsx_experiments.so, used by tools/): timing-only switches, results invalid
-    int opt_ablate = 0;        // 1 = host maps are packed but not copied, 2 = copied but not packed (handover.hip); << 4: last-stage ablations (vote.hip)
-#else
-    static constexpr int opt_ablate = 0;  // the product library has no such option: every branch on it folds away
-#endif
-    int opt_labels_u8 = 1;     // 1: the labels cross PCIe as one byte each (bin = label + 1) and are widened by the workers; 0: as int32
-    int opt_host_pack = 1;     // 1: host maps are narrowed to u8 by the workers (2.2 MB/map over PCIe); 0: raw copy + GPU pack kernel (8.3 MB/map)
-    void* h_labels = nullptr;  // pinned: n u8 bins (label + 1) + one int (the error flag) land here before the caller's array
-    size_t h_labels_cap = 0;
-    hipEvent_t h_ev[kLabelChunks] = {nullptr, nullptr, nullptr, nullptr};
-    void* h_views = nullptr;   // pinned: view descriptors + culling planes on their way to d_views / d_cull
-    size_t h_views_cap = 0;
-    hipEvent_t h_views_ev = nullptr;
-    std::vector<ViewDesc> own_views;  // gsx_vote_import: this rank's own views, for gsx_vote_import_undo
-    int own_first_view = 0;
-    const void* pool_base = nullptr;  // gsx_vote_import: the maps live in a caller-owned gathered pool, not in segpool
-    int n_flushed = 0;         // views [0, n_flushed) are already in the planes
-    bool planes_valid = false;  // planes hold votes (zeroed at begin/rewind)
-    bool planes_zero = false;   // planes are known to be all-zero
-    bool planes_stale = false;  // planes hold a rewound run's votes; the next fresh flush overwrites them
-    DevBuf cnt, fv;             // [bins][n_pad] counters / first-view codes (u8 or u16)
-    DevBuf keys, labels;        // [n_pad] int32
-    DevBuf labels8;             // [n] u8: bin = label + 1, what labels_to_host sends over PCIe
-    DevBuf bcnt, bcodes;        // > 255 views on one GPU: per-batch u8 count planes [S][bins][n_pad], tie codes u16 [S][n_pad]
-    DevBuf cand, codes;         // exchange v3: candidate masks u32[8][sn] of this slab; tie codes u16[n_pad]
-    // the layout gsx_vote_flush_counts / gsx_vote_tie_codes last wrote into cnt / codes: their kernels write the Gaussians (whole
-    // workgroups of them) only, so the pad entries behind them are zero as long as the layout is still this one
-    long long counts_n = -1, counts_npad = -1, counts_sn = -1, codes_n = -1, codes_npad = -1;
-    int counts_bins = -1;
-    bool labels_valid = false;
-    // early vote (vote.hip: early_vote_stage): the views [0, early_done) are voted on a second stream while the host is
-    // still handing over the rest of the run; vote_finalize then only walks the views behind them
-    int opt_filter_project = 1;  // fp32 filter in front of the two fp64 divisions of the projection (vote.hip: project_filtered); exact by construction
-    int opt_early_vote = 1;      // 0: off, 1: for runs worth it (one rank holds all <= 255 views, a large scene), 2: whenever possible (tests)
-    int opt_early_at = 0;        // the stage starts when this many permille of the announced views are staged; 0: chosen from the run's own hand-over rate
-    std::chrono::steady_clock::time_point early_t0;  // first gsx_vote_view of the run
-    int opt_early_replay = 1;    // 1 (default since round 3): the early stage only records the votes, the last stage replays them (vote_record_kernel / vote_fused_replay_kernel); 0: count + first-view planes and the fold
-    bool early_replayed = false; // this run's early stage was a record-only one
-    int early_state = 0;         // 0: not started in this run, 1: started, -1: not available any more (rewind, pool moved)
-    int early_done = 0;          // views [0, early_done) are in ecnt / efv (or, > 255 announced views, in the first early_batches planes of bcnt)
-    int early_batches = 0;       // > 255 announced views: batches of labels_batched() whose count kernels already ran on stream2
-    hipStream_t stream2 = nullptr;
-    bool stream_borrowed = false; // (a twin of gsx_render_views) `stream` is the parent context's second stream: not this context's to destroy
-    bool early_inflight = false; // early_done_ev was recorded on stream2 and c->stream has not been ordered behind it yet (early_join)
-    hipEvent_t early_maps_ev = nullptr, early_done_ev = nullptr, early_up_ev = nullptr;
-    DevBuf ecnt, efv;            // u8 [wave][bin][64]: counts / first-view codes of the early views
-    DevBuf erec;                 // u8 [wave][view][64]: bin + 1 voted by each Gaussian in each early view
-    DevBuf e_views, e_cull;      // descriptors and culling planes (pitch kEarlyPitch) of the run's views, filled stage by stage
-    void* h_early = nullptr;     // pinned staging of both
-    size_t h_early_cap = 0;
+    VotePlanes planes;
+    hipStream_t stream2 = nullptr;  // the early vote's stream (vote.hip: second_stream); gsx_render_views borrows it
+    bool stream_borrowed = false;   // (a twin of gsx_render_views) `stream` is the parent context's second stream: not this context's to destroy
+    EarlyVote early;
+    VoteStaging hstage;
 
     // rasterizer (render_scene.hip / render_pre.hip / render.hip / blend.hip)
     RenderScene scene;
@@ -387,7 +528,7 @@ struct Ctx {
     // ... with ONE pre pass per group of frames (pre_multi_kernel), issued by this context for all of them
     DevBuf r_pre_args;                   // pre_multi_kernel's per-view arguments, one slot per record set
     std::vector<unsigned long long> r_pre_args_host;  // ... and their host copies (8-byte aligned; alive while the H2D copies run)
-    hipEvent_t r_pre_ev[kPreSets] = {nullptr, nullptr, nullptr};  // recorded behind the pre pass that filled set s
+    Event r_pre_ev[kPreSets];            // recorded behind the pre pass that filled set s
 
     // nearest-neighbour search (normals.hip)
     int opt_nn_brute = 0;                // 1: a 1 x 1 x 1 grid, i.e. every query visits every point (the search the grid is tested against)
@@ -417,10 +558,8 @@ struct Ctx {
     DevBuf iou_table;                    // u64 [pair][P + 1][G + 1], then u32 [pair]: lowest flat index out of range
     DevBuf iou_top;                      // int32 [h w]
     DevBuf iou_raw[2];                   // host inputs: the two raw masks (or pairs of label maps) in flight ...
-    void* iou_pin[2] = {nullptr, nullptr};  // ... and the pinned staging pair they come through
-    size_t iou_pin_cap[2] = {0, 0};
-    hipEvent_t iou_ev[2] = {nullptr, nullptr};  // recorded behind a slot's H2D copy
-    bool iou_ev_pending[2] = {false, false};
+    PinBuf iou_pin[2];                   // ... and the pinned staging pair they come through
+    Event iou_ev[2];                     // recorded behind a slot's H2D copy
     int iou_slot = 0;
 
     // class maps from network outputs (segmap.hip)
@@ -452,7 +591,7 @@ struct ProfScope {
 int vote_begin(Ctx* c, int n_classes, int first_view, int total_views);
 int vote_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h);
 int early_pool_moves(Ctx* c);    // the seg pool is about to be re-allocated: wait for the early vote that reads it, drop its result
-void vote_release_host(Ctx* c);  // pinned buffers, events, worker pool, second stream (gsx_destroy)
+void vote_release_host(Ctx* c);  // the second stream (gsx_destroy)
 int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size);
 // handover.hip: segmentation maps into the seg pool, descriptors between ranks
 int vote_view_host(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h);
@@ -469,7 +608,6 @@ int vote_views_match_uniform(Ctx* c, int n, const gsx_camera* cams, int seg_w, i
 Workers* host_workers(Ctx* c, const void* near = nullptr);  // the context's pool, created at first use (nullptr: pack on the caller)
 int host_threads(Ctx* c);
 int vote_flush_pending(Ctx* c);  // queue the DMA of packed host maps that are still waiting for their group to fill
-void handover_release(Ctx* c);   // rings, their events, staging, worker pool
 void segpack_constants(int32_t out[8]);
 int debug_host_pack(const void* seg, int seg_dtype, int w, int h, int n_classes, int tiled, int coarse, int threads,
                     uint8_t* out, int64_t out_cap, int64_t* bytes, int64_t* coarse_off, int32_t* bad);
@@ -593,7 +731,6 @@ int iou_masks(Ctx* c, bool device, int n_masks, const void* const* masks, int ma
 int iou_label_maps(Ctx* c, bool device, int n_pairs, const void* const* pred, int pred_dtype, int n_pred_classes, const void* const* gt,
                    int gt_dtype, int n_gt_classes, int h, int w, int64_t* table_out);
 int masks_top_index(Ctx* c, int n_masks, const void* const* masks, int mask_dtype, int h, int w, int32_t* index_out);
-void iou_release(Ctx* c);  // pinned staging pair and its events (gsx_destroy)
 void iou_constants(int32_t out[8]);
 // segmap.hip
 int segmap_from_logits(Ctx* c, const void* logits, int dtype, int n, int C, int h, int w, int out_w, int out_h, int32_t* maps);

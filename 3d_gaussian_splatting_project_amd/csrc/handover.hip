@@ -212,25 +212,25 @@ __global__ __launch_bounds__(kBlock) void seg_expand_kernel(ExpandArgs a) {
 // host side: the pool
 // -------------------------------------------------------------------------------------------------
 static int pool_reserve(Ctx* c, size_t need) {
-    if (need <= c->segpool.cap) return GSX_OK;
+    if (need <= c->run.segpool.cap) return GSX_OK;
     int rc = vote_flush_pending(c);  // the pool is about to move: maps still waiting in the pinned ring go up first
     if (rc) return rc;
     if ((rc = early_pool_moves(c))) return rc;  // ... and an early stage may be reading the pool that is about to be freed
-    size_t cap = c->segpool.cap ? c->segpool.cap : ((size_t)64 << 20);
+    size_t cap = c->run.segpool.cap ? c->run.segpool.cap : ((size_t)64 << 20);
     while (cap < need) cap *= 2;
     void* np = nullptr;
     GSX_HIP(c, hipMalloc(&np, cap));
-    if (c->seg_used) {
-        hipError_t e = hipMemcpyAsync(np, c->segpool.p, c->seg_used, hipMemcpyDeviceToDevice, c->stream);
+    if (c->run.seg_used) {
+        hipError_t e = hipMemcpyAsync(np, c->run.segpool.p, c->run.seg_used, hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) {
             (void)hipFree(np);
             return fail(c, GSX_E_HIP, "seg pool growth copy failed: %s", hipGetErrorString(e));
         }
     }
-    c->segpool.release();
-    c->segpool.p = np;
-    c->segpool.cap = cap;
+    c->run.segpool.release();
+    c->run.segpool.p = np;
+    c->run.segpool.cap = cap;
     return GSX_OK;
 }
 
@@ -238,8 +238,8 @@ static int pool_reserve(Ctx* c, size_t need) {
 // Common front part of gsx_vote_view / gsx_vote_views_device: argument checks, the map's layout, room in the pool.
 static int view_prologue(Ctx* c, const char* who, const void* cams, const void* seg, int n, int seg_dtype, int seg_w, int seg_h,
                          int img_w, int img_h, MapLayout& L) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "%s before vote_begin", who);
-    if (c->pool_base) return fail(c, GSX_E_STATE, "%s after gsx_vote_import: the run's views are final; start the next one with gsx_vote_begin", who);
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "%s before vote_begin", who);
+    if (c->run.pool_base) return fail(c, GSX_E_STATE, "%s after gsx_vote_import: the run's views are final; start the next one with gsx_vote_begin", who);
     if (!cams || !seg) return fail(c, GSX_E_INVALID, "%s: NULL argument", who);
     if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1)
         return fail(c, GSX_E_INVALID, "%s: sizes must be positive (seg %dx%d, image %dx%d)", who, seg_w, seg_h, img_w, img_h);
@@ -247,22 +247,22 @@ static int view_prologue(Ctx* c, const char* who, const void* cams, const void* 
         return fail(c, GSX_E_RANGE, "%s: segmentation map %dx%d exceeds 65535 pixels a side", who, seg_w, seg_h);
     if (seg_dtype != GSX_SEG_I32 && seg_dtype != GSX_SEG_I64 && seg_dtype != GSX_SEG_U8 && seg_dtype != GSX_SEG_U8_LABELS)
         return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
-    if (c->first_view + (int)c->views.size() + n > c->total_views)
-        return fail(c, GSX_E_RANGE, "%s: more views than total_views=%d announced at vote_begin", who, c->total_views);
-    if (c->local_codes && (int)c->views.size() + n > kMaxBatch)
+    if (c->run.first_view + (int)c->run.views.size() + n > c->run.total_views)
+        return fail(c, GSX_E_RANGE, "%s: more views than total_views=%d announced at vote_begin", who, c->run.total_views);
+    if (c->run.local_codes && (int)c->run.views.size() + n > kMaxBatch)
         return fail(c, GSX_E_RANGE, "%s: the all-to-all exchange keeps 8-bit per-rank counters: at most %d views per rank", who,
                     kMaxBatch);
     GSX_HIP(c, hipSetDevice(c->device));
     // bin 255 must be free to mean "mixed" in the coarse level
-    L = map_layout(seg_w, seg_h, c->opt_seg_tiled != 0, c->opt_seg_coarse && c->bins <= 255);
+    L = map_layout(seg_w, seg_h, c->vopt.seg_tiled != 0, c->vopt.seg_coarse && c->run.bins <= 255);
     if (L.map_bytes > 0xffffffffull) return fail(c, GSX_E_RANGE, "%s: segmentation map %dx%d exceeds 4 GiB", who, seg_w, seg_h);
     const size_t stride = align256(L.map_bytes);  // 256-B aligned maps
-    const size_t off = align256(c->seg_used);
+    const size_t off = align256(c->run.seg_used);
     size_t need = off + stride * (size_t)n;
-    if (c->views.empty()) {
+    if (c->run.views.empty()) {
         // first view of a run: room for all announced views of this geometry at once (capped), so that the pool is
         // not re-allocated and copied while maps stream in
-        const size_t all = stride * (size_t)(c->total_views - c->first_view);
+        const size_t all = stride * (size_t)(c->run.total_views - c->run.first_view);
         need = std::max(need, std::min(all, (size_t)32 << 30));
     }
     return pool_reserve(c, need);
@@ -280,10 +280,10 @@ static void map_view_desc(ViewDesc& vd, const gsx_camera* cam, const MapLayout& 
 static void push_view(Ctx* c, const gsx_camera* cam, const MapLayout& L, size_t off, int img_w, int img_h) {
     ViewDesc vd;
     map_view_desc(vd, cam, L, off, img_w, img_h);
-    c->views.push_back(vd);
-    c->views_dirty = true;
-    c->seg_used = off + L.map_bytes;
-    c->labels_valid = false;
+    c->run.views.push_back(vd);
+    c->run.views_dirty = true;
+    c->run.seg_used = off + L.map_bytes;
+    c->run.labels_valid = false;
 }
 
 static void launch_pack(Ctx* c, const PackArgs& a, int jobs, int seg_dtype, bool vec) {
@@ -310,12 +310,11 @@ void segpack_constants(int32_t out[8]) {
 Workers* host_workers(Ctx* c, const void* near) {
     if (!c->ho.workers) {
         try {
-            c->ho.workers = new Workers(c->opt_host_threads > 0 ? c->opt_host_threads : default_host_threads(), numa_node_of(near));
+            c->ho.workers.reset(new Workers(c->vopt.host_threads > 0 ? c->vopt.host_threads : default_host_threads(), numa_node_of(near)));
         } catch (...) {  // out of memory (a thread that cannot be started is handled inside: the pool then has one thread)
-            c->ho.workers = nullptr;
         }
     }
-    return c->ho.workers;  // nullptr: single-threaded packing on the calling thread
+    return c->ho.workers.get();  // nullptr: single-threaded packing on the calling thread
 }
 
 // ---- host maps (gsx_vote_view): the three transfer forms ------------------------------------------------------------------
@@ -328,19 +327,9 @@ static constexpr int kRingSlots = kDmaBatch * kDmaGroups;
 static int relay_ring(Ctx* c, size_t slot_bytes, bool compact) {
     int rc = vote_flush_pending(c);
     if (rc) return rc;
-    for (int g = 0; g < kDmaGroups; ++g) {
-        if (c->ho.hring_busy[g]) GSX_HIP(c, hipEventSynchronize(c->ho.hring_ev[g]));
-        c->ho.hring_busy[g] = false;
-        if (!c->ho.hring_ev[g]) GSX_HIP(c, hipEventCreateWithFlags(&c->ho.hring_ev[g], hipEventDisableTiming));
-    }
-    if (c->ho.hring_bytes < slot_bytes * kRingSlots) {
-        if (c->ho.hring) GSX_HIP(c, hipHostFree(c->ho.hring));
-        c->ho.hring = nullptr;
-        c->ho.hring_bytes = 0;
-        GSX_HIP(c, hipHostMalloc(&c->ho.hring, slot_bytes * kRingSlots, hipHostMallocDefault));
-        c->ho.hring_bytes = slot_bytes * kRingSlots;
-    }
-    if (!compact) std::memset(c->ho.hring, 0, slot_bytes * kRingSlots);  // the bytes between a map's end and its stride travel too
+    for (Event& ev : c->ho.hring_ev) GSX_HIP(c, ev.wait());
+    GSX_HIP(c, c->ho.hring.ensure(slot_bytes * kRingSlots));
+    if (!compact) std::memset(c->ho.hring.p, 0, slot_bytes * kRingSlots);  // the bytes between a map's end and its stride travel too
     c->ho.hring_slot = slot_bytes;
     c->ho.hring_compact = compact;
     c->ho.hring_next = 0;
@@ -351,35 +340,32 @@ static int relay_ring(Ctx* c, size_t slot_bytes, bool compact) {
 
 // The last views of the run (as announced to vote_begin) go up one by one: a group waiting for more maps would put its DMA
 // between the last hand-over and the vote.
-static bool run_tail(const Ctx* c) { return c->total_views - c->first_view - (int)c->views.size() < kDmaBatch; }
+static bool run_tail(const Ctx* c) { return c->run.total_views - c->run.first_view - (int)c->run.views.size() < kDmaBatch; }
 
 // Compact ring: records of a group lie back to back (a record is as long as its map has mixed cells): one DMA per group moves
 // exactly the bytes in use, and a group takes as many records as fit (at most kCompactBatch).
 static int hand_over_compact(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, const MapLayout& L, const CompactLayout& CL,
                              size_t slot_bytes, int img_w, int img_h) {
     int rc = GSX_OK;
-    const size_t off = align256(c->seg_used);
+    const size_t off = align256(c->run.seg_used);
     const size_t gcap = (size_t)kDmaBatch * slot_bytes;
     if (c->ho.grp_recs == 0) {
-        if (c->ho.hring_busy[c->ho.cgrp]) {  // the group's previous DMA must have left the buffer
-            GSX_HIP(c, hipEventSynchronize(c->ho.hring_ev[c->ho.cgrp]));
-            c->ho.hring_busy[c->ho.cgrp] = false;
-        }
+        GSX_HIP(c, c->ho.hring_ev[c->ho.cgrp].wait());  // the group's previous DMA must have left the buffer
         c->ho.grp_used = 0;
     }
     if (c->ho.h_scratch_cap < L.fine_bytes) {
-        std::free(c->ho.h_scratch);
-        c->ho.h_scratch = nullptr;
+        c->ho.h_scratch.reset();  // the old block goes before the new one comes
         c->ho.h_scratch_cap = 0;
         const size_t cap = (L.fine_bytes + 4095) / 4096 * 4096;
-        if (!(c->ho.h_scratch = std::aligned_alloc(4096, cap))) return fail(c, GSX_E_HIP, "vote_view: out of host memory");
+        c->ho.h_scratch.reset(static_cast<uint8_t*>(std::aligned_alloc(4096, cap)));
+        if (!c->ho.h_scratch) return fail(c, GSX_E_HIP, "vote_view: out of host memory");
         c->ho.h_scratch_cap = cap;
     }
-    uint8_t* rec = static_cast<uint8_t*>(c->ho.hring) + (size_t)c->ho.cgrp * gcap + c->ho.grp_used;
+    uint8_t* rec = c->ho.hring.as<uint8_t>() + (size_t)c->ho.cgrp * gcap + c->ho.grp_used;
     size_t blocks = 0;
-    if (!(c->opt_ablate & 2) &&  // timing experiment only: the DMA stream without the host pass; results invalid
-        host_pack_map_compact(host_workers(c, seg), seg, seg_dtype, L, c->bins, static_cast<uint8_t*>(c->ho.h_scratch), rec, &blocks))
-        return fail(c, GSX_E_RANGE, "vote_view: segmentation map holds a label outside [-1, %d]", c->n_classes - 1);
+    if (!(c->vopt.ablate & 2) &&  // timing experiment only: the DMA stream without the host pass; results invalid
+        host_pack_map_compact(host_workers(c, seg), seg, seg_dtype, L, c->run.bins, c->ho.h_scratch.get(), rec, &blocks))
+        return fail(c, GSX_E_RANGE, "vote_view: segmentation map holds a label outside [-1, %d]", c->run.n_classes - 1);
     if (c->ho.pend_count && (L.w != c->ho.pend_L.w || L.h != c->ho.pend_L.h)) {  // one expansion launch = one geometry
         if ((rc = vote_flush_pending(c))) return rc;
     }
@@ -409,15 +395,12 @@ static int hand_over_compact(Ctx* c, const gsx_camera* cam, const void* seg, int
 static int hand_over_pool_form(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, const MapLayout& L, size_t stride, int img_w,
                                int img_h) {
     int rc = GSX_OK;
-    const size_t off = align256(c->seg_used);
+    const size_t off = align256(c->run.seg_used);
     const int s = c->ho.hring_next, g = s / kDmaBatch;
-    if (s % kDmaBatch == 0 && c->ho.hring_busy[g]) {  // the group's previous DMA must have left the buffer
-        GSX_HIP(c, hipEventSynchronize(c->ho.hring_ev[g]));
-        c->ho.hring_busy[g] = false;
-    }
-    uint8_t* slot = static_cast<uint8_t*>(c->ho.hring) + (size_t)s * stride;
-    if (!(c->opt_ablate & 2) && host_pack_map(host_workers(c, seg), seg, seg_dtype, L, c->bins, slot))
-        return fail(c, GSX_E_RANGE, "vote_view: segmentation map holds a label outside [-1, %d]", c->n_classes - 1);
+    if (s % kDmaBatch == 0) GSX_HIP(c, c->ho.hring_ev[g].wait());  // the group's previous DMA must have left the buffer
+    uint8_t* slot = c->ho.hring.as<uint8_t>() + (size_t)s * stride;
+    if (!(c->vopt.ablate & 2) && host_pack_map(host_workers(c, seg), seg, seg_dtype, L, c->run.bins, slot))
+        return fail(c, GSX_E_RANGE, "vote_view: segmentation map holds a label outside [-1, %d]", c->run.n_classes - 1);
     if (c->ho.pend_count && off != c->ho.pend_dst + (size_t)c->ho.pend_count * stride) {  // the pool moved on (device maps in between)
         if ((rc = vote_flush_pending(c))) return rc;
     }
@@ -439,41 +422,23 @@ static int hand_over_pool_form(Ctx* c, const gsx_camera* cam, const void* seg, i
 // GPU.  The range check is then the device-side one (reported with the labels).
 static int hand_over_raw(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, const MapLayout& L, int img_w, int img_h) {
     PinSlot& slot = c->ho.ring[c->ho.ring_next];
-    if (slot.busy) {
-        GSX_HIP(c, hipEventSynchronize(slot.ev));
-        slot.busy = false;
-    }
-    if (slot.cap < L.map_bytes) {
-        if (slot.p) GSX_HIP(c, hipHostFree(slot.p));
-        slot.p = nullptr;
-        slot.cap = 0;
-        const size_t cap = (L.map_bytes + ((size_t)1 << 20) - 1) >> 20 << 20;
-        GSX_HIP(c, hipHostMalloc(&slot.p, cap, hipHostMallocDefault));
-        slot.cap = cap;
-    }
-    if (!slot.ev) GSX_HIP(c, hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
+    GSX_HIP(c, slot.ev.wait());
     const size_t raw = seg_elem_size(seg_dtype) * (size_t)L.w * (size_t)L.h;
-    if (slot.cap < raw) {
-        GSX_HIP(c, hipHostFree(slot.p));
-        slot.p = nullptr;
-        slot.cap = 0;
-        GSX_HIP(c, hipHostMalloc(&slot.p, raw, hipHostMallocDefault));
-        slot.cap = raw;
-    }
+    // room for the raw map and for its packed form, whichever is larger; a slot that grows gets the packed form's MiB at least
+    GSX_HIP(c, slot.buf.ensure(std::max(L.map_bytes, raw), (L.map_bytes + ((size_t)1 << 20) - 1) >> 20 << 20));
     DevBuf& land = c->ho.dstage[c->ho.ring_next];
     GSX_HIP(c, land.ensure(raw));
-    host_copy(host_workers(c, seg), slot.p, seg, raw);
-    GSX_HIP(c, hipMemcpyAsync(land.p, slot.p, raw, hipMemcpyHostToDevice, c->stream));
-    const size_t off = align256(c->seg_used);
+    host_copy(host_workers(c, seg), slot.buf.p, seg, raw);
+    GSX_HIP(c, hipMemcpyAsync(land.p, slot.buf.p, raw, hipMemcpyHostToDevice, c->stream));
+    const size_t off = align256(c->run.seg_used);
     PackArgs a{};
     a.src[0] = land.p;
-    a.dst[0] = c->segpool.as<uint8_t>() + off;
-    a.view[0] = c->first_view + (int)c->views.size();
-    pack_geometry(a, L, c->bins, c->errflag.as<int>());
+    a.dst[0] = c->run.segpool.as<uint8_t>() + off;
+    a.view[0] = c->run.first_view + (int)c->run.views.size();
+    pack_geometry(a, L, c->run.bins, c->run.errflag.as<int>());
     launch_pack(c, a, 1, seg_dtype, L.w % 4 == 0);
     GSX_HIP(c, hipGetLastError());
-    GSX_HIP(c, hipEventRecord(slot.ev, c->stream));  // after the kernel: it is the last reader of this slot's landing zone
-    slot.busy = true;
+    GSX_HIP(c, slot.ev.record(c->stream));  // after the kernel: it is the last reader of this slot's landing zone
     c->ho.ring_next = (c->ho.ring_next + 1) % kPinSlots;
     push_view(c, cam, L, off, img_w, img_h);
     return GSX_OK;
@@ -483,13 +448,13 @@ int vote_view_host(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype
     MapLayout L;
     int rc = view_prologue(c, "vote_view", cam, seg, 1, seg_dtype, seg_w, seg_h, img_w, img_h, L);
     if (rc) return rc;
-    if (!c->opt_host_pack) return hand_over_raw(c, cam, seg, seg_dtype, L, img_w, img_h);
+    if (!c->vopt.host_pack) return hand_over_raw(c, cam, seg, seg_dtype, L, img_w, img_h);
     const size_t stride = align256(L.map_bytes);
     // compact transfer form (host_pack.hpp) whenever the pool form has both levels; else the pool form itself
-    const bool compact = c->opt_host_compact && L.strip_bytes && L.cstrip_bytes;
+    const bool compact = c->vopt.host_compact && L.strip_bytes && L.cstrip_bytes;
     const CompactLayout CL = compact ? compact_layout(L) : CompactLayout{};
     const size_t slot_bytes = compact ? align256(CL.capacity) : stride;
-    if (c->ho.hring_slot != slot_bytes || !c->ho.hring || c->ho.hring_compact != compact) {
+    if (c->ho.hring_slot != slot_bytes || !c->ho.hring.p || c->ho.hring_compact != compact) {
         if ((rc = relay_ring(c, slot_bytes, compact))) return rc;
     }
     return compact ? hand_over_compact(c, cam, seg, seg_dtype, L, CL, slot_bytes, img_w, img_h)
@@ -513,14 +478,14 @@ int vote_views_device(Ctx* c, int n, const gsx_camera* cams, const void* const* 
         bool vec = seg_w % 4 == 0;
         size_t off = 0;
         for (int k = 0; k < m; ++k) {
-            off = align256(c->seg_used);
+            off = align256(c->run.seg_used);
             a.src[k] = segs[i0 + k];
-            a.dst[k] = c->segpool.as<uint8_t>() + off;
-            a.view[k] = c->first_view + (int)c->views.size();
+            a.dst[k] = c->run.segpool.as<uint8_t>() + off;
+            a.view[k] = c->run.first_view + (int)c->run.views.size();
             vec = vec && reinterpret_cast<uintptr_t>(segs[i0 + k]) % (4 * esz) == 0;
             push_view(c, cams + i0 + k, L, off, img_w, img_h);
         }
-        pack_geometry(a, L, c->bins, c->errflag.as<int>());
+        pack_geometry(a, L, c->run.bins, c->run.errflag.as<int>());
         launch_pack(c, a, m, seg_dtype, vec);
         GSX_HIP(c, hipGetLastError());
     }
@@ -537,25 +502,24 @@ int vote_flush_pending(Ctx* c) {
         const int g = c->ho.pend_group;
         const size_t gcap = (size_t)kDmaBatch * c->ho.hring_slot;
         GSX_HIP(c, c->ho.cstage.ensure(gcap));
-        const uint8_t* src = static_cast<uint8_t*>(c->ho.hring) + (size_t)g * gcap;
-        if (!(c->opt_ablate & 1))  // timing experiment only (tools/tail_probe.py): the host pass without its DMA; results invalid
+        const uint8_t* src = c->ho.hring.as<uint8_t>() + (size_t)g * gcap;
+        if (!(c->vopt.ablate & 1))  // timing experiment only (tools/tail_probe.py): the host pass without its DMA; results invalid
             GSX_HIP(c, hipMemcpyAsync(c->ho.cstage.as<uint8_t>() + c->ho.pend_lo, src + c->ho.pend_lo, c->ho.grp_used - c->ho.pend_lo, hipMemcpyHostToDevice,
                                       c->stream));
-        GSX_HIP(c, hipEventRecord(c->ho.hring_ev[g], c->stream));
-        c->ho.hring_busy[g] = true;
+        GSX_HIP(c, c->ho.hring_ev[g].record(c->stream));
         const MapLayout& L = c->ho.pend_L;
         const CompactLayout CL = compact_layout(L);
         ExpandArgs a{};
         for (int k = 0; k < c->ho.pend_count; ++k) {
             a.rec[k] = c->ho.cstage.as<uint8_t>() + c->ho.pend_rec[k];
-            a.map[k] = c->segpool.as<uint8_t>() + c->ho.pend_map[k];
+            a.map[k] = c->run.segpool.as<uint8_t>() + c->ho.pend_map[k];
         }
         a.w = L.w, a.h = L.h, a.strip_bytes = L.strip_bytes, a.cstrip_bytes = L.cstrip_bytes, a.cw = L.cw, a.ch = L.ch;
         a.strips = (L.w + 15) / 16;
         a.table_bytes = (unsigned)CL.table_bytes, a.stream_off = (unsigned)CL.stream_off, a.coarse_off = (unsigned)L.coarse_off;
         a.fine_bytes = (unsigned)L.fine_bytes, a.map_bytes = (unsigned)L.map_bytes, a.stride = (unsigned)align256(L.map_bytes);
         a.max_block = (unsigned)(L.cw - 1);
-        if (!(c->opt_ablate & 3)) {  // (an ablation of the hand-over leaves no valid record to expand)
+        if (!(c->vopt.ablate & 3)) {  // (an ablation of the hand-over leaves no valid record to expand)
             ProfScope ps(c, "seg_expand");
             hipLaunchKernelGGL(seg_expand_kernel, dim3((unsigned)CL.bands, (unsigned)c->ho.pend_count), dim3(kBlock), 0, c->stream, a);
             GSX_HIP(c, hipGetLastError());
@@ -565,11 +529,10 @@ int vote_flush_pending(Ctx* c) {
     }
     const int g = c->ho.pend_first / kDmaBatch;
     const size_t bytes = (size_t)c->ho.pend_count * c->ho.hring_slot;
-    if (!(c->opt_ablate & 1))
-        GSX_HIP(c, hipMemcpyAsync(c->segpool.as<uint8_t>() + c->ho.pend_dst, static_cast<uint8_t*>(c->ho.hring) + (size_t)c->ho.pend_first * c->ho.hring_slot,
+    if (!(c->vopt.ablate & 1))
+        GSX_HIP(c, hipMemcpyAsync(c->run.segpool.as<uint8_t>() + c->ho.pend_dst, c->ho.hring.as<uint8_t>() + (size_t)c->ho.pend_first * c->ho.hring_slot,
                                   bytes, hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(c, hipEventRecord(c->ho.hring_ev[g], c->stream));
-    c->ho.hring_busy[g] = true;
+    GSX_HIP(c, c->ho.hring_ev[g].record(c->stream));
     c->ho.pend_count = 0;
     // a group that was flushed before it was full keeps filling: its later slots are not in flight, and the event (recorded
     // again by the next flush) always stands for the group's LAST copy, which is what the next lap waits for
@@ -579,29 +542,6 @@ int vote_flush_pending(Ctx* c) {
 int host_threads(Ctx* c) {
     Workers* w = host_workers(c);
     return w ? w->threads() : 1;
-}
-
-void handover_release(Ctx* c) {
-    for (PinSlot& s : c->ho.ring) {
-        if (s.ev) (void)hipEventDestroy(s.ev);
-        if (s.p) (void)hipHostFree(s.p);
-        s = PinSlot{};
-    }
-    for (DevBuf& b : c->ho.dstage) b.release();
-    for (hipEvent_t& e : c->ho.hring_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    if (c->ho.hring) (void)hipHostFree(c->ho.hring);
-    c->ho.hring = nullptr;
-    c->ho.hring_bytes = c->ho.hring_slot = 0;
-    std::free(c->ho.h_scratch);
-    c->ho.h_scratch = nullptr;
-    c->ho.h_scratch_cap = 0;
-    c->ho.cstage.release();
-    c->ho.pend_count = 0;
-    delete c->ho.workers;
-    c->ho.workers = nullptr;
 }
 
 // test hook, host only: the packed form of one map exactly as gsx_vote_view stages it
@@ -649,18 +589,18 @@ int debug_host_pack_compact(const void* seg, int seg_dtype, int w, int h, int n_
 // the Gaussians with the single-GPU kernel, and only 4 bytes per Gaussian (the labels) are gathered.  No histogram,
 // no tie-break exchange: a slab sees all views in order, the tie rule is the single-GPU one.
 int vote_export(Ctx* c, int64_t reserve_bytes, void* blobs_out, void** pool_dev, int64_t* pool_bytes) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_export before vote_begin");
-    if (c->pool_base) return fail(c, GSX_E_STATE, "vote_export after vote_import");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_export before vote_begin");
+    if (c->run.pool_base) return fail(c, GSX_E_STATE, "vote_export after vote_import");
     GSX_HIP(c, hipSetDevice(c->device));
     if (reserve_bytes < 0) return fail(c, GSX_E_INVALID, "vote_export: negative size");
     if (const int rc = vote_flush_pending(c)) return rc;  // the caller is about to read the pool (all-gather)
-    const size_t used = align256(c->seg_used);
+    const size_t used = align256(c->run.seg_used);
     int rc = pool_reserve(c, std::max<size_t>(std::max<size_t>((size_t)reserve_bytes, used), 256));
     if (rc) return rc;
-    c->views_dirty = true;  // the pool may have moved
+    c->run.views_dirty = true;  // the pool may have moved
     static_assert(sizeof(ViewDesc) == GSX_VIEW_BLOB_BYTES, "view blob size is part of the ABI");
-    if (blobs_out && !c->views.empty()) std::memcpy(blobs_out, c->views.data(), sizeof(ViewDesc) * c->views.size());
-    if (pool_dev) *pool_dev = c->segpool.p;
+    if (blobs_out && !c->run.views.empty()) std::memcpy(blobs_out, c->run.views.data(), sizeof(ViewDesc) * c->run.views.size());
+    if (pool_dev) *pool_dev = c->run.segpool.p;
     if (pool_bytes) *pool_bytes = (int64_t)used;
     return GSX_OK;
 }
@@ -669,33 +609,33 @@ int vote_export(Ctx* c, int64_t reserve_bytes, void* blobs_out, void** pool_dev,
 // that imports optimistically and then learns that a peer's pool was not what the schedule assumed falls back to the plain
 // exchange, which starts from the rank's own views again).
 static void import_commit(Ctx* c, std::vector<ViewDesc>& all, const void* pool_all_dev) {
-    if (!c->pool_base) {  // (a second import on top of an import keeps the first one's saved state)
-        c->own_views.swap(c->views);
-        c->own_first_view = c->first_view;
+    if (!c->run.pool_base) {  // (a second import on top of an import keeps the first one's saved state)
+        c->run.own_views.swap(c->run.views);
+        c->run.own_first_view = c->run.first_view;
     }
-    c->views.swap(all);
-    c->views_dirty = true;
-    c->pool_base = pool_all_dev;
-    c->first_view = 0;
-    c->n_flushed = 0;
-    c->labels_valid = false;
+    c->run.views.swap(all);
+    c->run.views_dirty = true;
+    c->run.pool_base = pool_all_dev;
+    c->run.first_view = 0;
+    c->run.n_flushed = 0;
+    c->run.labels_valid = false;
 }
 
 int vote_import_undo(Ctx* c) {
-    if (!c->vote_begun || !c->pool_base) return fail(c, GSX_E_STATE, "vote_import_undo without a gsx_vote_import");
-    c->views.swap(c->own_views);
-    c->own_views.clear();
-    c->first_view = c->own_first_view;
-    c->pool_base = nullptr;
-    c->views_dirty = true;
-    c->n_flushed = 0;
-    c->labels_valid = false;
+    if (!c->run.begun || !c->run.pool_base) return fail(c, GSX_E_STATE, "vote_import_undo without a gsx_vote_import");
+    c->run.views.swap(c->run.own_views);
+    c->run.own_views.clear();
+    c->run.first_view = c->run.own_first_view;
+    c->run.pool_base = nullptr;
+    c->run.views_dirty = true;
+    c->run.n_flushed = 0;
+    c->run.labels_valid = false;
     return GSX_OK;
 }
 
 int vote_import(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* part_offsets, const void* blobs,
                 const void* pool_all_dev, int64_t pool_all_bytes) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_import before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_import before vote_begin");
     if (n_parts < 1 || !part_views || !part_offsets || !pool_all_dev || pool_all_bytes < 0)
         return fail(c, GSX_E_INVALID, "vote_import: bad arguments");
     long long total = 0;
@@ -732,7 +672,7 @@ int vote_import(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* p
 // options).  So the descriptors are derived here, the same way gsx_vote_view derives them (fill_view_desc + map_layout),
 // and the header exchange of the blobs and its host wait disappear from the protocol.
 static MapLayout uniform_layout(const Ctx* c, int seg_w, int seg_h) {
-    return map_layout(seg_w, seg_h, c->opt_seg_tiled != 0, c->opt_seg_coarse && c->bins <= 255);  // as view_prologue
+    return map_layout(seg_w, seg_h, c->vopt.seg_tiled != 0, c->vopt.seg_coarse && c->run.bins <= 255);  // as view_prologue
 }
 // a staged view has the map geometry that (L, image size) derive: everything of a descriptor that does not come from the camera
 static bool same_geometry(const ViewDesc& d, const MapLayout& L, int img_w, int img_h) {
@@ -741,7 +681,7 @@ static bool same_geometry(const ViewDesc& d, const MapLayout& L, int img_w, int 
 }
 
 int vote_map_stride(Ctx* c, int seg_w, int seg_h, int64_t* stride) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_map_stride before vote_begin (the layout depends on the number of classes)");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_map_stride before vote_begin (the layout depends on the number of classes)");
     if (!stride) return fail(c, GSX_E_INVALID, "vote_map_stride: NULL argument");
     if (seg_w < 1 || seg_h < 1 || seg_w > 65535 || seg_h > 65535) return fail(c, GSX_E_INVALID, "vote_map_stride: map %dx%d", seg_w, seg_h);
     const MapLayout L = uniform_layout(c, seg_w, seg_h);
@@ -752,19 +692,19 @@ int vote_map_stride(Ctx* c, int seg_w, int seg_h, int64_t* stride) {
 // Are this context's own views exactly views [0, n) of a uniform run as gsx_vote_import_uniform would derive them: n of them, view i
 // from cams[i] with this map and image size, at byte i * stride of the pool?  A rank asks before it votes on a schedule that assumes so.
 int vote_views_match_uniform(Ctx* c, int n, const gsx_camera* cams, int seg_w, int seg_h, int img_w, int img_h, int32_t* match) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_views_match_uniform before vote_begin");
-    if (c->pool_base) return fail(c, GSX_E_STATE, "vote_views_match_uniform after gsx_vote_import: the context holds imported views");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_views_match_uniform before vote_begin");
+    if (c->run.pool_base) return fail(c, GSX_E_STATE, "vote_views_match_uniform after gsx_vote_import: the context holds imported views");
     if (n < 0 || (n > 0 && !cams) || !match) return fail(c, GSX_E_INVALID, "vote_views_match_uniform: bad arguments");
     if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1 || seg_w > 65535 || seg_h > 65535)
         return fail(c, GSX_E_INVALID, "vote_views_match_uniform: map %dx%d, image %dx%d", seg_w, seg_h, img_w, img_h);
     const MapLayout L = uniform_layout(c, seg_w, seg_h);
     const size_t stride = align256(L.map_bytes);
     *match = 0;
-    if ((size_t)n != c->views.size()) return GSX_OK;
+    if ((size_t)n != c->run.views.size()) return GSX_OK;
     for (int i = 0; i < n; ++i) {
         ViewDesc d;
         map_view_desc(d, &cams[i], L, (size_t)i * stride, img_w, img_h);
-        if (std::memcmp(&d, &c->views[(size_t)i], sizeof d) != 0) return GSX_OK;  // (fill_view_desc zeroes the padding)
+        if (std::memcmp(&d, &c->run.views[(size_t)i], sizeof d) != 0) return GSX_OK;  // (fill_view_desc zeroes the padding)
     }
     *match = 1;
     return GSX_OK;
@@ -772,7 +712,7 @@ int vote_views_match_uniform(Ctx* c, int n, const gsx_camera* cams, int seg_w, i
 
 int vote_import_uniform(Ctx* c, int n_parts, const int32_t* part_views, const int64_t* part_offsets, const gsx_camera* cams,
                         int seg_w, int seg_h, int img_w, int img_h, const void* pool_all_dev, int64_t pool_all_bytes) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_import_uniform before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_import_uniform before vote_begin");
     if (n_parts < 1 || !part_views || !part_offsets || !pool_all_dev || pool_all_bytes < 0)
         return fail(c, GSX_E_INVALID, "vote_import_uniform: bad arguments");
     if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1 || seg_w > 65535 || seg_h > 65535)
@@ -796,7 +736,7 @@ int vote_import_uniform(Ctx* c, int n_parts, const int32_t* part_views, const in
             return fail(c, GSX_E_INVALID, "vote_import_uniform: the part offsets leave less than %llu bytes a view, the stride of a %dx%d map",
                         (unsigned long long)stride, seg_w, seg_h);
     // what this context staged itself is part of the run: its geometry must be the one the descriptors are derived for
-    for (const ViewDesc& o : c->pool_base ? c->own_views : c->views)
+    for (const ViewDesc& o : c->run.pool_base ? c->run.own_views : c->run.views)
         if (!same_geometry(o, L, img_w, img_h))
             return fail(c, GSX_E_INVALID, "vote_import_uniform: map %dx%d / image %dx%d, but gsx_vote_view staged a %dx%d map (scales %g, %g)",
                         seg_w, seg_h, img_w, img_h, o.seg_w, o.seg_h, o.wscale, o.hscale);

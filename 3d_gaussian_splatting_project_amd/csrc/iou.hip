@@ -314,32 +314,12 @@ static int iou_seg_bytes(int seg_dtype) {
     return 0;
 }
 
-void iou_release(Ctx* c) {
-    for (int s = 0; s < 2; ++s) {
-        if (c->iou_pin[s]) (void)hipHostFree(c->iou_pin[s]);
-        if (c->iou_ev[s]) (void)hipEventDestroy(c->iou_ev[s]);
-        c->iou_pin[s] = nullptr;
-        c->iou_pin_cap[s] = 0;
-        c->iou_ev[s] = nullptr;
-        c->iou_ev_pending[s] = false;
-    }
-}
-
 // the pinned staging pair and the two raw device buffers behind it: room for `bytes` per slot
 static int iou_stage_reserve(Ctx* c, size_t bytes) {
     for (int s = 0; s < 2; ++s) {
-        if (!c->iou_ev[s]) GSX_HIP(c, hipEventCreateWithFlags(&c->iou_ev[s], hipEventDisableTiming));
-        if (c->iou_pin_cap[s] < bytes) {
-            if (c->iou_pin[s]) {
-                GSX_HIP(c, hipStreamSynchronize(c->stream));
-                (void)hipHostFree(c->iou_pin[s]);
-                c->iou_pin[s] = nullptr;
-                c->iou_pin_cap[s] = 0;
-            }
-            GSX_HIP(c, hipHostMalloc(&c->iou_pin[s], bytes, hipHostMallocDefault));
-            c->iou_pin_cap[s] = bytes;
-        }
-        c->iou_ev_pending[s] = false;
+        if (c->iou_pin[s].p && c->iou_pin[s].cap < bytes) GSX_HIP(c, hipStreamSynchronize(c->stream));  // a copy may still read the old block
+        GSX_HIP(c, c->iou_pin[s].ensure(bytes));
+        c->iou_ev[s].pending = false;  // (every call ends with a stream synchronise: the previous call's copies are done)
         GSX_HIP(c, c->iou_raw[s].ensure(bytes));
     }
     return GSX_OK;
@@ -347,11 +327,8 @@ static int iou_stage_reserve(Ctx* c, size_t bytes) {
 
 // host arrays a (and b, at byte off_b) -> pinned slot -> raw device slot, queued on the ctx stream
 static int iou_stage(Ctx* c, int slot, const void* a, size_t na, const void* b, size_t nb, size_t off_b) {
-    if (c->iou_ev_pending[slot]) {  // the slot's previous copy has to have left the pinned buffer
-        GSX_HIP(c, hipEventSynchronize(c->iou_ev[slot]));
-        c->iou_ev_pending[slot] = false;
-    }
-    char* pin = static_cast<char*>(c->iou_pin[slot]);
+    GSX_HIP(c, c->iou_ev[slot].wait());  // the slot's previous copy has to have left the pinned buffer
+    char* pin = c->iou_pin[slot].as<char>();
     std::memcpy(pin, a, na);
     size_t total = na;
     if (b) {
@@ -359,8 +336,7 @@ static int iou_stage(Ctx* c, int slot, const void* a, size_t na, const void* b, 
         total = off_b + nb;
     }
     GSX_HIP(c, hipMemcpyAsync(c->iou_raw[slot].p, pin, total, hipMemcpyHostToDevice, c->stream));
-    GSX_HIP(c, hipEventRecord(c->iou_ev[slot], c->stream));
-    c->iou_ev_pending[slot] = true;
+    GSX_HIP(c, c->iou_ev[slot].record(c->stream));
     return GSX_OK;
 }
 

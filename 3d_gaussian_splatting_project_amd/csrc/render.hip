@@ -555,11 +555,6 @@ static int twin_sync_scene(Ctx* c, int k) {
 }
 
 void render_release_twin(Ctx* c) {
-    for (hipEvent_t& e : c->r_pre_ev)
-        if (e) {
-            (void)hipEventDestroy(e);
-            e = nullptr;
-        }
     for (Ctx*& t : c->twins) {
         if (!t) continue;
         (void)hipStreamSynchronize(t->stream);
@@ -610,8 +605,6 @@ int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* con
         for (int f = 0; f < F; ++f)
             for (PreSet& ps : ctxs[f]->frame.sets)
                 if ((rc = ensure_pre_set(c, ps, c->scene.rn))) return rc;
-        for (int s = 0; s < kPreSets; ++s)
-            if (!c->r_pre_ev[s]) GSX_HIP(c, hipEventCreateWithFlags(&c->r_pre_ev[s], hipEventDisableTiming));
     }
     auto issue_pre = [&](int g) -> int {  // this thread only; stream 0
         // set g % 3 was last read by the frames of group g - 3: every context must have completed them
@@ -624,7 +617,7 @@ int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* con
         for (int v = 0; v < nv; ++v) sets[v] = &ctxs[v]->frame.sets[set];
         const int rcp = launch_pre_multi(c, nv, cams + g * F, W, H, sets, set);  // (argument slot = record set)
         if (rcp) return rcp;
-        GSX_HIP(c, hipEventRecord(c->r_pre_ev[set], c->stream));
+        GSX_HIP(c, c->r_pre_ev[set].record(c->stream));
         pre_issued.store(g + 1, std::memory_order_release);
         return GSX_OK;
     };
@@ -639,7 +632,7 @@ int render_views(Ctx* c, int n, const gsx_camera* cams, int W, int H, float* con
                 } else {
                     while (pre_issued.load(std::memory_order_acquire) < g + 1 && !failed.load()) std::this_thread::yield();
                     if (failed.load()) break;
-                    const hipError_t e = hipStreamWaitEvent(t->stream, c->r_pre_ev[g % kPreSets], 0);
+                    const hipError_t e = c->r_pre_ev[g % kPreSets].stream_wait(t->stream);
                     if (e != hipSuccess) {
                         rcs[f] = fail(t, GSX_E_HIP, "render_views: hipStreamWaitEvent: %s", hipGetErrorString(e));
                         break;

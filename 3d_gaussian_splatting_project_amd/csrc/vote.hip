@@ -87,7 +87,7 @@ static inline int odd_dwords(int bytes) {
 // 0.5 - E of project_filtered() for the staged views (E grows with the frame: the largest one decides)
 static float filter_half_width(const Ctx* c) {
     int dim = 64;
-    for (const ViewDesc& v : c->views) dim = std::max(dim, std::max(v.cam_w, v.cam_h));
+    for (const ViewDesc& v : c->run.views) dim = std::max(dim, std::max(v.cam_w, v.cam_h));
     return (float)(0.5 - kFilterK * (double)dim * 5.9604644775390625e-08);
 }
 // The parameters of a walk over ALL staged views of the whole scene (host side; call after sync_views()).  Every launch starts
@@ -98,16 +98,16 @@ static FusedParams fused_params(Ctx* c, int stride_bytes_per_bin) {
     p.y = c->y.as<float>();
     p.z = c->z.as<float>();
     p.n = c->n;
-    p.views = c->d_views.as<ViewDesc>();
-    p.nviews = (int)c->views.size();
-    p.pool = c->segpool.as<uint8_t>();
-    p.bins = c->bins;
-    p.xcd_swizzle = c->opt_xcd_swizzle;
+    p.views = c->run.d_views.as<ViewDesc>();
+    p.nviews = (int)c->run.views.size();
+    p.pool = c->run.segpool.as<uint8_t>();
+    p.bins = c->run.bins;
+    p.xcd_swizzle = c->vopt.xcd_swizzle;
     p.perm = c->sorted ? c->perm.as<uint32_t>() : nullptr;
-    p.stride_dw = odd_dwords(c->bins * stride_bytes_per_bin);
-    p.cull = c->opt_wave_cull ? c->d_cull.as<double>() : nullptr;
-    p.cull_pitch = c->cull_pitch;
-    p.cull_tally = c->d_cull_tally.as<unsigned long long>();
+    p.stride_dw = odd_dwords(c->run.bins * stride_bytes_per_bin);
+    p.cull = c->vopt.wave_cull ? c->run.d_cull.as<double>() : nullptr;
+    p.cull_pitch = c->run.cull_pitch;
+    p.cull_tally = c->run.d_cull_tally.as<unsigned long long>();
     p.filt_h = filter_half_width(c);
     return p;
 }
@@ -922,11 +922,11 @@ void fill_view_desc(ViewDesc& vd, const gsx_camera* cam, int seg_w, int seg_h, i
 // a tiled map; coarse: ... and a coarse level.
 static inline int flat_div_mode(const Ctx* c, bool simple, bool coarse) {
     if (!simple) return kDivFlat;
-    return coarse && c->opt_seg_coarse ? (c->opt_filter_project ? kDivFiltCoarse : kDivFlatCoarse) : kDivFlatSimple;
+    return coarse && c->vopt.seg_coarse ? (c->vopt.filter_project ? kDivFiltCoarse : kDivFlatCoarse) : kDivFlatSimple;
 }
 // call after sync_views(): views_simple describes the staged batch
 static inline int div_mode(const Ctx* c) {
-    return c->opt_flat_project ? flat_div_mode(c, c->views_simple, c->views_coarse) : kDivExact;
+    return c->vopt.flat_project ? flat_div_mode(c, c->run.views_simple, c->run.views_coarse) : kDivExact;
 }
 // Kernel selection: calls f(std::integral_constant<int, DIV>{}) for the projection variant dm and returns what it returns
 // (the same type for every DIV: a kernel pointer).  FLAT_ONLY: f is instantiated for the four branchless variants only -
@@ -959,8 +959,8 @@ int project_all(Ctx* c, const gsx_camera* cam, const float* dx, const float* dy,
         // the filtered form is the vote kernels' (kDivFiltCoarse): frames up to 65535 pixels a side (hw32 exact, E < 1/64)
         const int dim = std::max(cam->width, cam->height);
         const float filt_h = (float)(0.5 - kFilterK * (double)std::max(dim, 64) * 5.9604644775390625e-08);
-        const bool filtered = c->opt_flat_project && c->opt_filter_project && dim <= 65535;
-        auto k = filtered ? project_kernel<kDivFiltCoarse> : c->opt_flat_project ? project_kernel<kDivFlat> : project_kernel<kDivExact>;
+        const bool filtered = c->vopt.flat_project && c->vopt.filter_project && dim <= 65535;
+        auto k = filtered ? project_kernel<kDivFiltCoarse> : c->vopt.flat_project ? project_kernel<kDivFlat> : project_kernel<kDivExact>;
         hipLaunchKernelGGL(k, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dx, dy, dz, (long long)n, dvd.as<ViewDesc>(), perm, ox.as<int>(),
                            oy.as<int>(), filtered ? filt_h : 0.f);
         e = hipGetLastError();
@@ -979,9 +979,9 @@ int project_all(Ctx* c, const gsx_camera* cam, const float* dx, const float* dy,
 // efv, erec, bcnt) or the pool it reads are touched again: by the last stage that uses its result, and just as much by every
 // path that DROPS the result (fewer views than announced, rewind, a new run) and is about to overwrite those buffers.
 int early_join(Ctx* c) {
-    if (!c->early_inflight) return GSX_OK;
-    GSX_HIP(c, hipStreamWaitEvent(c->stream, c->early_done_ev, 0));
-    c->early_inflight = false;
+    if (!c->early.inflight) return GSX_OK;
+    GSX_HIP(c, c->early.done_ev.stream_wait(c->stream));
+    c->early.inflight = false;
     return GSX_OK;
 }
 
@@ -992,33 +992,14 @@ int vote_begin(Ctx* c, int n_classes, int first_view, int total_views) {
         return fail(c, GSX_E_INVALID, "vote_begin: first_view=%d total_views=%d (need 0 <= first < total <= 65535)",
                     first_view, total_views);
     GSX_HIP(c, hipSetDevice(c->device));
-    c->n_classes = n_classes;
-    c->bins = n_classes + 1;
-    c->first_view = first_view;
-    c->total_views = total_views;
-    c->local_codes = c->opt_local_codes != 0;
-    c->wide = total_views > 255 && !c->local_codes;
-    c->slabs = c->opt_slabs > 0 ? c->opt_slabs : 1;
-    c->sn = ((c->n + c->slabs - 1) / c->slabs + 255) / 256 * 256;
-    if (c->sn == 0) c->sn = 256;
-    c->n_pad = c->sn * c->slabs;
-    c->views.clear();
+    c->run.begin_run(c->vopt, c->n, n_classes, first_view, total_views);
     c->ho.begin_run();
-    c->views_dirty = true;
-    c->pool_base = nullptr;
-    c->seg_used = 0;
-    c->n_flushed = 0;
-    c->planes_valid = false;
-    c->planes_zero = false;
-    c->planes_stale = false;
-    c->labels_valid = false;
+    c->planes.begin_run();
     if (const int rc = early_join(c)) return rc;  // an abandoned run's early stage may still be running: this run reuses its buffers
-    c->early_state = 0;
-    c->early_done = 0;
-    c->early_batches = 0;
-    GSX_HIP(c, c->errflag.ensure(sizeof(int)));
-    GSX_HIP(c, hipMemsetAsync(c->errflag.p, 0x7f, sizeof(int), c->stream));  // kNoBadView
-    c->vote_begun = true;
+    c->early.begin_run();
+    GSX_HIP(c, c->run.errflag.ensure(sizeof(int)));
+    GSX_HIP(c, hipMemsetAsync(c->run.errflag.p, 0x7f, sizeof(int), c->stream));  // kNoBadView
+    c->run.begun = true;
     return GSX_OK;
 }
 
@@ -1072,19 +1053,19 @@ static void cull_planes(const ViewDesc& v, double out[kCullStride * kCullPlanes]
 
 static constexpr size_t kTallyBytes = sizeof(unsigned long long) * kTallySlots * kTallyStride;
 static int ensure_tally(Ctx* c) {
-    if (c->d_cull_tally.p) return GSX_OK;
-    GSX_HIP(c, c->d_cull_tally.ensure(kTallyBytes));
-    GSX_HIP(c, hipMemsetAsync(c->d_cull_tally.p, 0, kTallyBytes, c->stream));
+    if (c->run.d_cull_tally.p) return GSX_OK;
+    GSX_HIP(c, c->run.d_cull_tally.ensure(kTallyBytes));
+    GSX_HIP(c, hipMemsetAsync(c->run.d_cull_tally.p, 0, kTallyBytes, c->stream));
     return GSX_OK;
 }
 
 int vote_culled(Ctx* c, int64_t* out, bool reset) {
     unsigned long long h = 0;
-    if (c->d_cull_tally.p) {
+    if (c->run.d_cull_tally.p) {
         GSX_HIP(c, hipSetDevice(c->device));
         std::vector<unsigned long long> slots(kTallySlots * kTallyStride);
-        GSX_HIP(c, hipMemcpyAsync(slots.data(), c->d_cull_tally.p, kTallyBytes, hipMemcpyDeviceToHost, c->stream));
-        if (reset) GSX_HIP(c, hipMemsetAsync(c->d_cull_tally.p, 0, kTallyBytes, c->stream));
+        GSX_HIP(c, hipMemcpyAsync(slots.data(), c->run.d_cull_tally.p, kTallyBytes, hipMemcpyDeviceToHost, c->stream));
+        if (reset) GSX_HIP(c, hipMemsetAsync(c->run.d_cull_tally.p, 0, kTallyBytes, c->stream));
         GSX_HIP(c, hipStreamSynchronize(c->stream));
         for (unsigned k = 0; k < kTallySlots; ++k) h += slots[(size_t)k * kTallyStride];
     }
@@ -1153,7 +1134,7 @@ static ViewKinds stage_views(const Ctx* c, int lo, int hi, const void* pool_base
     ViewKinds kinds{true, true};
     for (int i = lo; i < hi; ++i) {
         ViewDesc& v = dev[i - lo];
-        v = c->views[i];
+        v = c->run.views[i];
         v.seg_off += base;
         kinds.simple = kinds.simple && v.unit_scale && v.seg_row_bytes;
         kinds.coarse = kinds.coarse && v.coarse_row_bytes;
@@ -1169,54 +1150,45 @@ static ViewKinds stage_views(const Ctx* c, int lo, int hi, const void* pool_base
 // event, so nothing waits for the stream: the maps that vote_view queued keep flowing while this is prepared.
 static int sync_views(Ctx* c) {
     if (const int rc = vote_flush_pending(c)) return rc;  // every consumer of the views comes through here
-    if (!c->views_dirty) return GSX_OK;
-    const size_t nv = c->views.size();
+    if (!c->run.views_dirty) return GSX_OK;
+    const size_t nv = c->run.views.size();
     const size_t bytes = sizeof(ViewDesc) * (nv ? nv : 1);
-    GSX_HIP(c, c->d_views.ensure(bytes));
-    c->views_simple = c->views_coarse = false;  // no views: nothing to be simple about
+    GSX_HIP(c, c->run.d_views.ensure(bytes));
+    c->run.views_simple = c->run.views_coarse = false;  // no views: nothing to be simple about
     if (nv) {
         const int pitch = (int)((nv + 63) / 64 * 64);
         const size_t plane_doubles = (size_t)kCullStride * kCullPlanes * pitch;
         const size_t need = bytes + sizeof(double) * plane_doubles;
-        if (c->h_views_ev) GSX_HIP(c, hipEventSynchronize(c->h_views_ev));  // the previous upload has left the buffer
-        else GSX_HIP(c, hipEventCreateWithFlags(&c->h_views_ev, hipEventDisableTiming));
-        if (c->h_views_cap < need) {
-            if (c->h_views) GSX_HIP(c, hipHostFree(c->h_views));
-            c->h_views = nullptr;
-            c->h_views_cap = 0;
-            GSX_HIP(c, hipHostMalloc(&c->h_views, need * 2, hipHostMallocDefault));
-            c->h_views_cap = need * 2;
-        }
-        ViewDesc* dev = static_cast<ViewDesc*>(c->h_views);
-        double* planes = reinterpret_cast<double*>(static_cast<char*>(c->h_views) + bytes);
+        GSX_HIP(c, c->hstage.views_ev.wait());  // the previous upload has left the buffer
+        GSX_HIP(c, c->hstage.views.ensure(need, need * 2));
+        ViewDesc* dev = c->hstage.views.as<ViewDesc>();
+        double* planes = reinterpret_cast<double*>(c->hstage.views.as<char>() + bytes);
         std::memset(planes, 0, sizeof(double) * plane_doubles);
-        const ViewKinds kinds = stage_views(c, 0, (int)nv, c->pool_base ? c->pool_base : c->segpool.p, dev, planes, (size_t)pitch);
-        c->views_simple = kinds.simple;
-        c->views_coarse = kinds.coarse;
-        GSX_HIP(c, c->d_cull.ensure(sizeof(double) * plane_doubles));
-        GSX_HIP(c, hipMemcpyAsync(c->d_views.p, dev, bytes, hipMemcpyHostToDevice, c->stream));
-        GSX_HIP(c, hipMemcpyAsync(c->d_cull.p, planes, sizeof(double) * plane_doubles, hipMemcpyHostToDevice, c->stream));
-        GSX_HIP(c, hipEventRecord(c->h_views_ev, c->stream));
-        c->cull_pitch = pitch;
+        const ViewKinds kinds = stage_views(c, 0, (int)nv, c->run.pool_base ? c->run.pool_base : c->run.segpool.p, dev, planes, (size_t)pitch);
+        c->run.views_simple = kinds.simple;
+        c->run.views_coarse = kinds.coarse;
+        GSX_HIP(c, c->run.d_cull.ensure(sizeof(double) * plane_doubles));
+        GSX_HIP(c, hipMemcpyAsync(c->run.d_views.p, dev, bytes, hipMemcpyHostToDevice, c->stream));
+        GSX_HIP(c, hipMemcpyAsync(c->run.d_cull.p, planes, sizeof(double) * plane_doubles, hipMemcpyHostToDevice, c->stream));
+        GSX_HIP(c, c->hstage.views_ev.record(c->stream));
+        c->run.cull_pitch = pitch;
         if (const int rc = ensure_tally(c)) return rc;
     }
-    c->views_dirty = false;
+    c->run.views_dirty = false;
     return GSX_OK;
 }
 
 static int ensure_planes(Ctx* c) {
-    const size_t esz = c->wide ? 2 : 1;
-    const size_t bytes = (size_t)c->bins * (size_t)c->n_pad * esz;
-    const bool grew = bytes > c->cnt.cap || bytes > c->fv.cap;
-    c->counts_n = -1;  // cnt is about to hold planes of this layout: the next vote_flush_counts clears its pad entries again
-    GSX_HIP(c, c->cnt.ensure(bytes ? bytes : 4));
-    GSX_HIP(c, c->fv.ensure(bytes ? bytes : 4));
-    if (grew || !(c->planes_valid || c->planes_zero || c->planes_stale)) {
-        GSX_HIP(c, hipMemsetAsync(c->cnt.p, 0, bytes, c->stream));
-        GSX_HIP(c, hipMemsetAsync(c->fv.p, 0, bytes, c->stream));
-        c->planes_zero = true;
-        c->planes_valid = false;
-        c->planes_stale = false;
+    const size_t esz = c->run.wide ? 2 : 1;
+    const size_t bytes = (size_t)c->run.bins * (size_t)c->run.n_pad * esz;
+    const bool grew = bytes > c->planes.cnt.cap || bytes > c->planes.fv.cap;
+    c->planes.counts = PlaneLayout{};  // cnt is about to hold planes of this layout: the next vote_flush_counts clears its pad entries again
+    GSX_HIP(c, c->planes.cnt.ensure(bytes ? bytes : 4));
+    GSX_HIP(c, c->planes.fv.ensure(bytes ? bytes : 4));
+    if (grew || !c->planes.holds()) {
+        GSX_HIP(c, hipMemsetAsync(c->planes.cnt.p, 0, bytes, c->stream));
+        GSX_HIP(c, hipMemsetAsync(c->planes.fv.p, 0, bytes, c->stream));
+        c->planes.state = PlaneState::Zero;
     }
     return GSX_OK;
 }
@@ -1225,28 +1197,22 @@ static int ensure_planes(Ctx* c) {
 // element of every Gaussian with its first batch, so nothing is cleared up front (2 x 453 MB of memset per
 // step at C3).  Anything that reads the planes before such a flush clears them here.
 static int clear_stale_planes(Ctx* c) {
-    if (!c->planes_stale) return GSX_OK;
-    const size_t bytes = (size_t)c->bins * (size_t)c->n_pad * (c->wide ? 2 : 1);
-    GSX_HIP(c, hipMemsetAsync(c->cnt.p, 0, bytes, c->stream));
-    GSX_HIP(c, hipMemsetAsync(c->fv.p, 0, bytes, c->stream));
-    c->planes_stale = false;
-    c->planes_zero = true;
+    if (c->planes.state != PlaneState::Stale) return GSX_OK;
+    const size_t bytes = (size_t)c->run.bins * (size_t)c->run.n_pad * (c->run.wide ? 2 : 1);
+    GSX_HIP(c, hipMemsetAsync(c->planes.cnt.p, 0, bytes, c->stream));
+    GSX_HIP(c, hipMemsetAsync(c->planes.fv.p, 0, bytes, c->stream));
+    c->planes.state = PlaneState::Zero;
     return GSX_OK;
 }
 
 int vote_rewind(Ctx* c) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_rewind before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_rewind before vote_begin");
     GSX_HIP(c, hipSetDevice(c->device));
-    c->n_flushed = 0;
-    c->labels_valid = false;
-    c->early_state = -1;  // a rewound run is voted in one piece (its views are all there)
-    c->early_batches = 0;
+    c->run.n_flushed = 0;
+    c->run.labels_valid = false;
+    c->early.drop();  // a rewound run is voted in one piece (its views are all there)
     if (const int rc = early_join(c)) return rc;  // ... behind whatever the early stage is still doing to bcnt / ecnt / erec
-    if (c->planes_valid) {
-        c->planes_valid = false;
-        c->planes_zero = false;
-        c->planes_stale = true;  // cleared lazily, see clear_stale_planes
-    }
+    if (c->planes.state == PlaneState::Votes) c->planes.state = PlaneState::Stale;  // cleared lazily, see clear_stale_planes
     return GSX_OK;
 }
 
@@ -1273,7 +1239,7 @@ static int launch_walk(Ctx* c, const char* name, hipStream_t st, K k, long long 
     return GSX_OK;
 }
 // bytes of keys / labels: int32 [n_pad], never an empty buffer
-static inline size_t label_bytes(const Ctx* c) { return sizeof(int) * (size_t)(c->n_pad ? c->n_pad : 1); }
+static inline size_t label_bytes(const Ctx* c) { return sizeof(int) * (size_t)(c->run.n_pad ? c->run.n_pad : 1); }
 
 // ---- early vote ---------------------------------------------------------------------------------------------------
 // A run is the hand-over of its maps (the host pass over them, ~37 us per 1080p map) followed by the vote over all of
@@ -1296,15 +1262,15 @@ static constexpr size_t kEarlySlack = 64 * 260;           // the last stage read
 static constexpr size_t kEarlyCullDoubles = (size_t)kCullStride * kCullPlanes * kEarlyPitch;
 
 static bool early_common(const Ctx* c) {
-    return c->opt_early_vote && c->first_view == 0 && !c->local_codes && c->slabs == 1 && c->n_flushed == 0 && !c->pool_base &&
-           c->opt_flat_project && c->n > 0 && c->bins <= 255 &&
-           (c->opt_early_vote == 2 || (c->n >= kEarlyMinGaussians && c->total_views >= kEarlyMinViews));
+    return c->vopt.early_vote && c->run.first_view == 0 && !c->run.local_codes && c->run.slabs == 1 && c->run.n_flushed == 0 && !c->run.pool_base &&
+           c->vopt.flat_project && c->n > 0 && c->run.bins <= 255 &&
+           (c->vopt.early_vote == 2 || (c->n >= kEarlyMinGaussians && c->run.total_views >= kEarlyMinViews));
 }
-static bool early_possible(const Ctx* c) { return early_common(c) && c->total_views <= kMaxBatch && !c->wide; }
+static bool early_possible(const Ctx* c) { return early_common(c) && c->run.total_views <= kMaxBatch && !c->run.wide; }
 // more than 255 announced views: the batches of labels_batched() (cut by the ANNOUNCED number of views) start their count
 // kernels on the second stream as soon as their views are staged; only the last batch, the totals and the tie walk are
 // left behind the last map
-static bool early_batched_possible(const Ctx* c) { return early_common(c) && c->total_views > kMaxBatch && c->opt_batched_counts; }
+static bool early_batched_possible(const Ctx* c) { return early_common(c) && c->run.total_views > kMaxBatch && c->vopt.batched_counts; }
 // The early batches: a short LAST batch (its count kernel is what stays behind the last map) after balanced ones of <= 255
 // views.  Any cut of the view order into consecutive batches gives the same labels (the earliest batch wins a tie).
 static int early_batch_count(int total) {
@@ -1327,31 +1293,27 @@ static void early_batch_bounds(int total, int s, int& lo, int& hi) {
 // dm: the projection variant these views allow.
 static int early_upload(Ctx* c, int lo, int hi, int block, int blocks, hipStream_t st, int* dm) {
     const size_t vbytes = sizeof(ViewDesc) * kEarlyPitch, cbytes = sizeof(double) * kEarlyCullDoubles;
-    if (!c->h_early) {
-        GSX_HIP(c, hipHostMalloc(&c->h_early, vbytes + cbytes, hipHostMallocDefault));
-        c->h_early_cap = vbytes + cbytes;
-    }
+    GSX_HIP(c, c->early.h_stage.ensure(vbytes + cbytes));
     // sized for the whole run at its first stage: a later stage must find the earlier ones' descriptors and planes in place
-    GSX_HIP(c, c->e_views.ensure(sizeof(ViewDesc) * (size_t)std::max(kEarlyPitch, c->total_views)));
-    GSX_HIP(c, c->e_cull.ensure(cbytes * (size_t)std::max(2, blocks)));
-    if (!c->early_up_ev) GSX_HIP(c, hipEventCreateWithFlags(&c->early_up_ev, hipEventDisableTiming));
-    else GSX_HIP(c, hipEventSynchronize(c->early_up_ev));  // the previous upload has left the staging buffer
-    ViewDesc* hv = static_cast<ViewDesc*>(c->h_early);  // the stage's views, at most kEarlyPitch
-    double* planes = reinterpret_cast<double*>(static_cast<char*>(c->h_early) + vbytes);
+    GSX_HIP(c, c->early.e_views.ensure(sizeof(ViewDesc) * (size_t)std::max(kEarlyPitch, c->run.total_views)));
+    GSX_HIP(c, c->early.e_cull.ensure(cbytes * (size_t)std::max(2, blocks)));
+    GSX_HIP(c, c->early.up_ev.wait());  // the previous upload has left the staging buffer
+    ViewDesc* hv = c->early.h_stage.as<ViewDesc>();  // the stage's views, at most kEarlyPitch
+    double* planes = reinterpret_cast<double*>(c->early.h_stage.as<char>() + vbytes);
     std::memset(planes, 0, cbytes);
-    const ViewKinds kinds = stage_views(c, lo, hi, c->segpool.p, hv, planes, kEarlyPitch);  // (early_common: no imported pool)
+    const ViewKinds kinds = stage_views(c, lo, hi, c->run.segpool.p, hv, planes, kEarlyPitch);  // (early_common: no imported pool)
     *dm = flat_div_mode(c, kinds.simple, kinds.coarse);
-    if (hi > lo) GSX_HIP(c, hipMemcpyAsync(c->e_views.as<ViewDesc>() + lo, hv, sizeof(ViewDesc) * (size_t)(hi - lo), hipMemcpyHostToDevice, st));
-    GSX_HIP(c, hipMemcpyAsync(c->e_cull.as<double>() + (size_t)block * kEarlyCullDoubles, planes, cbytes, hipMemcpyHostToDevice, st));
-    GSX_HIP(c, hipEventRecord(c->early_up_ev, st));
+    if (hi > lo) GSX_HIP(c, hipMemcpyAsync(c->early.e_views.as<ViewDesc>() + lo, hv, sizeof(ViewDesc) * (size_t)(hi - lo), hipMemcpyHostToDevice, st));
+    GSX_HIP(c, hipMemcpyAsync(c->early.e_cull.as<double>() + (size_t)block * kEarlyCullDoubles, planes, cbytes, hipMemcpyHostToDevice, st));
+    GSX_HIP(c, c->early.up_ev.record(st));
     return GSX_OK;
 }
 
 static FusedParams early_params(Ctx* c, int lo, int hi, int block, int stride_bytes_per_bin) {
     FusedParams p = fused_params(c, stride_bytes_per_bin);
-    p.views = c->e_views.as<ViewDesc>() + lo;
+    p.views = c->early.e_views.as<ViewDesc>() + lo;
     p.nviews = hi - lo;
-    p.cull = c->opt_wave_cull ? c->e_cull.as<double>() + (size_t)block * kEarlyCullDoubles : nullptr;
+    p.cull = c->vopt.wave_cull ? c->early.e_cull.as<double>() + (size_t)block * kEarlyCullDoubles : nullptr;
     p.cull_pitch = kEarlyPitch;
     return p;
 }
@@ -1368,127 +1330,101 @@ int second_stream(Ctx* c) {
     return GSX_OK;
 }
 
-static int early_streams(Ctx* c) {
-    const int rc = second_stream(c);
-    if (rc) return rc;
-    if (!c->early_maps_ev) GSX_HIP(c, hipEventCreateWithFlags(&c->early_maps_ev, hipEventDisableTiming));
-    if (!c->early_done_ev) GSX_HIP(c, hipEventCreateWithFlags(&c->early_done_ev, hipEventDisableTiming));
-    return GSX_OK;
-}
-
 // pool_reserve (handover.hip) is about to free the pool an early stage may still be reading: wait for it, and vote this run in one
 // piece
 int early_pool_moves(Ctx* c) {
-    if (c->early_state == 1 || c->early_batches > 0) {
+    if (c->early.phase == EarlyPhase::Started || c->early.batches > 0) {
         GSX_HIP(c, hipStreamSynchronize(c->stream2));
-        c->early_inflight = false;
-        c->early_state = -1;
-        c->early_batches = 0;
+        c->early.inflight = false;
+        c->early.drop();
     }
     return GSX_OK;
 }
 
-static void early_release(Ctx* c) {  // the second stream and everything the early stages allocate
-    if (c->stream2) {
-        (void)hipStreamSynchronize(c->stream2);
-        (void)hipStreamDestroy(c->stream2);
-        c->stream2 = nullptr;
-    }
-    for (hipEvent_t* e : {&c->early_maps_ev, &c->early_done_ev, &c->early_up_ev}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
-    if (c->h_early) (void)hipHostFree(c->h_early);
-    c->h_early = nullptr;
-    c->h_early_cap = 0;
-    for (DevBuf* b : {&c->ecnt, &c->efv, &c->erec, &c->e_views, &c->e_cull}) b->release();
-    c->early_state = -1;
-}
-
 static int early_batch_stage(Ctx* c) {
-    const int nv = (int)c->views.size();
-    const int S = early_batch_count(c->total_views);
-    const int s = c->early_batches;
+    const int nv = (int)c->run.views.size();
+    const int S = early_batch_count(c->run.total_views);
+    const int s = c->early.batches;
     if (s >= S - 1) return GSX_OK;  // the last batch ends with the last view: vote_finalize launches it
     int lo, hi;
-    early_batch_bounds(c->total_views, s, lo, hi);
+    early_batch_bounds(c->run.total_views, s, lo, hi);
     if (nv != hi) return GSX_OK;
     int rc = vote_flush_pending(c);
     if (rc) return rc;
-    if ((rc = early_streams(c))) return rc;
-    const size_t plane = (size_t)c->bins * (size_t)c->n_pad;
-    GSX_HIP(c, c->bcnt.ensure(plane * S));  // all batches at the first stage: a later one must find the earlier planes in place
+    if ((rc = second_stream(c))) return rc;
+    const size_t plane = (size_t)c->run.bins * (size_t)c->run.n_pad;
+    GSX_HIP(c, c->planes.bcnt.ensure(plane * S));  // all batches at the first stage: a later one must find the earlier planes in place
     if ((rc = ensure_tally(c))) return rc;
-    GSX_HIP(c, hipEventRecord(c->early_maps_ev, c->stream));
-    GSX_HIP(c, hipStreamWaitEvent(c->stream2, c->early_maps_ev, 0));
+    GSX_HIP(c, c->early.maps_ev.record(c->stream));
+    GSX_HIP(c, c->early.maps_ev.stream_wait(c->stream2));
     int dm = kDivFlat;
     if ((rc = early_upload(c, lo, hi, s, S, c->stream2, &dm))) return rc;
     const FusedParams p = early_params(c, lo, hi, s, 1);
     auto k = with_div<true>(dm, [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
-    if ((rc = launch_walk(c, "vote_early_counts", c->stream2, k, c->n, p, c->bcnt.as<uint8_t>() + plane * s, (long long)c->n_pad))) return rc;
-    GSX_HIP(c, hipEventRecord(c->early_done_ev, c->stream2));
-    c->early_inflight = true;
-    c->early_batches = s + 1;
-    c->early_done = hi;
+    if ((rc = launch_walk(c, "vote_early_counts", c->stream2, k, c->n, p, c->planes.bcnt.as<uint8_t>() + plane * s, (long long)c->run.n_pad))) return rc;
+    GSX_HIP(c, c->early.done_ev.record(c->stream2));
+    c->early.inflight = true;
+    c->early.batches = s + 1;
+    c->early.done = hi;
     return GSX_OK;
 }
 
 static int early_vote_stage(Ctx* c) {
-    if (c->early_state == 0 && early_batched_possible(c)) return early_batch_stage(c);
-    if (c->early_state != 0 || !early_possible(c)) return GSX_OK;
-    const int nv = (int)c->views.size();
+    if (c->early.phase == EarlyPhase::Idle && early_batched_possible(c)) return early_batch_stage(c);
+    if (c->early.phase != EarlyPhase::Idle || !early_possible(c)) return GSX_OK;
+    const int nv = (int)c->run.views.size();
     int at;
-    if (c->opt_early_at > 0) {
-        at = std::max(1, (int)(((long long)c->total_views * c->opt_early_at + 999) / 1000));
+    if (c->vopt.early_at > 0) {
+        at = std::max(1, (int)(((long long)c->run.total_views * c->vopt.early_at + 999) / 1000));
         if (nv != at) return GSX_OK;
     } else {
         // The split that lets the stage finish just as the last map arrives: it walks a view in about kEarlyUsPerGaussianView * n
         // microseconds, the caller hands over a map every t_map (measured on this run's own calls) - so E / V = t_map / (t_map +
         // that).  Kept between one half and 88 % of the announced views; the stage starts at the first call past it.
         const auto now = std::chrono::steady_clock::now();
-        if (nv == 1) c->early_t0 = now;
-        if (nv < std::max(8, c->total_views / 4)) return GSX_OK;
-        const double t_map = std::chrono::duration<double, std::micro>(now - c->early_t0).count() / (double)(nv - 1);
-        const double t_view = (c->opt_early_replay ? kRecordUsPerGaussianView : kEarlyUsPerGaussianView) * (double)c->n;
-        const int lo = (c->total_views + 1) / 2, hi = (int)(((long long)c->total_views * 880) / 1000);
-        const int want = std::min(std::max((int)std::ceil(c->total_views * t_map / (t_map + t_view)), lo), std::max(lo, hi));
+        if (nv == 1) c->early.t0 = now;
+        if (nv < std::max(8, c->run.total_views / 4)) return GSX_OK;
+        const double t_map = std::chrono::duration<double, std::micro>(now - c->early.t0).count() / (double)(nv - 1);
+        const double t_view = (c->vopt.early_replay ? kRecordUsPerGaussianView : kEarlyUsPerGaussianView) * (double)c->n;
+        const int lo = (c->run.total_views + 1) / 2, hi = (int)(((long long)c->run.total_views * 880) / 1000);
+        const int want = std::min(std::max((int)std::ceil(c->run.total_views * t_map / (t_map + t_view)), lo), std::max(lo, hi));
         if (nv < want) return GSX_OK;
         at = nv;
     }
-    if (at >= c->total_views) return GSX_OK;
+    if (at >= c->run.total_views) return GSX_OK;
     int rc = vote_flush_pending(c);  // the maps of these views are on their way on c->stream
     if (rc) return rc;
-    if ((rc = early_streams(c))) return rc;
-    const size_t plane = (size_t)c->bins * (size_t)c->n_pad;
-    if (!c->opt_early_replay) {
-        GSX_HIP(c, c->ecnt.ensure(plane + kEarlySlack));
-        GSX_HIP(c, c->efv.ensure(plane + kEarlySlack));
+    if ((rc = second_stream(c))) return rc;
+    const size_t plane = (size_t)c->run.bins * (size_t)c->run.n_pad;
+    if (!c->vopt.early_replay) {
+        GSX_HIP(c, c->early.ecnt.ensure(plane + kEarlySlack));
+        GSX_HIP(c, c->early.efv.ensure(plane + kEarlySlack));
     }
-    GSX_HIP(c, c->erec.ensure((size_t)c->n_pad * (size_t)at));
+    GSX_HIP(c, c->early.erec.ensure((size_t)c->run.n_pad * (size_t)at));
     if ((rc = ensure_tally(c))) return rc;
-    GSX_HIP(c, hipEventRecord(c->early_maps_ev, c->stream));
-    GSX_HIP(c, hipStreamWaitEvent(c->stream2, c->early_maps_ev, 0));
+    GSX_HIP(c, c->early.maps_ev.record(c->stream));
+    GSX_HIP(c, c->early.maps_ev.stream_wait(c->stream2));
     int dm = kDivFlat;
     if ((rc = early_upload(c, 0, at, 0, 2, c->stream2, &dm))) return rc;
-    c->early_replayed = c->opt_early_replay != 0;  // (read once early_state says that a stage has started)
-    if (c->early_replayed) {  // record only (no LDS): the last stage replays it
+    c->early.replayed = c->vopt.early_replay != 0;  // (read once early.phase says that a stage has started)
+    if (c->early.replayed) {  // record only (no LDS): the last stage replays it
         const FusedParams p = early_params(c, 0, at, 0, 1);
         auto kr = with_div<true>(dm, [](auto d) { return vote_record_kernel<kUnroll, decltype(d)::value>; });
         ProfScope ps(c, "vote_early_record", c->stream2);
-        hipLaunchKernelGGL(kr, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream2, p, p.views, c->erec.as<uint8_t>());
+        hipLaunchKernelGGL(kr, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream2, p, p.views, c->early.erec.as<uint8_t>());
         GSX_HIP(c, hipGetLastError());
     } else {
         const FusedParams p = early_params(c, 0, at, 0, 2);
         auto k = with_div<true>(dm, [](auto d) { return vote_fused_planes_kernel<kUnroll, uint8_t, decltype(d)::value>; });
         // fresh planes, one "slab" per wave (sn = 64: the wave-major layout the last stage streams), global view codes 255 - v
-        if ((rc = launch_walk(c, "vote_early_planes", c->stream2, k, c->n, p, c->ecnt.as<uint8_t>(), c->efv.as<uint8_t>(), 64LL, 0, 1, 0,
-                              c->erec.as<uint8_t>())))
+        if ((rc = launch_walk(c, "vote_early_planes", c->stream2, k, c->n, p, c->early.ecnt.as<uint8_t>(), c->early.efv.as<uint8_t>(), 64LL, 0, 1, 0,
+                              c->early.erec.as<uint8_t>())))
             return rc;
     }
-    GSX_HIP(c, hipEventRecord(c->early_done_ev, c->stream2));
-    c->early_inflight = true;
-    c->early_done = at;
-    c->early_state = 1;
+    GSX_HIP(c, c->early.done_ev.record(c->stream2));
+    c->early.inflight = true;
+    c->early.done = at;
+    c->early.phase = EarlyPhase::Started;
     return GSX_OK;
 }
 
@@ -1497,25 +1433,25 @@ int vote_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int
     return rc ? rc : early_vote_stage(c);  // enough of the run staged: its first views are voted while the rest is handed over
 }
 
-// vote_finalize behind an early stage: the views [early_done, nv) on top of the early planes -> c->labels
+// vote_finalize behind an early stage: the views [early_done, nv) on top of the early planes -> c->planes.labels
 static int early_vote_finish(Ctx* c) {
-    const int nv = (int)c->views.size();
+    const int nv = (int)c->run.views.size();
     int rc = vote_flush_pending(c);
     if (rc) return rc;
     int dm = kDivFlat;
-    if ((rc = early_upload(c, c->early_done, nv, 1, 2, c->stream, &dm))) return rc;
-    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
-    if (c->early_replayed) {
-        FusedParams pr = early_params(c, c->early_done, nv, 1, 1);
+    if ((rc = early_upload(c, c->early.done, nv, 1, 2, c->stream, &dm))) return rc;
+    GSX_HIP(c, c->planes.labels.ensure(label_bytes(c)));
+    if (c->early.replayed) {
+        FusedParams pr = early_params(c, c->early.done, nv, 1, 1);
         auto kr = with_div<true>(dm, [](auto d) { return vote_fused_replay_kernel<kUnroll, decltype(d)::value>; });
         if ((rc = early_join(c))) return rc;
-        if ((c->opt_ablate >> 4) & 2) pr.nviews = 0;  // timing experiment (tools/early_probe.py)
-        return launch_walk(c, "vote_fused_replay", c->stream, kr, c->n, pr, c->erec.as<uint8_t>(), c->early_done, c->labels.as<int>());
+        if ((c->vopt.ablate >> 4) & 2) pr.nviews = 0;  // timing experiment (tools/early_probe.py)
+        return launch_walk(c, "vote_fused_replay", c->stream, kr, c->n, pr, c->early.erec.as<uint8_t>(), c->early.done, c->planes.labels.as<int>());
     }
-    FusedParams p = early_params(c, c->early_done, nv, 1, 1);
-    const size_t lds = (size_t)(kBlock / 64) * ((c->bins + 3) / 4) * 256;  // per wave: [bin][64] bytes, rows padded to a multiple of four
+    FusedParams p = early_params(c, c->early.done, nv, 1, 1);
+    const size_t lds = (size_t)(kBlock / 64) * ((c->run.bins + 3) / 4) * 256;  // per wave: [bin][64] bytes, rows padded to a multiple of four
     constexpr int kRegRows = 38;  // bins <= 152 (the 150 ADE20K classes + unlabelled): the first-view rows wait in registers
-    const bool regs = c->bins <= 4 * kRegRows;
+    const bool regs = c->run.bins <= 4 * kRegRows;
     auto k = with_div<true>(dm, [&](auto d) {
         constexpr int kDiv = decltype(d)::value;
         return regs ? vote_fused_final_kernel<kUnroll, kDiv, kRegRows> : vote_fused_final_kernel<kUnroll, kDiv, 0>;
@@ -1525,68 +1461,66 @@ static int early_vote_finish(Ctx* c) {
     // timing experiments (results invalid), option "ablate": 16 every wave reads the planes of wave 0; 32 no views behind the
     // early ones; 64 no pass over the first-view rows; 128 no look-up in the vote record; 256 labels stored in Morton order;
     // 512 no wave-level culling
-    const int ablate = (c->opt_ablate >> 4) & 63;
+    const int ablate = (c->vopt.ablate >> 4) & 63;
     if (ablate & 2) p.nviews = 0;
     ProfScope ps(c, "vote_fused_final");
-    hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->ecnt.as<uint8_t>(), c->efv.as<uint8_t>(),
-                       c->erec.as<uint8_t>(), c->early_done, c->labels.as<int>(), ablate);
+    hipLaunchKernelGGL(k, dim3(grid_for(c->n)), dim3(kBlock), lds, c->stream, p, p.views, c->early.ecnt.as<uint8_t>(), c->early.efv.as<uint8_t>(),
+                       c->early.erec.as<uint8_t>(), c->early.done, c->planes.labels.as<int>(), ablate);
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;
 }
 
 // merge views [n_flushed, size) into the planes, kMaxBatch at a time
 int vote_flush(Ctx* c) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_flush before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_flush before vote_begin");
     GSX_HIP(c, hipSetDevice(c->device));
     int rc = early_join(c);
     if (rc) return rc;
     if ((rc = sync_views(c))) return rc;
     if ((rc = ensure_planes(c))) return rc;
-    const int nv = (int)c->views.size();
-    if (c->n <= 0 || c->n_flushed >= nv) {
-        c->n_flushed = nv;
+    const int nv = (int)c->run.views.size();
+    if (c->n <= 0 || c->run.n_flushed >= nv) {
+        c->run.n_flushed = nv;
         return clear_stale_planes(c);  // nothing will overwrite them
     }
     const FusedParams all = fused_params(c, 2);
-    while (c->n_flushed < nv) {
-        const int batch = std::min(kMaxBatch, nv - c->n_flushed);
+    while (c->run.n_flushed < nv) {
+        const int batch = std::min(kMaxBatch, nv - c->run.n_flushed);
         FusedParams p = all;
-        p.views = all.views + c->n_flushed;
+        p.views = all.views + c->run.n_flushed;
         p.nviews = batch;
-        if (p.cull) p.cull = all.cull + c->n_flushed;
-        const int view_base = c->first_view + c->n_flushed;
-        const int fresh = (c->planes_zero || c->planes_stale) ? 1 : 0;
+        if (p.cull) p.cull = all.cull + c->run.n_flushed;
+        const int view_base = c->run.first_view + c->run.n_flushed;
+        const int fresh = (c->planes.state == PlaneState::Zero || c->planes.state == PlaneState::Stale) ? 1 : 0;
         auto planes = [&](auto t) {  // PT = the planes' element: u16 only when `wide` (then never local codes, vote_begin)
             using PT = decltype(t);
             auto k = with_div(div_mode(c), [](auto d) { return vote_fused_planes_kernel<kUnroll, PT, decltype(d)::value>; });
-            return launch_walk(c, "vote_fused_planes", c->stream, k, c->n, p, c->cnt.as<PT>(), c->fv.as<PT>(), (long long)c->sn, view_base,
-                               fresh, c->local_codes ? 1 : 0, (uint8_t*)nullptr);
+            return launch_walk(c, "vote_fused_planes", c->stream, k, c->n, p, c->planes.cnt.as<PT>(), c->planes.fv.as<PT>(), (long long)c->run.sn, view_base,
+                               fresh, c->run.local_codes ? 1 : 0, (uint8_t*)nullptr);
         };
-        if ((rc = c->wide ? planes(uint16_t{}) : planes(uint8_t{}))) return rc;
-        c->planes_zero = false;
-        c->planes_stale = false;
-        c->planes_valid = true;
-        c->n_flushed += batch;
+        if ((rc = c->run.wide ? planes(uint16_t{}) : planes(uint8_t{}))) return rc;
+        c->planes.state = PlaneState::Votes;
+        c->run.n_flushed += batch;
     }
     return GSX_OK;
 }
 
 int vote_tiebreak_keys(Ctx* c) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_tiebreak_keys before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_tiebreak_keys before vote_begin");
     GSX_HIP(c, hipSetDevice(c->device));
     int rc = ensure_planes(c);
     if (rc) return rc;
     if ((rc = clear_stale_planes(c))) return rc;
-    GSX_HIP(c, c->keys.ensure(label_bytes(c)));
-    GSX_HIP(c, hipMemsetAsync(c->keys.p, 0, sizeof(int) * (size_t)c->n_pad, c->stream));
+    GSX_HIP(c, c->planes.keys.ensure(label_bytes(c)));
+    GSX_HIP(c, hipMemsetAsync(c->planes.keys.p, 0, sizeof(int) * (size_t)c->run.n_pad, c->stream));
     if (c->n <= 0) return GSX_OK;
     ProfScope ps(c, "vote_keys");
     auto keys = [&](auto t) {
         using PT = decltype(t);
-        hipLaunchKernelGGL(vote_keys_kernel<PT>, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, c->cnt.as<PT>(), c->fv.as<PT>(),
-                           (long long)c->n, (long long)c->sn, c->bins, c->keys.as<int>());
+        hipLaunchKernelGGL(vote_keys_kernel<PT>, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, c->planes.cnt.as<PT>(), c->planes.fv.as<PT>(),
+                           (long long)c->n, (long long)c->run.sn, c->run.bins, c->planes.keys.as<int>());
     };
-    c->wide ? keys(uint16_t{}) : keys(uint8_t{});
+    c->run.wide ? keys(uint16_t{}) : keys(uint8_t{});
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;
 }
@@ -1596,7 +1530,7 @@ int vote_tiebreak_keys(Ctx* c) {
 // on the critical path of every run) into pinned memory, in kLabelChunks pieces; the worker threads widen piece i into
 // the caller's (pageable) int32 array while piece i+1 is still on the link.  A map that gsx_vote_view_device packed
 // with a label out of range fails the call here.
-static constexpr int kBadLabelWord = -2;  // errflag value: c->labels held something that is not a label (never a view index)
+static constexpr int kBadLabelWord = -2;  // errflag value: c->planes.labels held something that is not a label (never a view index)
 __global__ __launch_bounds__(kBlock) void labels_narrow_kernel(const int* __restrict__ labels, long long n, uint8_t* __restrict__ out,
                                                                int* __restrict__ errflag) {
     const long long i4 = ((long long)blockIdx.x * kBlock + threadIdx.x) * 4;
@@ -1617,91 +1551,70 @@ __global__ __launch_bounds__(kBlock) void labels_narrow_kernel(const int* __rest
 }
 
 static int labels_to_host(Ctx* c, int32_t* labels_out) {
-    c->labels_valid = true;
+    c->run.labels_valid = true;
     const size_t n = labels_out && c->n > 0 ? (size_t)c->n : 0;
-    const size_t esz = c->opt_labels_u8 ? 1 : sizeof(int);  // bytes per label on the link ("labels_u8" = 0: the A/B of DESIGN.md)
+    const size_t esz = c->vopt.labels_u8 ? 1 : sizeof(int);  // bytes per label on the link ("labels_u8" = 0: the A/B of DESIGN.md)
     const size_t nbytes = n * esz;
     const size_t flag_off = (nbytes + 63) / 64 * 64;
     const size_t need = flag_off + 64;
-    if (c->h_labels_cap < need) {
-        if (c->h_labels) GSX_HIP(c, hipHostFree(c->h_labels));
-        c->h_labels = nullptr;
-        c->h_labels_cap = 0;
-        GSX_HIP(c, hipHostMalloc(&c->h_labels, need + need / 8, hipHostMallocDefault));
-        c->h_labels_cap = need + need / 8;
-    }
-    char* land = static_cast<char*>(c->h_labels);
+    GSX_HIP(c, c->hstage.labels.ensure(need, need + need / 8));
+    char* land = c->hstage.labels.as<char>();
     int* flag = reinterpret_cast<int*>(land + flag_off);
-    const char* src = c->labels.as<char>();
-    if (n && c->opt_labels_u8) {
-        GSX_HIP(c, c->labels8.ensure(align256(n)));
+    const char* src = c->planes.labels.as<char>();
+    if (n && c->vopt.labels_u8) {
+        GSX_HIP(c, c->planes.labels8.ensure(align256(n)));
         ProfScope ps(c, "labels_narrow");
-        hipLaunchKernelGGL(labels_narrow_kernel, dim3(grid_for((long long)(n + 3) / 4)), dim3(kBlock), 0, c->stream, c->labels.as<int>(),
-                           (long long)n, c->labels8.as<uint8_t>(), c->errflag.as<int>());
+        hipLaunchKernelGGL(labels_narrow_kernel, dim3(grid_for((long long)(n + 3) / 4)), dim3(kBlock), 0, c->stream, c->planes.labels.as<int>(),
+                           (long long)n, c->planes.labels8.as<uint8_t>(), c->run.errflag.as<int>());
         GSX_HIP(c, hipGetLastError());
-        src = c->labels8.as<char>();
+        src = c->planes.labels8.as<char>();
     }
-    GSX_HIP(c, hipMemcpyAsync(flag, c->errflag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipMemcpyAsync(flag, c->run.errflag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (n) {
         const int chunks = nbytes >= ((size_t)1 << 20) ? kLabelChunks : 1;
         const size_t per = ((n + chunks - 1) / chunks + 4095) / 4096 * 4096;  // labels per chunk
         for (int k = 0; k < chunks; ++k) {
             const size_t lo = std::min(n, per * k), hi = std::min(n, per * (k + 1));
             if (lo < hi) GSX_HIP(c, hipMemcpyAsync(land + lo * esz, src + lo * esz, (hi - lo) * esz, hipMemcpyDeviceToHost, c->stream));
-            if (!c->h_ev[k]) GSX_HIP(c, hipEventCreateWithFlags(&c->h_ev[k], hipEventDisableTiming));
-            GSX_HIP(c, hipEventRecord(c->h_ev[k], c->stream));
+            GSX_HIP(c, c->hstage.labels_ev[k].record(c->stream));
         }
         Workers* w = host_workers(c);
         for (int k = 0; k < chunks; ++k) {
             const size_t lo = std::min(n, per * k), hi = std::min(n, per * (k + 1));
-            GSX_HIP(c, hipEventSynchronize(c->h_ev[k]));
+            GSX_HIP(c, c->hstage.labels_ev[k].wait());
             if (lo >= hi) continue;
-            if (c->opt_labels_u8) host_widen_labels(w, labels_out + lo, reinterpret_cast<const uint8_t*>(land) + lo, hi - lo);
+            if (c->vopt.labels_u8) host_widen_labels(w, labels_out + lo, reinterpret_cast<const uint8_t*>(land) + lo, hi - lo);
             else host_copy(w, labels_out + lo, land + lo * esz, (hi - lo) * esz);
         }
     }
     GSX_HIP(c, hipStreamSynchronize(c->stream));
     if (*flag != kNoBadView) {
         const int view = *flag;
-        GSX_HIP(c, hipMemsetAsync(c->errflag.p, 0x7f, sizeof(int), c->stream));
+        GSX_HIP(c, hipMemsetAsync(c->run.errflag.p, 0x7f, sizeof(int), c->stream));
         if (view == kBadLabelWord)
             return fail(c, GSX_E_STATE, "the label buffer holds a value outside [-1, 254] (a corrupt exchange buffer?)");
         return fail(c, GSX_E_RANGE, "the segmentation map of view %d (gsx_vote_view_device) holds a label outside [-1, %d]", view,
-                    c->n_classes - 1);
+                    c->run.n_classes - 1);
     }
     return GSX_OK;
 }
 
-static void staging_release(Ctx* c) {  // the pinned landing zone of the labels and the descriptor staging of sync_views
-    for (hipEvent_t& e : c->h_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    if (c->h_labels) (void)hipHostFree(c->h_labels);
-    c->h_labels = nullptr;
-    c->h_labels_cap = 0;
-    if (c->h_views_ev) (void)hipEventDestroy(c->h_views_ev);
-    c->h_views_ev = nullptr;
-    if (c->h_views) (void)hipHostFree(c->h_views);
-    c->h_views = nullptr;
-    c->h_views_cap = 0;
-}
-
-void vote_release_host(Ctx* c) {  // gsx_destroy
-    handover_release(c);
-    staging_release(c);
-    early_release(c);
+void vote_release_host(Ctx* c) {  // gsx_destroy: the second stream goes before the first
+    if (!c->stream2) return;
+    (void)hipStreamSynchronize(c->stream2);
+    (void)hipStreamDestroy(c->stream2);
+    c->stream2 = nullptr;
 }
 
 int vote_labels_from_keys(Ctx* c, int32_t* labels_out) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_labels_from_keys before vote_begin");
-    if (c->keys.cap < sizeof(int) * (size_t)c->n_pad) return fail(c, GSX_E_STATE, "vote_labels_from_keys before vote_tiebreak_keys");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_labels_from_keys before vote_begin");
+    if (c->planes.keys.cap < sizeof(int) * (size_t)c->run.n_pad) return fail(c, GSX_E_STATE, "vote_labels_from_keys before vote_tiebreak_keys");
     GSX_HIP(c, hipSetDevice(c->device));
-    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
+    GSX_HIP(c, c->planes.labels.ensure(label_bytes(c)));
     if (c->n > 0) {
         ProfScope ps(c, "vote_labels");
-        hipLaunchKernelGGL(vote_labels_kernel, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, c->keys.as<int>(),
-                           (long long)c->n, c->sorted ? c->perm.as<uint32_t>() : nullptr, c->labels.as<int>());
+        hipLaunchKernelGGL(vote_labels_kernel, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, c->planes.keys.as<int>(),
+                           (long long)c->n, c->sorted ? c->perm.as<uint32_t>() : nullptr, c->planes.labels.as<int>());
         GSX_HIP(c, hipGetLastError());
     }
     return labels_to_host(c, labels_out);
@@ -1730,7 +1643,7 @@ static int labels_one_batch(Ctx* c, const VoteRange& r, const uint32_t* perm, in
     p.perm = perm ? perm + r.i0 : nullptr;
     // kernel variants: unroll U in {2,4,8} x division mode
     using K = void (*)(FusedParams, const ViewDesc*, int*);
-    const int ui = c->opt_vote_unroll == 2 ? 0 : c->opt_vote_unroll == 4 ? 1 : 2;
+    const int ui = c->vopt.vote_unroll == 2 ? 0 : c->vopt.vote_unroll == 4 ? 1 : 2;
     K k = with_div(div_mode(c), [ui](auto d) {
         constexpr int kDiv = decltype(d)::value;
         static const K by_unroll[3] = {vote_fused_labels_kernel<2, kDiv>, vote_fused_labels_kernel<4, kDiv>, vote_fused_labels_kernel<8, kDiv>};
@@ -1746,19 +1659,19 @@ static int labels_one_batch(Ctx* c, const VoteRange& r, const uint32_t* perm, in
 // tied Gaussians and vote_tie_resolve_kernel takes the earliest batch that voted a candidate = the earliest view,
 // which is the reference's first-inserted rule (dls.py:303).  Replaces the 16-bit count + first-view planes of
 // vote_flush() for this case (1.9 ms per 200 views at C3 sizes against 1.1 ms).
-// Leaves the range's labels in Morton order at c->keys[0 .. r.n).
+// Leaves the range's labels in Morton order at c->planes.keys[0 .. r.n).
 static int labels_batched(Ctx* c, const VoteRange& r) {
-    const int nv = (int)c->views.size();
+    const int nv = (int)c->run.views.size();
     // batches whose count kernels already ran on the second stream while the run's later maps were handed over (early_batch_stage:
     // same batches - the run brought exactly the announced views -, same planes, the whole scene)
-    const bool early = c->early_batches > 0 && c->early_state == 0 && early_batched_possible(c) && nv == c->total_views && r.i0 == 0 &&
+    const bool early = c->early.batches > 0 && c->early.phase == EarlyPhase::Idle && early_batched_possible(c) && nv == c->run.total_views && r.i0 == 0 &&
                        r.n == c->n;
     const int S = early ? early_batch_count(nv) : (nv + kMaxBatch - 1) / kMaxBatch;
     const long long npad = (r.n + 255) / 256 * 256;
-    const size_t plane = (size_t)c->bins * (size_t)npad;
-    GSX_HIP(c, c->bcnt.ensure(plane * S));
-    GSX_HIP(c, c->cand.ensure(sizeof(uint32_t) * kCandWords * (size_t)npad));
-    GSX_HIP(c, c->bcodes.ensure(sizeof(uint16_t) * (size_t)npad * S));
+    const size_t plane = (size_t)c->run.bins * (size_t)npad;
+    GSX_HIP(c, c->planes.bcnt.ensure(plane * S));
+    GSX_HIP(c, c->planes.cand.ensure(sizeof(uint32_t) * kCandWords * (size_t)npad));
+    GSX_HIP(c, c->planes.bcodes.ensure(sizeof(uint16_t) * (size_t)npad * S));
     if (r.n <= 0) return GSX_OK;
     auto k = with_div(div_mode(c), [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
     const FusedParams base = range_params(c, r, 1);
@@ -1770,69 +1683,69 @@ static int labels_batched(Ctx* c, const VoteRange& r) {
         p.nviews = hi - lo;
         if (p.cull) p.cull = base.cull + lo;
     };
-    const int s0 = early ? c->early_batches : 0;
+    const int s0 = early ? c->early.batches : 0;
     for (int s = s0; s < S; ++s) {
         FusedParams p;
         batch(s, p);
-        const int rc = launch_walk(c, "vote_fused_counts", c->stream, k, r.n, p, c->bcnt.as<uint8_t>() + plane * s, npad);
+        const int rc = launch_walk(c, "vote_fused_counts", c->stream, k, r.n, p, c->planes.bcnt.as<uint8_t>() + plane * s, npad);
         if (rc) return rc;
     }
     {
         ProfScope ps(c, "vote_slab_totals");
-        hipLaunchKernelGGL(vote_slab_totals_kernel, dim3(grid_for(npad / 4)), dim3(kBlock), 0, c->stream, c->bcnt.as<uint8_t>(), S,
-                           c->bins, npad, c->keys.as<int>(), c->cand.as<uint32_t>());
+        hipLaunchKernelGGL(vote_slab_totals_kernel, dim3(grid_for(npad / 4)), dim3(kBlock), 0, c->stream, c->planes.bcnt.as<uint8_t>(), S,
+                           c->run.bins, npad, c->planes.keys.as<int>(), c->planes.cand.as<uint32_t>());
     }
     for (int s = 0; s < S; ++s) {
         FusedParams p;
         batch(s, p);
         ProfScope ps(c, "vote_tie");
-        hipLaunchKernelGGL(vote_tie_kernel, dim3(grid_for(r.n)), dim3(kBlock), 0, c->stream, p, p.views, c->cand.as<uint32_t>(), npad,
-                           c->bcodes.as<uint16_t>() + (size_t)npad * s, c->bcodes.as<uint16_t>(), s);
+        hipLaunchKernelGGL(vote_tie_kernel, dim3(grid_for(r.n)), dim3(kBlock), 0, c->stream, p, p.views, c->planes.cand.as<uint32_t>(), npad,
+                           c->planes.bcodes.as<uint16_t>() + (size_t)npad * s, c->planes.bcodes.as<uint16_t>(), s);
     }
     {
         ProfScope ps(c, "vote_tie_resolve");
-        hipLaunchKernelGGL(vote_tie_resolve_kernel, dim3(grid_for(npad)), dim3(kBlock), 0, c->stream, c->bcodes.as<uint16_t>(), S, npad,
-                           c->keys.as<int>());
+        hipLaunchKernelGGL(vote_tie_resolve_kernel, dim3(grid_for(npad)), dim3(kBlock), 0, c->stream, c->planes.bcodes.as<uint16_t>(), S, npad,
+                           c->planes.keys.as<int>());
     }
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;
 }
 
 // labels of a range of Gaussians over ALL staged views, whatever their number.  to_sorted: leave them in Morton order
-// at c->keys[0 .. r.n) (protocol v4); otherwise write c->labels in the caller's order (needs r = the whole scene).
+// at c->planes.keys[0 .. r.n) (protocol v4); otherwise write c->planes.labels in the caller's order (needs r = the whole scene).
 static int labels_for_range(Ctx* c, const VoteRange& r, bool to_sorted) {
     // early or not: an early batch may still be writing its plane of bcnt on the second stream (a run that stopped short of the
     // announced views, a rewind) - the buffers are (re)sized and the kernels launched behind it
     int rc = early_join(c);
     if (rc) return rc;
     if ((rc = sync_views(c))) return rc;
-    GSX_HIP(c, c->keys.ensure(label_bytes(c)));
-    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
+    GSX_HIP(c, c->planes.keys.ensure(label_bytes(c)));
+    GSX_HIP(c, c->planes.labels.ensure(label_bytes(c)));
     const uint32_t* perm = c->sorted ? c->perm.as<uint32_t>() : nullptr;
-    if ((int)c->views.size() <= kMaxBatch)
-        return labels_one_batch(c, r, to_sorted ? nullptr : perm, to_sorted ? c->keys.as<int>() : c->labels.as<int>());
+    if ((int)c->run.views.size() <= kMaxBatch)
+        return labels_one_batch(c, r, to_sorted ? nullptr : perm, to_sorted ? c->planes.keys.as<int>() : c->planes.labels.as<int>());
     if ((rc = labels_batched(c, r))) return rc;
     if (!to_sorted && r.n > 0) {
         ProfScope ps(c, "vote_labels");
-        hipLaunchKernelGGL(unpermute_labels_kernel, dim3(grid_for(r.n)), dim3(kBlock), 0, c->stream, c->keys.as<int>(), r.n, perm,
-                           c->labels.as<int>());
+        hipLaunchKernelGGL(unpermute_labels_kernel, dim3(grid_for(r.n)), dim3(kBlock), 0, c->stream, c->planes.keys.as<int>(), r.n, perm,
+                           c->planes.labels.as<int>());
         GSX_HIP(c, hipGetLastError());
     }
     return GSX_OK;
 }
 
 int vote_finalize(Ctx* c, int32_t* labels_out) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_finalize before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_finalize before vote_begin");
     GSX_HIP(c, hipSetDevice(c->device));
-    const int nv = (int)c->views.size();
-    const bool batched_ok = !c->local_codes && c->opt_batched_counts;
-    if (c->early_state == 1 && early_possible(c) && nv >= c->early_done && nv <= kMaxBatch) {
+    const int nv = (int)c->run.views.size();
+    const bool batched_ok = !c->run.local_codes && c->vopt.batched_counts;
+    if (c->early.phase == EarlyPhase::Started && early_possible(c) && nv >= c->early.done && nv <= kMaxBatch) {
         // the first views were voted while the rest was handed over: only the views behind them are left
         int rc = early_vote_finish(c);
         if (rc) return rc;
         return labels_to_host(c, labels_out);
     }
-    if (c->n_flushed == 0 && (nv <= kMaxBatch || batched_ok)) {
+    if (c->run.n_flushed == 0 && (nv <= kMaxBatch || batched_ok)) {
         // nothing in the planes yet: labels come straight out of the fused kernel(s)
         int rc = labels_for_range(c, VoteRange{0, c->n}, false);
         if (rc) return rc;
@@ -1845,7 +1758,7 @@ int vote_finalize(Ctx* c, int32_t* labels_out) {
 }
 
 int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_slab_labels before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_slab_labels before vote_begin");
     if (slabs < 1 || slab < 0 || slab >= slabs) return fail(c, GSX_E_INVALID, "vote_slab_labels: slab %d of %d", slab, slabs);
     GSX_HIP(c, hipSetDevice(c->device));
     long long sn = ((c->n + slabs - 1) / slabs + 255) / 256 * 256;
@@ -1853,113 +1766,114 @@ int vote_slab_labels(Ctx* c, int slab, int slabs, int64_t* slab_size) {
     if (slab_size) *slab_size = sn;
     const long long i0 = std::min<long long>(c->n, sn * slab);
     const long long cnt = std::min<long long>(c->n - i0, sn);
-    if ((long long)sn > c->n_pad) {  // tiny scenes: the key buffer must hold one whole slab for the all-gather
-        GSX_HIP(c, c->keys.ensure(sizeof(int) * (size_t)sn));
+    if ((long long)sn > c->run.n_pad) {  // tiny scenes: the key buffer must hold one whole slab for the all-gather
+        GSX_HIP(c, c->planes.keys.ensure(sizeof(int) * (size_t)sn));
     }
     return labels_for_range(c, VoteRange{i0, cnt}, true);
 }
 
 // ---- exchange v3 host side ------------------------------------------------------------------------------------
 int vote_flush_counts(Ctx* c) {
-    if (!c->vote_begun || !c->local_codes) return fail(c, GSX_E_STATE, "vote_flush_counts needs vote_begin with the 'exchange_local' option");
+    if (!c->run.begun || !c->run.local_codes) return fail(c, GSX_E_STATE, "vote_flush_counts needs vote_begin with the 'exchange_local' option");
     GSX_HIP(c, hipSetDevice(c->device));
     int rc = sync_views(c);
     if (rc) return rc;
-    const size_t bytes = (size_t)c->bins * (size_t)c->n_pad;
+    const size_t bytes = (size_t)c->run.bins * (size_t)c->run.n_pad;
     // pad Gaussians stay zero as long as the plane keeps its layout: a context that comes back with another scene, bin count or
     // slab count (or whose buffer held vote_flush's planes in between) would otherwise show the earlier run's counters there
-    const bool same = c->counts_n == c->n && c->counts_npad == c->n_pad && c->counts_sn == c->sn && c->counts_bins == c->bins;
-    if (bytes > c->cnt.cap || !same) {
-        GSX_HIP(c, c->cnt.ensure(bytes));
-        GSX_HIP(c, hipMemsetAsync(c->cnt.p, 0, bytes, c->stream));
-        c->counts_n = c->n, c->counts_npad = c->n_pad, c->counts_sn = c->sn, c->counts_bins = c->bins;
+    const PlaneLayout layout{c->n, c->run.n_pad, c->run.sn, c->run.bins};
+    if (bytes > c->planes.cnt.cap || !(c->planes.counts == layout)) {
+        GSX_HIP(c, c->planes.cnt.ensure(bytes));
+        GSX_HIP(c, hipMemsetAsync(c->planes.cnt.p, 0, bytes, c->stream));
+        c->planes.counts = layout;
     }
     if (c->n > 0) {
         auto k = with_div(div_mode(c), [](auto d) { return vote_fused_counts_kernel<kUnroll, decltype(d)::value>; });
-        if ((rc = launch_walk(c, "vote_fused_counts", c->stream, k, c->n, fused_params(c, 1), c->cnt.as<uint8_t>(), (long long)c->sn))) return rc;
+        if ((rc = launch_walk(c, "vote_fused_counts", c->stream, k, c->n, fused_params(c, 1), c->planes.cnt.as<uint8_t>(), (long long)c->run.sn))) return rc;
     }
-    c->n_flushed = (int)c->views.size();
+    c->run.n_flushed = (int)c->run.views.size();
     return GSX_OK;
 }
 
 int vote_slab_totals(Ctx* c, const void* recv_cnt) {
-    if (!c->vote_begun || !c->local_codes) return fail(c, GSX_E_STATE, "vote_slab_totals needs the 'exchange_local' option");
+    if (!c->run.begun || !c->run.local_codes) return fail(c, GSX_E_STATE, "vote_slab_totals needs the 'exchange_local' option");
     if (!recv_cnt) return fail(c, GSX_E_INVALID, "vote_slab_totals: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
-    GSX_HIP(c, c->keys.ensure(sizeof(int) * (size_t)c->n_pad));
-    GSX_HIP(c, c->cand.ensure(sizeof(uint32_t) * kCandWords * (size_t)c->sn));
+    GSX_HIP(c, c->planes.keys.ensure(sizeof(int) * (size_t)c->run.n_pad));
+    GSX_HIP(c, c->planes.cand.ensure(sizeof(uint32_t) * kCandWords * (size_t)c->run.sn));
     ProfScope ps(c, "vote_slab_totals");
-    hipLaunchKernelGGL(vote_slab_totals_kernel, dim3(grid_for(c->sn / 4)), dim3(kBlock), 0, c->stream, (const uint8_t*)recv_cnt,
-                       c->slabs, c->bins, (long long)c->sn, c->keys.as<int>(), c->cand.as<uint32_t>());
+    hipLaunchKernelGGL(vote_slab_totals_kernel, dim3(grid_for(c->run.sn / 4)), dim3(kBlock), 0, c->stream, (const uint8_t*)recv_cnt,
+                       c->run.slabs, c->run.bins, (long long)c->run.sn, c->planes.keys.as<int>(), c->planes.cand.as<uint32_t>());
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;  // ordered by the ctx stream; nothing waits on the host
 }
 
 int vote_tie_codes(Ctx* c, const void* cand_all) {
-    if (!c->vote_begun || !c->local_codes) return fail(c, GSX_E_STATE, "vote_tie_codes needs the 'exchange_local' option");
+    if (!c->run.begun || !c->run.local_codes) return fail(c, GSX_E_STATE, "vote_tie_codes needs the 'exchange_local' option");
     if (!cand_all) return fail(c, GSX_E_INVALID, "vote_tie_codes: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
-    const size_t bytes = sizeof(uint16_t) * (size_t)c->n_pad;
-    if (bytes > c->codes.cap || c->codes_n != c->n || c->codes_npad != c->n_pad) {  // pad entries are zero: see vote_flush_counts
-        GSX_HIP(c, c->codes.ensure(bytes));
-        GSX_HIP(c, hipMemsetAsync(c->codes.p, 0, bytes, c->stream));
-        c->codes_n = c->n, c->codes_npad = c->n_pad;
+    const size_t bytes = sizeof(uint16_t) * (size_t)c->run.n_pad;
+    const PlaneLayout layout{c->n, c->run.n_pad};
+    if (bytes > c->planes.codes.cap || !(c->planes.tie_codes == layout)) {  // pad entries are zero: see vote_flush_counts
+        GSX_HIP(c, c->planes.codes.ensure(bytes));
+        GSX_HIP(c, hipMemsetAsync(c->planes.codes.p, 0, bytes, c->stream));
+        c->planes.tie_codes = layout;
     }
     if (c->n > 0) {
         FusedParams p = fused_params(c, 1);
         ProfScope ps(c, "vote_tie");
         hipLaunchKernelGGL(vote_tie_kernel, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, p, p.views,
-                           (const uint32_t*)cand_all, (long long)c->sn, c->codes.as<uint16_t>(), (const uint16_t*)nullptr, 0);
+                           (const uint32_t*)cand_all, (long long)c->run.sn, c->planes.codes.as<uint16_t>(), (const uint16_t*)nullptr, 0);
         GSX_HIP(c, hipGetLastError());
     }
     return GSX_OK;  // ordered by the ctx stream; nothing waits on the host
 }
 
 int vote_tie_resolve(Ctx* c, const void* recv_codes) {
-    if (!c->vote_begun || !c->local_codes) return fail(c, GSX_E_STATE, "vote_tie_resolve needs the 'exchange_local' option");
+    if (!c->run.begun || !c->run.local_codes) return fail(c, GSX_E_STATE, "vote_tie_resolve needs the 'exchange_local' option");
     if (!recv_codes) return fail(c, GSX_E_INVALID, "vote_tie_resolve: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
     ProfScope ps(c, "vote_tie_resolve");
-    hipLaunchKernelGGL(vote_tie_resolve_kernel, dim3(grid_for(c->sn)), dim3(kBlock), 0, c->stream, (const uint16_t*)recv_codes,
-                       c->slabs, (long long)c->sn, c->keys.as<int>());
+    hipLaunchKernelGGL(vote_tie_resolve_kernel, dim3(grid_for(c->run.sn)), dim3(kBlock), 0, c->stream, (const uint16_t*)recv_codes,
+                       c->run.slabs, (long long)c->run.sn, c->planes.keys.as<int>());
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;  // ordered by the ctx stream; nothing waits on the host
 }
 
 int vote_slab_reduce(Ctx* c, const void* recv_cnt, const void* recv_fv) {
-    if (!c->vote_begun || !c->local_codes) return fail(c, GSX_E_STATE, "vote_slab_reduce needs vote_begin with the 'exchange_local' option");
+    if (!c->run.begun || !c->run.local_codes) return fail(c, GSX_E_STATE, "vote_slab_reduce needs vote_begin with the 'exchange_local' option");
     if (!recv_cnt || !recv_fv) return fail(c, GSX_E_INVALID, "vote_slab_reduce: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
-    GSX_HIP(c, c->keys.ensure(sizeof(int) * (size_t)c->n_pad));
+    GSX_HIP(c, c->planes.keys.ensure(sizeof(int) * (size_t)c->run.n_pad));
     ProfScope ps(c, "vote_slab_reduce");
-    hipLaunchKernelGGL(vote_slab_reduce_kernel, dim3(grid_for(c->sn)), dim3(kBlock), 0, c->stream, (const uint8_t*)recv_cnt,
-                       (const uint8_t*)recv_fv, c->slabs, c->bins, (long long)c->sn, c->keys.as<int>());
+    hipLaunchKernelGGL(vote_slab_reduce_kernel, dim3(grid_for(c->run.sn)), dim3(kBlock), 0, c->stream, (const uint8_t*)recv_cnt,
+                       (const uint8_t*)recv_fv, c->run.slabs, c->run.bins, (long long)c->run.sn, c->planes.keys.as<int>());
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;  // ordered by the ctx stream; nothing waits on the host
 }
 
 int vote_labels_from_sorted(Ctx* c, const void* sorted_labels_dev, int32_t* labels_out) {
-    if (!c->vote_begun) return fail(c, GSX_E_STATE, "vote_labels_from_sorted before vote_begin");
+    if (!c->run.begun) return fail(c, GSX_E_STATE, "vote_labels_from_sorted before vote_begin");
     if (!sorted_labels_dev) return fail(c, GSX_E_INVALID, "vote_labels_from_sorted: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
-    GSX_HIP(c, c->labels.ensure(label_bytes(c)));
+    GSX_HIP(c, c->planes.labels.ensure(label_bytes(c)));
     if (c->n > 0) {
         ProfScope ps(c, "vote_labels");
         hipLaunchKernelGGL(unpermute_labels_kernel, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream,
                            (const int*)sorted_labels_dev, (long long)c->n, c->sorted ? c->perm.as<uint32_t>() : nullptr,
-                           c->labels.as<int>());
+                           c->planes.labels.as<int>());
         GSX_HIP(c, hipGetLastError());
     }
     return labels_to_host(c, labels_out);
 }
 
 int vote_debug_planes(Ctx* c, uint16_t* counts_out, uint16_t* first_out) {
-    if (!c->vote_begun || !(c->planes_valid || c->planes_zero || c->planes_stale)) return fail(c, GSX_E_STATE, "vote_debug_planes: no planes");
+    if (!c->run.begun || !c->planes.holds()) return fail(c, GSX_E_STATE, "vote_debug_planes: no planes");
     if (const int rc = clear_stale_planes(c)) return rc;
     if (!counts_out || !first_out) return fail(c, GSX_E_INVALID, "vote_debug_planes: NULL argument");
     GSX_HIP(c, hipSetDevice(c->device));
-    const size_t esz = c->wide ? 2 : 1;
-    const size_t elems = (size_t)c->bins * (size_t)c->n_pad;
+    const size_t esz = c->run.wide ? 2 : 1;
+    const size_t elems = (size_t)c->run.bins * (size_t)c->run.n_pad;
     std::vector<uint8_t> tmp(elems * esz);
     std::vector<uint32_t> perm;
     if (c->sorted && c->n > 0) {
@@ -1967,14 +1881,14 @@ int vote_debug_planes(Ctx* c, uint16_t* counts_out, uint16_t* first_out) {
         GSX_HIP(c, hipMemcpy(perm.data(), c->perm.p, sizeof(uint32_t) * (size_t)c->n, hipMemcpyDeviceToHost));
     }
     for (int which = 0; which < 2; ++which) {
-        GSX_HIP(c, hipMemcpyAsync(tmp.data(), which ? c->fv.p : c->cnt.p, elems * esz, hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(c, hipMemcpyAsync(tmp.data(), which ? c->planes.fv.p : c->planes.cnt.p, elems * esz, hipMemcpyDeviceToHost, c->stream));
         GSX_HIP(c, hipStreamSynchronize(c->stream));
         uint16_t* out = which ? first_out : counts_out;
-        for (int b = 0; b < c->bins; ++b)
+        for (int b = 0; b < c->run.bins; ++b)
             for (int64_t i = 0; i < c->n; ++i) {
-                const size_t slab = (size_t)i / (size_t)c->sn;
-                const size_t at = (slab * c->bins + b) * (size_t)c->sn + ((size_t)i - slab * (size_t)c->sn);
-                out[(size_t)b * c->n + (perm.empty() ? (size_t)i : (size_t)perm[i])] = c->wide ? reinterpret_cast<uint16_t*>(tmp.data())[at] : tmp[at];
+                const size_t slab = (size_t)i / (size_t)c->run.sn;
+                const size_t at = (slab * c->run.bins + b) * (size_t)c->run.sn + ((size_t)i - slab * (size_t)c->run.sn);
+                out[(size_t)b * c->n + (perm.empty() ? (size_t)i : (size_t)perm[i])] = c->run.wide ? reinterpret_cast<uint16_t*>(tmp.data())[at] : tmp[at];
             }
     }
     return GSX_OK;
