@@ -145,6 +145,17 @@ _SIGS = {
     "gsx_lift_finalize": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "gsx_lift_table": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gsx_debug_lift_constants": (C.c_int, [C.c_void_p]),
+    "gsx_assoc_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
+    "gsx_assoc_view": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_void_p]),
+    "gsx_assoc_view_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p]),
+    "gsx_assoc_num_views": (C.c_int32, [C.c_void_p]),
+    "gsx_assoc_num_instances": (C.c_int32, [C.c_void_p]),
+    "gsx_assoc_num_dropped": (C.c_int64, [C.c_void_p]),
+    "gsx_assoc_ids": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gsx_assoc_table": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gsx_debug_assoc_constants": (C.c_int, [C.c_void_p]),
     "gsx_ply_open":(C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "gsx_ply_close": (None, [C.c_void_p]),
     "gsx_ply_num_vertices": (C.c_int64, [C.c_void_p]),

@@ -269,6 +269,7 @@ static int alloc_positions(Ctx* c, int64_t n) {
     c->run.n_pad = (n + 255) / 256 * 256;
     c->run.begun = false;  // planes are sized by n: a new scene needs a new vote_begin
     c->run.labels_valid = false;
+    gsx::assoc_end(c);  // an association run's ids belong to the Gaussians that go away here
     return GSX_OK;
 }
 
@@ -760,6 +761,48 @@ int gsx_lift_finalize(gsx_ctx* ctx, double min_weight, int32_t* labels_out, doub
 int gsx_lift_table(gsx_ctx* ctx, uint64_t* table_out) {
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::lift_table(c, table_out); });
+}
+// ---- instance association (assoc.hip) --------------------------------------------------------------
+int gsx_assoc_begin(gsx_ctx* ctx, int32_t max_segments, int32_t max_instances, double min_overlap, int32_t min_size) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::assoc_begin(c, max_segments, max_instances, min_overlap, min_size); });
+}
+int gsx_assoc_view(gsx_ctx* ctx, const gsx_camera* cam, const void* seg, int32_t seg_dtype, int32_t seg_w, int32_t seg_h, int32_t img_w,
+                   int32_t img_h, int32_t* remap_out, void* map_out_dev) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__,
+                      [&] { return gsx::assoc_view(c, cam, seg, seg_dtype, seg_w, seg_h, img_w, img_h, remap_out, map_out_dev, false); });
+}
+int gsx_assoc_view_device(gsx_ctx* ctx, const gsx_camera* cam, const void* seg_dev, int32_t seg_dtype, int32_t seg_w, int32_t seg_h,
+                          int32_t img_w, int32_t img_h, int32_t* remap_out, void* map_out_dev) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__,
+                      [&] { return gsx::assoc_view(c, cam, seg_dev, seg_dtype, seg_w, seg_h, img_w, img_h, remap_out, map_out_dev, true); });
+}
+int32_t gsx_assoc_num_views(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c && c->assoc.begun ? c->assoc.views : 0;
+}
+int32_t gsx_assoc_num_instances(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c && c->assoc.begun ? c->assoc.instances : 0;
+}
+int64_t gsx_assoc_num_dropped(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c && c->assoc.begun ? (int64_t)c->assoc.dropped : 0;
+}
+int gsx_assoc_ids(gsx_ctx* ctx, int32_t* gid_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::assoc_ids(c, gid_out); });
+}
+int gsx_assoc_table(gsx_ctx* ctx, uint32_t* table_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::assoc_table(c, table_out); });
+}
+int gsx_debug_assoc_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_assoc_constants: NULL argument");
+    gsx::assoc_constants(out);
+    return GSX_OK;
 }
 int gsx_debug_lift_constants(int32_t* out) {
     if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_lift_constants: NULL argument");

@@ -495,6 +495,24 @@ struct LiftState {
     unsigned long long atomics = 0;    // global atomics lift_kernel issued for the last view
 };
 
+// State of an association run (assoc.hip): gsx_assoc_begin .. the next gsx_upload_positions
+struct AssocState {
+    bool begun = false;
+    int max_segments = 0, max_instances = 0;  // S, M: the view's table is (S + 1) x (M + 1)
+    unsigned long long q = 0;          // ceil(min_overlap * 2^20)
+    long long min_size = 1;
+    int views = 0, instances = 0;      // views associated; G, the global instances so far
+    long long dropped = 0;             // segments that found no instance with G == M
+    DevBuf gid;                        // int32 [n], Morton order: the instance a Gaussian was first given, -1 = none yet
+    DevBuf bins;                       // u8 [n], Morton order: the view's bin (segment + 1) under the Gaussian, 255 = invisible
+    DevBuf table;                      // u32 [(S + 1) (M + 1)], then u32: the lowest flat map index out of range (~0: none)
+    DevBuf remap, view, raw, ids;      // int32 [S]; the ViewDesc; a host map on its way to the kernels; int32 [n] upload order
+    PinBuf up;                         // pinned, host -> device: ViewDesc (256 B) | remap int32 [S] (1024 B) | the raw host map
+    PinBuf down;                       // pinned, device -> host: the table and the range word behind it
+    Event up_ev, down_ev;              // recorded behind the copies out of `up` / into `down`
+    std::vector<uint32_t> last;        // the last view's table (gsx_assoc_table)
+};
+
 struct Ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -522,6 +540,7 @@ struct Ctx {
     RenderOpts ropt;
     RenderFrame frame;
     LiftState lift;
+    AssocState assoc;
     // gsx_render_views: further streams + per-frame buffers.  A twin is a whole Ctx because sort.hip, ProfScope and fail take
     // one; what it uses of it is stream, sort_hist, err, scene (aliases of this context's), ropt (a copy) and frame
     Ctx* twins[kMaxFrames - 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -725,6 +744,14 @@ int lift_finalize(Ctx* c, double min_weight, int32_t* labels_out, double* share_
 int lift_table(Ctx* c, uint64_t* table_out);
 void lift_end(Ctx* c);             // a new upload ends the run
 void lift_constants(int32_t out[8]);
+// assoc.hip: per-view segment ids -> global instance ids through the Gaussians
+int assoc_begin(Ctx* c, int max_segments, int max_instances, double min_overlap, int min_size);
+int assoc_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h,
+               int32_t* remap_out, void* map_out_dev, bool device);
+int assoc_ids(Ctx* c, int32_t* gid_out);
+int assoc_table(Ctx* c, uint32_t* table_out);
+void assoc_end(Ctx* c);            // a new upload ends the run
+void assoc_constants(int32_t out[8]);
 // iou.hip
 int iou_masks(Ctx* c, bool device, int n_masks, const void* const* masks, int mask_dtype, int n_gt, const void* const* gts, int gt_dtype,
               int h, int w, int64_t* inter_out, int64_t* area_masks_out, int64_t* area_gt_out, double* iou_out);

@@ -48,6 +48,7 @@ class Context:
         self._keep_alive = []   # device maps handed to vote_view until the ctx stream has consumed them
         self._ext = None        # the ctx stream as torch sees it (segmap_from_*)
         self._lift_bins, self._lift_keep = 1, []   # columns of the lift table; the device map a lift view may still read
+        self._assoc_shape = (2, 2)                 # the association table's shape, set by assoc_begin
 
     def close(self):
         if getattr(self, "h", None):
@@ -659,6 +660,71 @@ class Context:
         check(self._lib.gsx_lift_table(self.h, table.ctypes.data), self.h)
         return table
 
+    # -- instance association (include/gsx.h: gsx_assoc_*) ------------------------------------------
+    def assoc_begin(self, max_segments=254, max_instances=255, min_overlap=0.3, min_size=1):
+        """Start an association run on the Gaussians of upload_positions: maps with segment ids -1 .. max_segments - 1 per
+        view become maps of at most max_instances global instance ids."""
+        check(self._lib.gsx_assoc_begin(self.h, int(max_segments), int(max_instances), float(min_overlap), int(min_size)), self.h)
+        self._assoc_shape = (int(max_segments) + 1, int(max_instances) + 1)
+
+    def assoc_view(self, camera, seg_map, image_size=None, packed_u8=False):
+        """Associate one view's segment map (2-D; a numpy array on the host or a torch tensor on this GPU) with the run's
+        instances -> (remap int32 (max_segments,), map_dev): remap[s] is the global instance of segment s or -1, map_dev the
+        relabelled map as an int32 torch tensor on this GPU, a class map for vote_view / lift_view.  image_size as in
+        vote_view.  A value outside [-1, max_segments - 1] raises ValueError and leaves the run as it was."""
+        import torch
+        cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
+        device = type(seg_map) is not np.ndarray and hasattr(seg_map, "data_ptr")
+        if device:
+            seg = seg_map.contiguous()
+            if not seg.is_cuda:
+                raise ValueError("tensor seg maps must live on the GPU; pass numpy arrays for host maps")
+            dt = self._TORCH_DT.get(str(seg.dtype))
+            if dt is None:
+                seg, dt = seg.to(torch.int32), _lib.GSX_SEG_I32
+        else:
+            seg = np.asarray(seg_map)
+            dt = self._NP_DT.get(seg.dtype)
+            if dt is None:
+                seg, dt = seg.astype(np.int32), _lib.GSX_SEG_I32
+            seg = np.ascontiguousarray(seg)
+        if seg.ndim != 2:
+            raise ValueError("seg_map must be 2-D")
+        if packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
+            dt = _lib.GSX_SEG_U8
+        h, w = (int(v) for v in seg.shape)
+        iw, ih = (w, h) if image_size is None else (int(image_size[0]), int(image_size[1]))
+        remap = np.empty(self._assoc_shape[0] - 1, np.int32)
+        out = torch.empty((h, w), dtype=torch.int32, device=torch.device("cuda", self.device))
+        # the ctx stream behind torch's: the producer of a device map, and whoever last used the block `out` was given
+        self._seg_enter()
+        fn, ptr = (self._lib.gsx_assoc_view_device, seg.data_ptr()) if device else (self._lib.gsx_assoc_view, seg.ctypes.data)
+        check(fn(self.h, C.byref(cam), ptr, dt, w, h, iw, ih, remap.ctypes.data, out.data_ptr()), self.h)   # waits for its kernels
+        return remap, out
+
+    def assoc_num_views(self):
+        return self._lib.gsx_assoc_num_views(self.h)
+
+    def assoc_num_instances(self):
+        """G: the global instances opened so far"""
+        return self._lib.gsx_assoc_num_instances(self.h)
+
+    def assoc_num_dropped(self):
+        """segments that matched no instance when max_instances were already open"""
+        return self._lib.gsx_assoc_num_dropped(self.h)
+
+    def assoc_ids(self):
+        """-> int32 (n,), upload order: the instance each Gaussian was first given, -1 = none"""
+        gid = np.empty(int(self._lib.gsx_num_gaussians(self.h)), np.int32)
+        check(self._lib.gsx_assoc_ids(self.h, gid.ctypes.data), self.h)
+        return gid
+
+    def assoc_table(self):
+        """-> uint32 (max_segments + 1, max_instances + 1): the last view's table, row = segment + 1, column = instance + 1"""
+        table = np.empty(self._assoc_shape, np.uint32)
+        check(self._lib.gsx_assoc_table(self.h, table.ctypes.data), self.h)
+        return table
+
     def hit_test(self, camera, width, height, x, y):
         """performHitTesting (gs.js:361-395) -> (label or -999999, importance-order row or -1)."""
         cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
@@ -1051,6 +1117,25 @@ def assign_labels_from_maps(gaussians, cameras, segmaps, image_sizes=None, n_cla
             ctx.close()
 
 
+def assign_instances_from_maps(gaussians, cameras, segmaps, image_sizes=None, max_instances=255, min_overlap=0.3, min_size=1, ctx=None):
+    """Instance labels from per-view SEGMENT maps (ids numbered per image, -1 .. 253; Mask2Former's default map): every map is
+    first associated with the instances the Gaussians already carry (Context.assoc_view), then the relabelled maps are voted
+    like class maps.  Arguments as assign_labels_from_maps.  Returns (int32 labels (N,), number of instances)."""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.upload_positions(gaussians)
+        ctx.assoc_begin(254, max_instances, min_overlap, min_size)
+        ctx.vote_begin(max_instances, 0, max(1, len(cameras)))
+        for k, (cam, seg) in enumerate(zip(cameras, segmaps)):
+            size = None if image_sizes is None else image_sizes[k]
+            ctx.vote_view(cam, ctx.assoc_view(cam, seg, size)[1], size)
+        return ctx.vote_finalize(), ctx.assoc_num_instances()
+    finally:
+        if own:
+            ctx.close()
+
+
 def host_pack(seg_map, n_classes, tiled=True, coarse=True, threads=1, packed_u8=False):
     """Test hook, no GPU: the packed form gsx_vote_view stages for a host map -> (bytes u8, coarse_off or -1, bad)."""
     seg = np.asarray(seg_map)
@@ -1254,6 +1339,14 @@ def iou_constants():
     out = np.zeros(8, np.int32)
     check(_lib.lib().gsx_debug_iou_constants(out.ctypes.data))
     names = ("load_bytes", "word_bits", "wave_tile", "block_tile", "pair_tile", "pair_chunk_words", "table_lds_max", "table_run")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def assoc_constants():
+    """Test hook, host only: the units the association kernels are built on (gsx_debug_assoc_constants)."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_assoc_constants(out.ctypes.data))
+    names = ("one", "shift", "block", "max_segments", "max_instances", "lds_entries", "max_chunks")
     return dict(zip(names, (int(v) for v in out)))
 
 

@@ -29,6 +29,12 @@ the rasterizer's own blend (Context.lift_view): a splat takes the class of the p
 blend weight T * alpha * G, so a splat behind a wall no longer takes the wall's class.  Needs the PLY's splat attributes
 (scale_*, rot_*, opacity, f_dc_*); uses the VIEWER's camera convention, not the reference labeler's; single GPU.
 --lift_min_weight W (default 0): splats whose summed weight over all views stays below W are labelled -1.
+--associate [--assoc_min_overlap F] [--assoc_min_size N] [--assoc_max_instances M] (default off): the maps hold SEGMENT ids,
+numbered per image (Mask2Former's default map), and every map first goes through Context.assoc_view, which renames its
+segments to the global instances most of their Gaussians already carry (a segment matches when at least the fraction F of its
+Gaussians, default 0.3, carry the instance; segments of fewer than N Gaussians are left out; at most M instances, default 255).
+The relabelled map is voted or lifted with n_classes = M; the _segmap.npy side files stay the raw maps.  Single GPU: the
+association is ordered over the views.
 """
 import argparse
 import importlib
@@ -172,7 +178,8 @@ def _image_size(path):
 
 
 def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2former", segmap_dir=None, n_classes=None,
-                  ctx=None, mask2former_map="segments", labeler="vote", splats=None, lift_min_weight=0.0):
+                  ctx=None, mask2former_map="segments", labeler="vote", splats=None, lift_min_weight=0.0, associate=False,
+                  assoc_min_overlap=0.3, assoc_min_size=1, assoc_max_instances=255):
     """Majority-vote label per Gaussian (int32, -1 = never visible), bit-identical to the reference.
 
     Cameras whose `<img_name>.png` is missing from input_dir are skipped with a warning, as in the
@@ -180,7 +187,10 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
 
     labeler="lift": the maps are lifted through the rasterizer's blend instead (Context.lift_view, each at the map's own
     size with fx, fy scaled by map size / image size); splats = load_splat_attributes(plydata); a splat whose summed weight
-    stays below lift_min_weight gets -1."""
+    stays below lift_min_weight gets -1.
+
+    associate: the maps hold per-image segment ids; each goes through Context.assoc_view first and its relabelled device map,
+    a class map of assoc_max_instances instance ids, is what the labeler sees."""
     if labeler not in ("vote", "lift"):
         raise ValueError(f"Unknown labeler: {labeler}")
     lift = labeler == "lift"
@@ -189,6 +199,10 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
     if model_type not in N_CLASSES:
         raise ValueError(f"Unknown model type: {model_type}")
     n_classes = n_classes or N_CLASSES[model_type]
+    if associate:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("--associate runs on one GPU: the association is ordered over the views")
+        n_segments, n_classes = 254, int(assoc_max_instances)   # what a raw map may hold; what the labeler is begun with
     todo = []
     for camera in cameras:
         img_path = os.path.join(input_dir, camera["img_name"] + ".png")
@@ -222,6 +236,12 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
             ctx.upload_positions(gaussians)
             ctx.vote_begin(n_classes, min(lo, total - 1), total)
             view = ctx.vote_view
+        if associate:
+            if lift:
+                ctx.upload_positions(gaussians)
+            ctx.assoc_begin(n_segments, n_classes, assoc_min_overlap, assoc_min_size)
+            labeler_view = view
+            view = lambda camera, seg_map, size: labeler_view(camera, ctx.assoc_view(camera, seg_map, size)[1], size)
         for camera, img_path in todo[lo:hi]:
             print(f"Processing image {os.path.basename(img_path)}...")
             if segmap_dir is not None:
@@ -231,9 +251,12 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
             from PIL import Image
             os.makedirs(output_dir, exist_ok=True)
             image = Image.open(img_path)
-            seg_dev = _segment_image_device(image, processor, model, device, model_type, ctx, mask2former_map, n_classes)
+            seg_dev = _segment_image_device(image, processor, model, device, model_type, ctx, mask2former_map,
+                                            n_segments if associate else n_classes)
             view(camera, seg_dev, image.size)                   # the map goes from the network to the vote on the device ...
             _save_segmap(img_path, output_dir, seg_dev.cpu().numpy())   # ... and is copied down behind it, for the .npy only
+        if associate:
+            print(f"Association: {ctx.assoc_num_instances()} instances found, {ctx.assoc_num_dropped()} segments dropped")
         if world > 1:
             return gsx.dist.exchange_labels_gather(gsx.dist.GpuGatherShard(ctx), cap_views=total)
         return ctx.lift_finalize(lift_min_weight) if lift else ctx.vote_finalize()
@@ -312,6 +335,12 @@ def make_parser():
                         "centres; lift: class maps lifted through the rasterizer's blend (occlusion-aware, the viewer's camera convention)")
     parser.add_argument("--lift_min_weight", type=float, default=0.0, help="lift: splats whose summed blend weight stays below this "
                         "are labelled -1")
+    parser.add_argument("--associate", action="store_true", help="the maps hold per-image segment ids: associate them across the "
+                        "views through the Gaussians before they are voted or lifted (instance labels; single GPU)")
+    parser.add_argument("--assoc_min_overlap", type=float, default=0.3, help="associate: a segment takes an instance that at least "
+                        "this fraction of its Gaussians already carry")
+    parser.add_argument("--assoc_min_size", type=int, default=1, help="associate: segments of fewer Gaussians are left out")
+    parser.add_argument("--assoc_max_instances", type=int, default=255, help="associate: at most this many instances (<= 255)")
     return parser
 
 
@@ -345,6 +374,8 @@ def main(argv=None):
         parser.error("--fill_unlabeled needs --smooth_k")
     if args.split_k <= 0 and (args.split_max_dist is not None or args.split_min_size != 1 or args.split_max_instances != 0):
         parser.error("--split_max_dist, --split_min_size and --split_max_instances need --split_k")
+    if not args.associate and (args.assoc_min_overlap != 0.3 or args.assoc_min_size != 1 or args.assoc_max_instances != 255):
+        parser.error("--assoc_min_overlap, --assoc_min_size and --assoc_max_instances need --associate")
 
     print("Loading cameras...")
     cameras = load_cameras(args.camera_file)
@@ -355,7 +386,9 @@ def main(argv=None):
         labels = assign_labels(gaussians, cameras, args.input_dir, args.output_dir, model_type=args.model,
                                segmap_dir=args.segmap_dir, n_classes=args.n_classes, mask2former_map=args.mask2former_map,
                                labeler=args.labeler, splats=load_splat_attributes(plydata) if args.labeler == "lift" else None,
-                               lift_min_weight=args.lift_min_weight)
+                               lift_min_weight=args.lift_min_weight, associate=args.associate,
+                               assoc_min_overlap=args.assoc_min_overlap, assoc_min_size=args.assoc_min_size,
+                               assoc_max_instances=args.assoc_max_instances)
     except BaseException:
         _shutdown(failed=True)
         raise

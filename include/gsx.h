@@ -580,6 +580,60 @@ int gsx_lift_table(gsx_ctx* ctx, uint64_t* table_out);
 int gsx_debug_lift_constants(int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * instance association — per-view segment ids made to mean the same object in every view.  A Mask2Former map numbers its
+ * segments per image in acceptance order (dls.py:156-158): voted as they are, the ids mix objects.  A run walks the views in
+ * order and keeps, per Gaussian, the global instance it was first given (a "memory bank"); a view's segment takes the
+ * instance most of its Gaussians already carry, or opens a new one.  The relabelled maps are ordinary class maps with
+ * n_classes = max_instances for gsx_vote_view* / gsx_lift_view*.
+ *
+ * State of a run: gid[n] (int32, -1 = none yet), G = instances so far, dropped = a counter.  One view (cam, map, image size):
+ *   1. Sample.  Gaussian i is projected exactly as the vote projects it (dls.py:43-82, R (x - p), fp64), then scaled,
+ *      truncated and clamped onto the map (dls.py:270-286).  An invisible Gaussian takes no part; a visible one has
+ *      bin b = map[y_s, x_s] + 1 in 0 .. S.
+ *   2. Table.  table[b][gid[i] + 1] += 1 over the visible Gaussians: uint32, (S + 1) x (M + 1); row 0 is the background,
+ *      column 0 is "no instance yet".
+ *   3. Decide (on the host).  The rows b >= 1 in order of descending size_b (the row sum), the lower b first among equal
+ *      sizes.  size_b < min_size: remap[b-1] = -1.  Otherwise, among the instances g no earlier row of this view has taken
+ *      and with table[b][g+1] > 0, the largest count, the lowest g among equal counts; if there is one and
+ *      count * 2^20 >= q * size_b with q = ceil(min_overlap * 2^20), remap[b-1] = g and g is taken.  Otherwise, if G < M,
+ *      remap[b-1] = G, it is taken and G += 1.  Otherwise remap[b-1] = -1 and dropped += 1.
+ *   4. Remember.  Every visible Gaussian with b >= 1, remap[b-1] >= 0 and gid == -1 gets gid = remap[b-1]; the first
+ *      assignment stays.
+ *   5. Relabel.  out[p] = map[p] >= 0 ? remap[map[p]] : -1, int32, same shape.
+ * Everything is an integer: a run is reproducible bit for bit (tests/assoc_model.py is the rule in numpy).
+ * On the device one thread per Gaussian stores its bin as a byte (255 = invisible), which is why S <= 254, and the maps of the
+ * vote hold a byte per pixel, which is why M <= 255.
+ * A new gsx_upload_positions (or gsx_destroy) ends a run; calls before gsx_assoc_begin return GSX_E_STATE.
+ * ------------------------------------------------------------------------------------------- */
+/* 1 <= max_segments <= 254, 1 <= max_instances <= 255, min_overlap finite in [0, 1], min_size >= 1, else GSX_E_INVALID.
+ * Needs gsx_upload_positions (GSX_E_STATE).  Starts a run: gid = -1 everywhere, G = 0, dropped = 0, no views. */
+int gsx_assoc_begin(gsx_ctx* ctx, int32_t max_segments, int32_t max_instances, double min_overlap, int32_t min_size);
+/* seg: HOST pointer, seg_h x seg_w row-major, any gsx_seg_dtype, values in [-1, max_segments - 1]; img_w, img_h as in
+ * gsx_vote_view.  The raw map is staged into device memory through a pinned buffer and the device path runs.  The host
+ * waits for the view's table (it decides on it), so the range is checked in the same wait: a value outside the range
+ * anywhere in the map is GSX_E_RANGE, fails THIS call and changes nothing of the run.
+ * remap_out: max_segments int32 (global instance of segment s, or -1), or NULL.  map_out_dev: DEVICE pointer of seg_h x seg_w
+ * int32 that receives the relabelled map, or NULL.  Everything is done and both maps are the caller's again on return. */
+int gsx_assoc_view(gsx_ctx* ctx, const gsx_camera* cam, const void* seg, int32_t seg_dtype, int32_t seg_w, int32_t seg_h, int32_t img_w,
+                   int32_t img_h, int32_t* remap_out, void* map_out_dev);
+/* same, seg_dev is a DEVICE pointer read on the ctx stream, under the ordering rule of gsx_vote_view_device */
+int gsx_assoc_view_device(gsx_ctx* ctx, const gsx_camera* cam, const void* seg_dev, int32_t seg_dtype, int32_t seg_w, int32_t seg_h,
+                          int32_t img_w, int32_t img_h, int32_t* remap_out, void* map_out_dev);
+/* views associated, G, and the segments dropped since gsx_assoc_begin (0 outside a run) */
+int32_t gsx_assoc_num_views(const gsx_ctx* ctx);
+int32_t gsx_assoc_num_instances(const gsx_ctx* ctx);
+int64_t gsx_assoc_num_dropped(const gsx_ctx* ctx);
+/* gid_out: n int32 in the order of the arrays given to gsx_upload_positions */
+int gsx_assoc_ids(gsx_ctx* ctx, int32_t* gid_out);
+/* table_out: the last view's (max_segments + 1) x (max_instances + 1) uint32 table (zeros before the first view): a test hook,
+ * and diagnostics for a caller who wants to see why a segment matched */
+int gsx_assoc_table(gsx_ctx* ctx, uint32_t* table_out);
+/* test hook: out[8] = 2^20, its shift, Gaussians per workgroup and step of the table kernel, the largest max_segments, the
+ * largest max_instances, the 16-bit counters a workgroup's LDS copy of the table holds at most, the steps a workgroup takes at
+ * most, 0 */
+int gsx_debug_assoc_constants(int32_t* out);
+
+/* ---------------------------------------------------------------------------------------------
  * PLY files — replaces the plyfile calls of the reference: PlyData.read (dls.py:29, ply_handler.py:
  * 44-45) and PlyData([vertex], text=False).write (dls.py:331-332, ply_handler.py:35-37).
  * Only the vertex element (scalar properties) is kept, as save_labeled_ply does.  ascii and
