@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "seg_dtype.hpp"
 #include "vote_device.hpp"
 
 namespace gsx {
@@ -26,43 +27,10 @@ static constexpr int kAssocRun = 4;                       // consecutive pixels 
 static constexpr unsigned kAssocNoBad = 0xffffffffu;
 static constexpr size_t kAssocUpView = 0, kAssocUpRemap = 256, kAssocUpMap = 256 + 1024;  // byte offsets inside AssocState::up
 
-// bin = value + 1 as an unsigned number (a packed uint8 map holds the bin itself): anything outside [-1, S - 1] comes out above S
-template <int DT>
-__device__ __forceinline__ unsigned long long assoc_bin(const void* p, long long i) {
-    if (DT == GSX_SEG_I32) return (unsigned long long)((unsigned)reinterpret_cast<const int*>(p)[i] + 1u);
-    if (DT == GSX_SEG_I64) return (unsigned long long)reinterpret_cast<const long long*>(p)[i] + 1ull;
-    if (DT == GSX_SEG_U8) return reinterpret_cast<const uint8_t*>(p)[i];
-    return (unsigned long long)reinterpret_cast<const uint8_t*>(p)[i] + 1ull;
-}
-
-// four consecutive values of one lane as one 16-byte load (two for int64, four bytes for uint8) where the pointer allows it
-template <int DT>
-__device__ __forceinline__ void assoc_bins4(const void* p, long long i, long long npix, unsigned long long b[4]) {
-    constexpr int B = DT == GSX_SEG_I32 ? 4 : (DT == GSX_SEG_I64 ? 8 : 1);
-    const bool vec = (reinterpret_cast<uintptr_t>(p) & (B == 1 ? 3 : 15)) == 0 && i + 4 <= npix;
-    if (vec) {
-        if (DT == GSX_SEG_I32) {
-            const uint4 v = *reinterpret_cast<const uint4*>(reinterpret_cast<const int*>(p) + i);
-            b[0] = (unsigned long long)(v.x + 1u), b[1] = (unsigned long long)(v.y + 1u);
-            b[2] = (unsigned long long)(v.z + 1u), b[3] = (unsigned long long)(v.w + 1u);
-        } else if (DT == GSX_SEG_I64) {
-            const ulonglong2 v0 = *reinterpret_cast<const ulonglong2*>(reinterpret_cast<const long long*>(p) + i);
-            const ulonglong2 v1 = *reinterpret_cast<const ulonglong2*>(reinterpret_cast<const long long*>(p) + i + 2);
-            b[0] = v0.x + 1ull, b[1] = v0.y + 1ull, b[2] = v1.x + 1ull, b[3] = v1.y + 1ull;
-        } else {
-            const unsigned v = *reinterpret_cast<const unsigned*>(reinterpret_cast<const uint8_t*>(p) + i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = (unsigned long long)((v >> (8 * j)) & 255u) + (DT == GSX_SEG_U8 ? 0ull : 1ull);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = i + j < npix ? assoc_bin<DT>(p, i + j) : ~0ull;
-    }
-}
-
 // iou.hip's iou_table_add with a count of one, onto 16-bit counters packed in pairs: the lanes that hold the first active lane's
 // key add once, with the popcount of their ballot; two rounds (in Morton order most waves hold one or two keys), then whoever
 // is left adds on its own.  No half can carry into the other: a workgroup sees fewer than 2^16 Gaussians.
+// (Kept apart from iou_table_add on purpose: counter width, packing and LDS-only against LDS-or-global differ.)
 __device__ __forceinline__ void assoc_lds_add(unsigned* ltab, unsigned key, unsigned count) { atomicAdd(&ltab[key >> 1], count << (16 * (key & 1u))); }
 __device__ __forceinline__ void assoc_table_add(bool act, unsigned key, int lane, unsigned* ltab) {
     unsigned long long pend = __ballot(act);
@@ -117,7 +85,7 @@ __global__ __launch_bounds__(kAssocTableBlock) void assoc_table_kernel(const flo
                 xi = xs > (double)(vr.seg_w - 1) ? vr.seg_w - 1 : (int)xs;  // :285 (xs >= 0 always)
                 yi = ys > (double)(seg_h - 1) ? seg_h - 1 : (int)ys;        // :286
             }
-            const unsigned long long b = assoc_bin<DT>(seg, (long long)yi * vr.seg_w + xi);
+            const unsigned long long b = seg_bin<DT>(seg, (long long)yi * vr.seg_w + xi);
             if (b <= (unsigned long long)S) {
                 b8 = (unsigned)b;
                 key = (unsigned)b * (unsigned)G1 + (unsigned)(gid[i] + 1);
@@ -130,7 +98,7 @@ __global__ __launch_bounds__(kAssocTableBlock) void assoc_table_kernel(const flo
     unsigned bad = kAssocNoBad;
     const long long stride = (long long)gridDim.x * B;
     for (long long p = (long long)blockIdx.x * B + t; p < npix; p += stride)
-        if (assoc_bin<DT>(seg, p) > (unsigned long long)S) bad = min(bad, (unsigned)p);
+        if (seg_bin<DT>(seg, p) > (unsigned long long)S) bad = min(bad, (unsigned)p);
     if (bad != kAssocNoBad) atomicMin(err, bad);
     __syncthreads();
     for (int w = t; w < lwords; w += B) {
@@ -167,7 +135,7 @@ __global__ __launch_bounds__(kAssocBlock) void assoc_relabel_kernel(const void* 
     const long long i0 = ((long long)blockIdx.x * kAssocBlock + t) * kAssocRun;
     if (i0 >= npix) return;
     unsigned long long b[4];
-    assoc_bins4<DT>(seg, i0, npix, b);
+    seg_bins4<DT>(seg, i0, npix, b);
     int r[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = b[j] <= (unsigned long long)S ? s_remap[(int)b[j]] : -1;
@@ -310,10 +278,9 @@ int assoc_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, in
     if (seg_w < 1 || seg_h < 1 || img_w < 1 || img_h < 1 || seg_w > 65535 || seg_h > 65535)
         return fail(c, GSX_E_INVALID, "%s: map %d x %d, image %d x %d: sizes must be positive and a map at most 65535 a side", who, seg_w,
                     seg_h, img_w, img_h);
-    if (seg_dtype != GSX_SEG_I32 && seg_dtype != GSX_SEG_I64 && seg_dtype != GSX_SEG_U8 && seg_dtype != GSX_SEG_U8_LABELS)
-        return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
+    if (!seg_dtype_known(seg_dtype)) return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
     const size_t elem = seg_elem_size(seg_dtype);
-    if (reinterpret_cast<uintptr_t>(seg) & (uintptr_t)(elem - 1)) return fail(c, GSX_E_INVALID, "%s: the map is not aligned to its element", who);
+    if (seg_misaligned(seg, (int)elem)) return fail(c, GSX_E_INVALID, "%s: the map is not aligned to its element", who);
     if (reinterpret_cast<uintptr_t>(map_out_dev) & 3u) return fail(c, GSX_E_INVALID, "%s: map_out_dev is not aligned to int32", who);
     const long long npix = (long long)seg_w * seg_h;
     if (npix >= (1ll << 31)) return fail(c, GSX_E_UNSUPPORTED, "%s: %d x %d pixels: seg_w * seg_h must stay below 2^31", who, seg_w, seg_h);
@@ -338,13 +305,7 @@ int assoc_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, in
     }
     GSX_HIP(c, hipMemsetAsync(A.table.p, 0, entries * sizeof(unsigned), c->stream));
     GSX_HIP(c, hipMemsetAsync(A.table.as<unsigned>() + entries, 0xff, sizeof(unsigned), c->stream));
-    int rc;
-    switch (seg_dtype) {
-        case GSX_SEG_I32: rc = assoc_launch<GSX_SEG_I32>(c, seg_dev, npix); break;
-        case GSX_SEG_I64: rc = assoc_launch<GSX_SEG_I64>(c, seg_dev, npix); break;
-        case GSX_SEG_U8: rc = assoc_launch<GSX_SEG_U8>(c, seg_dev, npix); break;
-        default: rc = assoc_launch<GSX_SEG_U8_LABELS>(c, seg_dev, npix); break;
-    }
+    const int rc = with_seg_dtype(seg_dtype, [&](auto d) { return assoc_launch<decltype(d)::value>(c, seg_dev, npix); });
     if (rc) return rc;
     // the table comes back; the decision needs it, and so does the range check
     GSX_HIP(c, hipMemcpyAsync(A.down.p, A.table.p, tbytes, hipMemcpyDeviceToHost, c->stream));
@@ -371,12 +332,7 @@ int assoc_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, in
     GSX_HIP(c, hipGetLastError());
     if (map_out_dev) {
         int* out = static_cast<int*>(map_out_dev);
-        switch (seg_dtype) {
-            case GSX_SEG_I32: assoc_launch_relabel<GSX_SEG_I32>(c, seg_dev, npix, out); break;
-            case GSX_SEG_I64: assoc_launch_relabel<GSX_SEG_I64>(c, seg_dev, npix, out); break;
-            case GSX_SEG_U8: assoc_launch_relabel<GSX_SEG_U8>(c, seg_dev, npix, out); break;
-            default: assoc_launch_relabel<GSX_SEG_U8_LABELS>(c, seg_dev, npix, out); break;
-        }
+        with_seg_dtype(seg_dtype, [&](auto d) { assoc_launch_relabel<decltype(d)::value>(c, seg_dev, npix, out); });
         GSX_HIP(c, hipGetLastError());
     }
     GSX_HIP(c, A.up_ev.record(c->stream));

@@ -228,8 +228,6 @@ struct ProfEvent {
 // ---- small expressions with one spelling -----------------------------------------------------------------------------
 // maps, records and staging areas start on 256-byte boundaries
 constexpr size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
-// bytes per element of a map handed over as GSX_SEG_*
-constexpr size_t seg_elem_size(int seg_dtype) { return seg_dtype == GSX_SEG_I32 ? 4 : seg_dtype == GSX_SEG_I64 ? 8 : 1; }
 
 // State of the segmentation-map hand-over (handover.hip): worker pool, the pinned rings of the three transfer forms and the
 // packed maps that wait for their DMA.  Plain data; only handover.hip (and the option "host_threads") writes it.

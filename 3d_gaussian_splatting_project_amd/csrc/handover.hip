@@ -22,7 +22,7 @@
 #include <new>
 #include <vector>
 
-#include "gsx_ctx.hpp"
+#include "seg_dtype.hpp"
 #include "vote_device.hpp"
 
 namespace gsx {
@@ -245,8 +245,7 @@ static int view_prologue(Ctx* c, const char* who, const void* cams, const void* 
         return fail(c, GSX_E_INVALID, "%s: sizes must be positive (seg %dx%d, image %dx%d)", who, seg_w, seg_h, img_w, img_h);
     if (seg_w > 65535 || seg_h > 65535)  // in-map byte offsets are 32-bit, row products use 24-bit multiplies
         return fail(c, GSX_E_RANGE, "%s: segmentation map %dx%d exceeds 65535 pixels a side", who, seg_w, seg_h);
-    if (seg_dtype != GSX_SEG_I32 && seg_dtype != GSX_SEG_I64 && seg_dtype != GSX_SEG_U8 && seg_dtype != GSX_SEG_U8_LABELS)
-        return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
+    if (!seg_dtype_known(seg_dtype)) return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
     if (c->run.first_view + (int)c->run.views.size() + n > c->run.total_views)
         return fail(c, GSX_E_RANGE, "%s: more views than total_views=%d announced at vote_begin", who, c->run.total_views);
     if (c->run.local_codes && (int)c->run.views.size() + n > kMaxBatch)
@@ -547,7 +546,7 @@ int host_threads(Ctx* c) {
 // test hook, host only: the packed form of one map exactly as gsx_vote_view stages it
 int debug_host_pack(const void* seg, int seg_dtype, int w, int h, int n_classes, int tiled, int coarse, int threads,
                     uint8_t* out, int64_t out_cap, int64_t* bytes, int64_t* coarse_off, int32_t* bad) {
-    if (!seg || w < 1 || h < 1 || w > 65535 || h > 65535 || n_classes < 1 || n_classes > 255 || seg_dtype < 0 || seg_dtype > 3)
+    if (!seg || w < 1 || h < 1 || w > 65535 || h > 65535 || n_classes < 1 || n_classes > 255 || !seg_dtype_known(seg_dtype))
         return fail(nullptr, GSX_E_INVALID, "debug_host_pack: bad arguments");
     const MapLayout L = map_layout(w, h, tiled != 0, coarse != 0 && n_classes + 1 <= 255);
     if (bytes) *bytes = (int64_t)L.map_bytes;
@@ -563,7 +562,7 @@ int debug_host_pack(const void* seg, int seg_dtype, int w, int h, int n_classes,
 // test hook, host only: the compact transfer form of one map (host_pack.hpp), as gsx_vote_view writes it into the pinned ring
 int debug_host_pack_compact(const void* seg, int seg_dtype, int w, int h, int n_classes, int threads, uint8_t* out, int64_t out_cap,
                             int64_t* bytes, int64_t* table_bytes, int64_t* stream_off, int32_t* bad) {
-    if (!seg || w < 1 || h < 1 || w > 65535 || h > 65535 || n_classes < 1 || n_classes > 254 || seg_dtype < 0 || seg_dtype > 3 || !bytes)
+    if (!seg || w < 1 || h < 1 || w > 65535 || h > 65535 || n_classes < 1 || n_classes > 254 || !seg_dtype_known(seg_dtype) || !bytes)
         return fail(nullptr, GSX_E_INVALID, "debug_host_pack_compact: bad arguments");
     const MapLayout L = map_layout(w, h, true, true);
     const CompactLayout CL = compact_layout(L);

@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "gsx_ctx.hpp"
+#include "seg_dtype.hpp"
 
 namespace gsx {
 
@@ -178,41 +178,7 @@ __global__ __launch_bounds__(256) void iou_top_index_kernel(const unsigned long 
     if (in) out[i] = best;
 }
 
-// ---- table: contingency table of two label maps ------------------------------------------------------------------------------------
-// bin = label + 1 as an unsigned number: anything outside [0, n] - a label below -1 included - comes out above n
-template <int DT>
-__device__ __forceinline__ unsigned long long iou_bin(const void* p, long long i) {
-    if (DT == GSX_SEG_I32) return (unsigned long long)((unsigned)reinterpret_cast<const int*>(p)[i] + 1u);
-    if (DT == GSX_SEG_I64) return (unsigned long long)reinterpret_cast<const long long*>(p)[i] + 1ull;
-    if (DT == GSX_SEG_U8) return reinterpret_cast<const uint8_t*>(p)[i];
-    return (unsigned long long)reinterpret_cast<const uint8_t*>(p)[i] + 1ull;
-}
-
-// four consecutive labels of one lane, as one 16-byte load (two for int64, four bytes for uint8) where the pointer allows it
-template <int DT>
-__device__ __forceinline__ void iou_bins4(const void* p, long long i, long long npix, unsigned long long b[4]) {
-    constexpr int B = DT == GSX_SEG_I32 ? 4 : (DT == GSX_SEG_I64 ? 8 : 1);
-    const bool vec = (reinterpret_cast<uintptr_t>(p) & (B == 1 ? 3 : 15)) == 0 && i + 4 <= npix;
-    if (vec) {
-        if (DT == GSX_SEG_I32) {
-            const uint4 v = *reinterpret_cast<const uint4*>(reinterpret_cast<const int*>(p) + i);
-            b[0] = (unsigned long long)(v.x + 1u), b[1] = (unsigned long long)(v.y + 1u);
-            b[2] = (unsigned long long)(v.z + 1u), b[3] = (unsigned long long)(v.w + 1u);
-        } else if (DT == GSX_SEG_I64) {
-            const ulonglong2 v0 = *reinterpret_cast<const ulonglong2*>(reinterpret_cast<const long long*>(p) + i);
-            const ulonglong2 v1 = *reinterpret_cast<const ulonglong2*>(reinterpret_cast<const long long*>(p) + i + 2);
-            b[0] = v0.x + 1ull, b[1] = v0.y + 1ull, b[2] = v1.x + 1ull, b[3] = v1.y + 1ull;
-        } else {
-            const unsigned v = *reinterpret_cast<const unsigned*>(reinterpret_cast<const uint8_t*>(p) + i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = (unsigned long long)((v >> (8 * j)) & 255u) + (DT == GSX_SEG_U8 ? 0ull : 1ull);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = i + j < npix ? iou_bin<DT>(p, i + j) : ~0ull;
-    }
-}
-
+// ---- table: contingency table of two label maps (the maps are read through seg_dtype.hpp's seg_bins4) -------------------------------
 // the lanes that hold the first active lane's (key, count) add once, with count x the popcount of their ballot (the device of
 // normals.hip's radix-select histogram); two rounds, then whoever is left adds on its own
 template <bool LDS>
@@ -261,8 +227,8 @@ __global__ __launch_bounds__(kIouTableBlock) void iou_table_kernel(const void* c
         const long long i0 = q * kIouTableRun;
         unsigned long long a[4], b[4];
         if (i0 < npix) {
-            iou_bins4<DP>(pp, i0, npix, a);
-            iou_bins4<DG>(pg, i0, npix, b);
+            seg_bins4<DP>(pp, i0, npix, a);
+            seg_bins4<DG>(pg, i0, npix, b);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) a[j] = b[j] = ~0ull;
@@ -302,14 +268,6 @@ static int iou_elem_bytes(int mask_dtype) {
         case GSX_MASK_U8: return 1;
         case GSX_MASK_I32: case GSX_MASK_F32: return 4;
         case GSX_MASK_I64: case GSX_MASK_F64: return 8;
-    }
-    return 0;
-}
-static int iou_seg_bytes(int seg_dtype) {
-    switch (seg_dtype) {
-        case GSX_SEG_I32: return 4;
-        case GSX_SEG_I64: return 8;
-        case GSX_SEG_U8: case GSX_SEG_U8_LABELS: return 1;
     }
     return 0;
 }
@@ -522,17 +480,6 @@ static int iou_launch_table2(Ctx* c, bool lds, dim3 grid, size_t lds_bytes, cons
     return GSX_OK;
 }
 
-template <int DP>
-static int iou_launch_table1(Ctx* c, int gdt, bool lds, dim3 grid, size_t lds_bytes, const void* const* preds, const void* const* gts,
-                             int pair0, long long npix, int np1, int ng1, unsigned long long* table, unsigned* err) {
-    switch (gdt) {
-        case GSX_SEG_I32: return iou_launch_table2<DP, GSX_SEG_I32>(c, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-        case GSX_SEG_I64: return iou_launch_table2<DP, GSX_SEG_I64>(c, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-        case GSX_SEG_U8: return iou_launch_table2<DP, GSX_SEG_U8>(c, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-        default: return iou_launch_table2<DP, GSX_SEG_U8_LABELS>(c, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-    }
-}
-
 static int iou_launch_table(Ctx* c, int pdt, int gdt, bool lds, int pairs, const void* const* preds, const void* const* gts, int pair0,
                             long long npix, int np1, int ng1, unsigned long long* table, unsigned* err) {
     const long long nquads = (npix + kIouTableRun - 1) / kIouTableRun;
@@ -541,12 +488,12 @@ static int iou_launch_table(Ctx* c, int pdt, int gdt, bool lds, int pairs, const
     const dim3 grid((unsigned)gx, (unsigned)pairs);
     const size_t lds_bytes = lds ? sizeof(unsigned) * (size_t)np1 * ng1 : 0;
     ProfScope ps(c, "iou_table");
-    switch (pdt) {
-        case GSX_SEG_I32: return iou_launch_table1<GSX_SEG_I32>(c, gdt, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-        case GSX_SEG_I64: return iou_launch_table1<GSX_SEG_I64>(c, gdt, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-        case GSX_SEG_U8: return iou_launch_table1<GSX_SEG_U8>(c, gdt, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-        default: return iou_launch_table1<GSX_SEG_U8_LABELS>(c, gdt, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table, err);
-    }
+    return with_seg_dtype(pdt, [&](auto dp) {
+        return with_seg_dtype(gdt, [&](auto dg) {
+            return iou_launch_table2<decltype(dp)::value, decltype(dg)::value>(c, lds, grid, lds_bytes, preds, gts, pair0, npix, np1, ng1, table,
+                                                                               err);
+        });
+    });
 }
 
 int iou_label_maps(Ctx* c, bool device, int n_pairs, const void* const* pred, int pred_dtype, int n_pred_classes, const void* const* gt,
@@ -555,8 +502,9 @@ int iou_label_maps(Ctx* c, bool device, int n_pairs, const void* const* pred, in
     if (h <= 0 || w <= 0) return fail(c, GSX_E_INVALID, "%s: h and w must be positive (got %d x %d)", who, h, w);
     if (n_pairs <= 0) return fail(c, GSX_E_INVALID, "%s: n_pairs must be positive (got %d)", who, n_pairs);
     if (!pred || !gt || !table_out) return fail(c, GSX_E_INVALID, "%s: NULL argument", who);
-    const int pb = iou_seg_bytes(pred_dtype), gb = iou_seg_bytes(gt_dtype);
-    if (!pb || !gb) return fail(c, GSX_E_INVALID, "%s: unknown seg dtype (%d, %d)", who, pred_dtype, gt_dtype);
+    if (!seg_dtype_known(pred_dtype) || !seg_dtype_known(gt_dtype))
+        return fail(c, GSX_E_INVALID, "%s: unknown seg dtype (%d, %d)", who, pred_dtype, gt_dtype);
+    const int pb = (int)seg_elem_size(pred_dtype), gb = (int)seg_elem_size(gt_dtype);
     if (n_pred_classes < 1 || n_pred_classes > 255 || n_gt_classes < 1 || n_gt_classes > 255)
         return fail(c, GSX_E_INVALID, "%s: class counts must lie in [1, 255] (got %d, %d)", who, n_pred_classes, n_gt_classes);
     const long long npix = (long long)h * w;
@@ -568,7 +516,7 @@ int iou_label_maps(Ctx* c, bool device, int n_pairs, const void* const* pred, in
                     kIouListMax);
     for (int i = 0; i < n_pairs; ++i) {
         if (!pred[i] || !gt[i]) return fail(c, GSX_E_INVALID, "%s: a map of pair %d is NULL", who, i);
-        if (device && ((reinterpret_cast<uintptr_t>(pred[i]) & (uintptr_t)(pb - 1)) || (reinterpret_cast<uintptr_t>(gt[i]) & (uintptr_t)(gb - 1))))
+        if (device && (seg_misaligned(pred[i], pb) || seg_misaligned(gt[i], gb)))
             return fail(c, GSX_E_INVALID, "%s: a map of pair %d is not aligned to its element", who, i);
     }
     GSX_HIP(c, hipSetDevice(c->device));

@@ -21,8 +21,8 @@
 #include <cmath>
 #include <vector>
 
-#include "gsx_ctx.hpp"
 #include "render_device.hpp"
+#include "seg_dtype.hpp"
 
 namespace gsx {
 
@@ -47,29 +47,29 @@ void lift_constants(int32_t out[8]) {
 // are checked before anything is launched and never get here with one).
 // The stored value v is compared with the range of stored values itself, [lo - off, n_classes - off], and the bin v + off is
 // formed only for a value inside it: no sum that could leave 64 bits (v + 1 at 2^63 - 1), nothing narrowed before the test.
-template <int DTYPE>
+template <int DT>
 __host__ __device__ __forceinline__ bool lift_value_ok(long long v, int n_classes) {
-    const long long off = DTYPE == GSX_SEG_U8 ? 0 : 1;  // a packed u8 map holds the bin itself
-    const long long lo = DTYPE == GSX_SEG_U8_LABELS ? 1 : 0;  // u8 labels cannot say -1
+    const long long off = SegElem<DT>::add;  // a packed u8 map holds the bin itself
+    const long long lo = DT == GSX_SEG_U8_LABELS ? 1 : 0;  // u8 labels cannot say -1
     return v >= lo - off && v <= (long long)n_classes - off;
 }
 
-template <typename T, int DTYPE>
-__global__ __launch_bounds__(kRB) void lift_narrow_kernel(const T* __restrict__ seg, long long npix, int n_classes, int view,
-                                                           uint8_t* __restrict__ bins, int* __restrict__ flag) {
+template <int DT>
+__global__ __launch_bounds__(kRB) void lift_narrow_kernel(const typename SegElem<DT>::type* __restrict__ seg, long long npix, int n_classes,
+                                                           int view, uint8_t* __restrict__ bins, int* __restrict__ flag) {
     const long long p = (long long)blockIdx.x * kRB + threadIdx.x;
     if (p >= npix) return;
     const long long v = (long long)seg[p];
-    const bool ok = lift_value_ok<DTYPE>(v, n_classes);
-    bins[p] = ok ? (uint8_t)(v + (DTYPE == GSX_SEG_U8 ? 0 : 1)) : (uint8_t)0;
+    const bool ok = lift_value_ok<DT>(v, n_classes);
+    bins[p] = ok ? (uint8_t)(v + SegElem<DT>::add) : (uint8_t)0;
     if (!ok) atomicMin(flag, view);
 }
 
-template <typename T, int DTYPE>
+template <int DT>
 static long long host_first_bad(const void* seg, long long npix, int n_classes) {
-    const T* s = static_cast<const T*>(seg);
+    const auto* s = static_cast<const typename SegElem<DT>::type*>(seg);
     for (long long p = 0; p < npix; ++p)
-        if (!lift_value_ok<DTYPE>((long long)s[p], n_classes)) return p;
+        if (!lift_value_ok<DT>((long long)s[p], n_classes)) return p;
     return -1;
 }
 
@@ -288,24 +288,11 @@ static int lift_narrow(Ctx* c, const void* seg_dev, int seg_dtype, long long npi
     int* flag = L.flag.as<int>();
     const dim3 grid(grid_for(npix)), block(kRB);
     ProfScope ps(c, "lift_narrow");
-    switch (seg_dtype) {
-        case GSX_SEG_I32:
-            hipLaunchKernelGGL((lift_narrow_kernel<int32_t, GSX_SEG_I32>), grid, block, 0, c->stream, (const int32_t*)seg_dev, npix,
-                               L.n_classes, L.views, bins, flag);
-            break;
-        case GSX_SEG_I64:
-            hipLaunchKernelGGL((lift_narrow_kernel<long long, GSX_SEG_I64>), grid, block, 0, c->stream, (const long long*)seg_dev, npix,
-                               L.n_classes, L.views, bins, flag);
-            break;
-        case GSX_SEG_U8:
-            hipLaunchKernelGGL((lift_narrow_kernel<uint8_t, GSX_SEG_U8>), grid, block, 0, c->stream, (const uint8_t*)seg_dev, npix,
-                               L.n_classes, L.views, bins, flag);
-            break;
-        default:
-            hipLaunchKernelGGL((lift_narrow_kernel<uint8_t, GSX_SEG_U8_LABELS>), grid, block, 0, c->stream, (const uint8_t*)seg_dev, npix,
-                               L.n_classes, L.views, bins, flag);
-            break;
-    }
+    with_seg_dtype(seg_dtype, [&](auto d) {
+        constexpr int DT = decltype(d)::value;
+        hipLaunchKernelGGL(lift_narrow_kernel<DT>, grid, block, 0, c->stream, static_cast<const typename SegElem<DT>::type*>(seg_dev), npix,
+                           L.n_classes, L.views, bins, flag);
+    });
     GSX_HIP(c, hipGetLastError());
     return GSX_OK;
 }
@@ -321,8 +308,7 @@ int lift_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int
     if (!L.begun) return fail(c, GSX_E_STATE, "%s: call gsx_lift_begin first", who);
     if (c->scene.edits_on) return fail(c, GSX_E_STATE, "%s: a render edit state is set (gsx_render_set_edits): lifting through an edited frame is not defined", who);
     if (!cam || !seg || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "%s: bad arguments", who);
-    if (seg_dtype != GSX_SEG_I32 && seg_dtype != GSX_SEG_I64 && seg_dtype != GSX_SEG_U8 && seg_dtype != GSX_SEG_U8_LABELS)
-        return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
+    if (!seg_dtype_known(seg_dtype)) return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
     const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
     if (tiles_x > 256 || tiles_y > 256) return fail(c, GSX_E_UNSUPPORTED, "%s: %dx%d exceeds 4096 pixels per side", who, W, H);
     if (c->frame.pre_ext >= 0 || c->frame.in_flight) return fail(c, GSX_E_STATE, "%s: gsx_render_views is running on this context", who);
@@ -330,13 +316,7 @@ int lift_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int
     if (seg_misaligned(seg, (int)elem)) return fail(c, GSX_E_INVALID, "%s: the map is not aligned to its element", who);
     const long long npix = (long long)W * H;
     if (!device) {  // the label range, before anything is launched
-        long long bad = -1;
-        switch (seg_dtype) {
-            case GSX_SEG_I32: bad = host_first_bad<int32_t, GSX_SEG_I32>(seg, npix, L.n_classes); break;
-            case GSX_SEG_I64: bad = host_first_bad<long long, GSX_SEG_I64>(seg, npix, L.n_classes); break;
-            case GSX_SEG_U8: bad = host_first_bad<uint8_t, GSX_SEG_U8>(seg, npix, L.n_classes); break;
-            default: bad = host_first_bad<uint8_t, GSX_SEG_U8_LABELS>(seg, npix, L.n_classes); break;
-        }
+        const long long bad = with_seg_dtype(seg_dtype, [&](auto d) { return host_first_bad<decltype(d)::value>(seg, npix, L.n_classes); });
         if (bad >= 0)
             return fail(c, GSX_E_RANGE, "%s: view %d: the label at row %lld, column %lld is outside [-1, %d]", who, L.views, bad / W, bad % W,
                         L.n_classes - 1);

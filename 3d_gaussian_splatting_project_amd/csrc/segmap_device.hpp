@@ -1,5 +1,6 @@
-// Device helpers shared by the class-map units (segmap.hip, queries.hip): the widening of a network output's element and the
-// nearest-neighbour index rules.  Both units are built with -ffp-contract=off.
+// Device helpers shared by the units that make class maps from network outputs (segmap.hip, queries.hip): the widening of an
+// output's element (GSX_F32 / F16 / BF16) and the nearest-neighbour index rules.  Both units are built with -ffp-contract=off.
+// (The element codes of a class map as an argument, GSX_SEG_*, are seg_dtype.hpp's.)
 #pragma once
 #include <hip/hip_fp16.h>
 

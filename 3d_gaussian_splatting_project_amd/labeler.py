@@ -33,6 +33,39 @@ def load_cameras(camera_file):
         return json.load(f)
 
 
+_SEG_TORCH_DT = {"torch.int32": _lib.GSX_SEG_I32, "torch.int64": _lib.GSX_SEG_I64, "torch.uint8": _lib.GSX_SEG_U8_LABELS}
+_SEG_NP_DT = {np.dtype(np.int32): _lib.GSX_SEG_I32, np.dtype(np.int64): _lib.GSX_SEG_I64, np.dtype(np.uint8): _lib.GSX_SEG_U8_LABELS}
+
+
+def _seg_map_arg(seg_map, packed_u8):
+    """A class map as the library takes it -> (obj, GSX_SEG_* code, h, w, device): a C-contiguous 2-D numpy array, or with
+    device=True a contiguous tensor on the GPU.  int32, int64 and uint8 go as they are, every other dtype is widened to int32;
+    packed_u8: a uint8 map already holds label + 1.  (Once per view in a 10 ms run: the usual case - a contiguous array of a
+    supported dtype - is passed through without a numpy call.)"""
+    device = type(seg_map) is not np.ndarray and hasattr(seg_map, "data_ptr")   # a torch tensor
+    if device:
+        seg = seg_map.contiguous()
+        if not seg.is_cuda:
+            raise ValueError("tensor seg maps must live on the GPU; pass numpy arrays for host maps")
+        dt = _SEG_TORCH_DT.get(str(seg.dtype))
+        if dt is None:
+            import torch
+            seg, dt = seg.to(torch.int32), _lib.GSX_SEG_I32
+    else:
+        seg = seg_map if type(seg_map) is np.ndarray else np.asarray(seg_map)
+        dt = _SEG_NP_DT.get(seg.dtype)
+        if dt is None:
+            seg, dt = seg.astype(np.int32, copy=False), _lib.GSX_SEG_I32
+        if not seg.flags.c_contiguous:
+            seg = np.ascontiguousarray(seg)
+    if seg.ndim != 2:
+        raise ValueError("seg_map must be 2-D")
+    if packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
+        dt = _lib.GSX_SEG_U8
+    h, w = seg.shape
+    return seg, dt, h, w, device
+
+
 class Context:
     """One GPU (gsx_ctx).  device: HIP ordinal; defaults to LOCAL_RANK or 0."""
 
@@ -120,9 +153,6 @@ class Context:
         self._keep_alive.clear()
         check(self._lib.gsx_vote_begin(self.h, n_classes, first_view, total_views), self.h)
 
-    _TORCH_DT = {"torch.int32": _lib.GSX_SEG_I32, "torch.int64": _lib.GSX_SEG_I64, "torch.uint8": _lib.GSX_SEG_U8_LABELS}
-    _NP_DT = {np.dtype(np.int32): _lib.GSX_SEG_I32, np.dtype(np.int64): _lib.GSX_SEG_I64, np.dtype(np.uint8): _lib.GSX_SEG_U8_LABELS}
-
     def vote_view(self, camera, seg_map, image_size=None, packed_u8=False):
         """seg_map: 2-D int array of labels (-1..n_classes-1; any integer dtype, as the reference accepts) on the host,
         or a torch tensor on this GPU.  image_size: (width, height) of the input image; defaults to the map's own size.
@@ -136,36 +166,12 @@ class Context:
             if rc != _fast.DECLINED:
                 check(rc, self.h)
                 return
-        if type(seg_map) is not np.ndarray and hasattr(seg_map, "data_ptr"):  # torch tensor on the device
-            t = seg_map.contiguous()
-            h, w = t.shape
-            if not t.is_cuda:
-                raise ValueError("tensor seg maps must live on the GPU; pass numpy arrays for host maps")
-            dt = self._TORCH_DT.get(str(t.dtype))
-            if dt is None:
-                import torch
-                t, dt = t.to(torch.int32), _lib.GSX_SEG_I32
-            if packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
-                dt = _lib.GSX_SEG_U8
-            iw, ih = image_size if image_size is not None else (w, h)
-            check(self._lib.gsx_vote_view_device(self.h, C.byref(cam), t.data_ptr(), dt, w, h, int(iw), int(ih)), self.h)
-            self._keep_alive.append(t)   # the pack kernel runs asynchronously on the ctx stream
-            return
-        # (this runs once per view, 200 times in the 10 ms of a run: the usual case - a contiguous int32 / int64 / uint8 array -
-        # takes the short way through, ~1.5 us of Python instead of 3)
-        seg = seg_map if type(seg_map) is np.ndarray else np.asarray(seg_map)
-        if seg.ndim != 2:
-            raise ValueError("seg_map must be 2-D")
-        dt = self._NP_DT.get(seg.dtype)
-        if dt is None:
-            seg = seg.astype(np.int32, copy=False)
-            dt = _lib.GSX_SEG_I32
-        elif packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
-            dt = _lib.GSX_SEG_U8
-        if not seg.flags.c_contiguous:
-            seg = np.ascontiguousarray(seg)
-        h, w = seg.shape
+        seg, dt, h, w, device = _seg_map_arg(seg_map, packed_u8)
         iw, ih = (w, h) if image_size is None else (int(image_size[0]), int(image_size[1]))
+        if device:
+            check(self._lib.gsx_vote_view_device(self.h, C.byref(cam), seg.data_ptr(), dt, w, h, iw, ih), self.h)
+            self._keep_alive.append(seg)   # the pack kernel runs asynchronously on the ctx stream
+            return
         try:
             ptr = C.addressof(C.c_char.from_buffer(seg))   # 3x cheaper than seg.ctypes.data
         except (TypeError, ValueError):                    # a read-only or empty array
@@ -179,7 +185,7 @@ class Context:
         if not ts:
             return
         h, w = ts[0].shape
-        dt = self._TORCH_DT[str(ts[0].dtype)]
+        dt = _SEG_TORCH_DT[str(ts[0].dtype)]   # (several maps of ONE supported dtype: nothing is widened here, unlike _seg_map_arg)
         if packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
             dt = _lib.GSX_SEG_U8
         if any(t.shape != ts[0].shape or t.dtype != ts[0].dtype or not t.is_cuda for t in ts):
@@ -606,26 +612,7 @@ class Context:
         refer to (default: the camera's own width, height); they are scaled by map size / image size, which is the caller's
         job at the C level.  Host maps are range-checked here (ValueError); device maps when the table is fetched."""
         cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
-        device = type(seg_map) is not np.ndarray and hasattr(seg_map, "data_ptr")
-        if device:
-            seg = seg_map.contiguous()
-            if not seg.is_cuda:
-                raise ValueError("tensor seg maps must live on the GPU; pass numpy arrays for host maps")
-            dt = self._TORCH_DT.get(str(seg.dtype))
-            if dt is None:
-                import torch
-                seg, dt = seg.to(torch.int32), _lib.GSX_SEG_I32
-        else:
-            seg = np.asarray(seg_map)
-            dt = self._NP_DT.get(seg.dtype)
-            if dt is None:
-                seg, dt = seg.astype(np.int32), _lib.GSX_SEG_I32
-            seg = np.ascontiguousarray(seg)
-        if seg.ndim != 2:
-            raise ValueError("seg_map must be 2-D")
-        if packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
-            dt = _lib.GSX_SEG_U8
-        h, w = (int(v) for v in seg.shape)
+        seg, dt, h, w, device = _seg_map_arg(seg_map, packed_u8)
         iw, ih = (cam.width, cam.height) if image_size is None else (int(image_size[0]), int(image_size[1]))
         if (iw, ih) != (w, h) and iw > 0 and ih > 0:
             scaled = Camera()
@@ -674,25 +661,7 @@ class Context:
         vote_view.  A value outside [-1, max_segments - 1] raises ValueError and leaves the run as it was."""
         import torch
         cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
-        device = type(seg_map) is not np.ndarray and hasattr(seg_map, "data_ptr")
-        if device:
-            seg = seg_map.contiguous()
-            if not seg.is_cuda:
-                raise ValueError("tensor seg maps must live on the GPU; pass numpy arrays for host maps")
-            dt = self._TORCH_DT.get(str(seg.dtype))
-            if dt is None:
-                seg, dt = seg.to(torch.int32), _lib.GSX_SEG_I32
-        else:
-            seg = np.asarray(seg_map)
-            dt = self._NP_DT.get(seg.dtype)
-            if dt is None:
-                seg, dt = seg.astype(np.int32), _lib.GSX_SEG_I32
-            seg = np.ascontiguousarray(seg)
-        if seg.ndim != 2:
-            raise ValueError("seg_map must be 2-D")
-        if packed_u8 and dt == _lib.GSX_SEG_U8_LABELS:
-            dt = _lib.GSX_SEG_U8
-        h, w = (int(v) for v in seg.shape)
+        seg, dt, h, w, device = _seg_map_arg(seg_map, packed_u8)
         iw, ih = (w, h) if image_size is None else (int(image_size[0]), int(image_size[1]))
         remap = np.empty(self._assoc_shape[0] - 1, np.int32)
         out = torch.empty((h, w), dtype=torch.int32, device=torch.device("cuda", self.device))
@@ -1237,19 +1206,7 @@ def _iou_list(x, what, seg=False, packed_u8=False, to_host=False):
     if seg:
         out, codes = [], []
         for t in x:
-            if device:
-                t = t.contiguous()
-                code = Context._TORCH_DT.get(str(t.dtype))
-                if code is None:
-                    import torch
-                    t, code = t.to(torch.int32), _lib.GSX_SEG_I32
-            else:
-                code = Context._NP_DT.get(t.dtype)
-                if code is None:
-                    t, code = t.astype(np.int32), _lib.GSX_SEG_I32
-                t = np.ascontiguousarray(t)
-            if packed_u8 and code == _lib.GSX_SEG_U8_LABELS:
-                code = _lib.GSX_SEG_U8
+            t, code = _seg_map_arg(t, packed_u8)[:2]
             out.append(t)
             codes.append(code)
         if len(set(codes)) > 1:   # mixed dtypes: int64 holds them all (a packed uint8 map is unpacked on the way)
