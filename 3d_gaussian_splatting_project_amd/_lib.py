@@ -181,6 +181,7 @@ _SIGS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "gsx_smooth_labels_lists": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "gsx_debug_smooth_constants": (C.c_int, [C.c_void_p]),
     "gsx_split_labels": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int64)]),

@@ -648,6 +648,11 @@ int gsx_smooth_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* k
     const gsx::SmoothArgs a{rounds, min_votes, ignore_label, flags, labels_out, support_out, changed_out, rounds_done_out};
     return gsx::guard(c, __func__, [&] { return gsx::smooth_labels_lists(c, n, k, knn, labels, a); });
 }
+int gsx_debug_smooth_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_smooth_constants: NULL argument");
+    gsx::smooth_constants(out);
+    return GSX_OK;
+}
 
 int gsx_split_labels(gsx_ctx* ctx, int64_t n, const float* points, const int32_t* labels, int32_t k, double max_dist, int64_t min_size,
                      int32_t max_instances, int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* component_out,

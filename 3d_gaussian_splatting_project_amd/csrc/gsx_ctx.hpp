@@ -679,6 +679,7 @@ struct SmoothArgs {
 };
 int smooth_labels(Ctx* c, int64_t n, const float* points, const int32_t* labels, int64_t k, const SmoothArgs& a);
 int smooth_labels_lists(Ctx* c, int64_t n, int32_t k, const int32_t* knn, const int32_t* labels, const SmoothArgs& a);
+void smooth_constants(int32_t out[8]);
 // split.hip: connected components of every label over the k-nearest-neighbour graph
 struct SplitArgs {
     double max_dist;

@@ -277,4 +277,13 @@ int smooth_labels_lists(Ctx* c, int64_t n, int32_t k, const int32_t* knn, const 
     return smooth_run_lists(c, n, k, lists, labels, a);
 }
 
+void smooth_constants(int32_t out[8]) {
+    out[0] = kSmMaxK;
+    out[1] = kSmMaxClasses;
+    out[2] = 16;  // bits of a counter of the search form's table, two counters to a dword
+    out[3] = 64;  // lanes of the winner scan: lane l reads the dwords l, l + 64, ..
+    out[4] = kNnWaves;
+    out[5] = out[6] = out[7] = 0;
+}
+
 }  // namespace gsx

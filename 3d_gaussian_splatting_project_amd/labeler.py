@@ -1307,6 +1307,14 @@ def assoc_constants():
     return dict(zip(names, (int(v) for v in out)))
 
 
+def smooth_constants():
+    """Test hook, host only: the units the label filter's two forms are built on (gsx_debug_smooth_constants)."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_smooth_constants(out.ctypes.data))
+    names = ("list_max_k", "max_classes", "counter_bits", "lanes", "waves")
+    return dict(zip(names, (int(v) for v in out)))
+
+
 def lift_constants():
     """Test hook, host only: the units the lifting kernel is built on (gsx_debug_lift_constants); one = GSX_LIFT_ONE."""
     out = np.zeros(8, np.int32)

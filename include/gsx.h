@@ -865,6 +865,10 @@ int gsx_smooth_labels(gsx_ctx* ctx, int64_t n, const float* points, const int32_
 int gsx_smooth_labels_lists(gsx_ctx* ctx, int64_t n, int32_t k, const int32_t* knn, const int32_t* labels, int32_t rounds,
                             int32_t min_votes, int32_t ignore_label, int32_t flags, int32_t* labels_out, int32_t* support_out,
                             int64_t* changed_out, int32_t* rounds_done_out);
+/* test hook: out[8] = the largest k of the list form, the most distinct labels of the search form, the bits of one counter of
+ * its class table (two counters to a dword: class c is half c & 1 of dword c >> 1), the lanes of its winner scan (lane l reads
+ * the dwords l, l + lanes, ..), the queries (waves) of a workgroup, 0, 0, 0 */
+int gsx_debug_smooth_constants(int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
  * class labels into object instances: connected components of every label over the k-nearest-neighbour graph.  The viewer
