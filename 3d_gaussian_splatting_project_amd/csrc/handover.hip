@@ -302,7 +302,8 @@ void segpack_constants(int32_t out[8]) {
     out[3] = kBandRows;
     out[4] = kCStripCells;
     out[5] = kCBandRows;
-    out[6] = out[7] = 0;
+    out[6] = kDmaBatch;
+    out[7] = kCompactBatch;
 }
 
 // near: a buffer the pool is about to read (the first map of a run): the workers are placed on its NUMA node

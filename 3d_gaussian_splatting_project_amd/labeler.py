@@ -1284,10 +1284,10 @@ def queries_constants():
 
 
 def segpack_constants():
-    """Test hook, host only: the units the device map pack is built on (gsx_debug_segpack_constants)."""
+    """Test hook, host only: the units the device map pack and the host map hand-over are built on (gsx_debug_segpack_constants)."""
     out = np.zeros(8, np.int32)
     check(_lib.lib().gsx_debug_segpack_constants(out.ctypes.data))
-    names = ("block", "batch", "strip_cols", "band_rows", "cstrip_cells", "cband_rows")
+    names = ("block", "batch", "strip_cols", "band_rows", "cstrip_cells", "cband_rows", "dma_batch", "compact_batch")
     return dict(zip(names, (int(v) for v in out)))
 
 

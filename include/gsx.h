@@ -1045,7 +1045,8 @@ int gsx_segmap_from_queries(gsx_ctx* ctx, const void* masks_dev, int32_t dtype, 
 int gsx_debug_queries_constants(int32_t* out);
 /* test hook, host only: the units the device map pack (gsx_vote_view_device, gsx_vote_views_device, "host_pack" = 0) is built on,
  * out[8] = cells (threads) per workgroup, maps per launch, pixel columns per strip and pixel rows per band of the full-resolution
- * level, cells per strip and cell rows per band of the coarse level, 0, 0 */
+ * level, cells per strip and cell rows per band of the coarse level, pool-form maps per H2D copy (slots per group of the pinned
+ * ring), the most compact records per H2D copy and expansion launch */
 int gsx_debug_segpack_constants(int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------

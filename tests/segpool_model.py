@@ -128,6 +128,20 @@ BIG_SHAPE = (1920, 1080)
 NOISE = (0.0, 0.02, 0.6)
 DTYPES = ("i32", "i64", "u8", "u8p")
 
+# ---- the maps of the compact hand-over's tests (tests/test_handover_expand_gpu.py, and their host chain in tests/test_segpool_model.py)
+RANK_SHAPE = (1040, 8)                                  # 260 cells per cell row - one round of 256 threads and four more - in one band
+RANK_CASES = (                                          # mixed cells as {cell row: cell columns}: the ranks at the wave and round edges
+    {0: [63]}, {0: [64]}, {0: [63, 64], 1: [0]}, {0: range(256)}, {0: [255, 256]}, {0: list(range(256)) + [257]}, {1: [256, 259]},
+    {0: range(260), 1: range(260)})
+RANK_BLOCKS = (1, 1, 3, 256, 2, 257, 2, 520)            # mixed cells = 16-byte blocks of each case
+UNIT_SHAPES = tuple((w, h) for w in (1020, 1024, 1028) for h in (8, 9)) + ((2044, 5), (2048, 8), (2052, 5), (4100, 4))
+LONG_SHAPES = ((65535, 1), (1, 65535))                  # the largest sides the library takes
+DTYPE_SHAPES = ((61, 35), (130, 71), (1028, 9))
+
+
+def rank_case_cells(case):
+    return [(cy, cx) for cy, cols in sorted(case.items()) for cx in cols]
+
 
 def blocky_labels(rng, w, h, n_classes, p_noise, lowest=-1):
     """int64 labels in [lowest, n_classes - 1]: 8 x 8 blocks of one random label with per-pixel noise, so that uniform cells,
@@ -137,6 +151,28 @@ def blocky_labels(rng, w, h, n_classes, p_noise, lowest=-1):
     noise = rng.random((h, w)) < p_noise
     lab[noise] = rng.integers(lowest, n_classes, size=int(noise.sum()))
     return lab
+
+
+def mixed_cells_map(w, h, cells, base, n_classes=150):
+    """int64 labels: `base` everywhere, and one odd pixel in each of the listed (cell row, cell column) cells, so that exactly those
+    cells are mixed (given that no cell sticks out of the map: w and h are multiples of 4).  The k-th listed cell gets a label and
+    a place in the cell that no other of the first 16 * (n_classes - 1) cells has: a block expanded from another cell's rank shows."""
+    assert w % CELL == 0 and h % CELL == 0 and 0 <= base < n_classes
+    odd = [v for v in range(n_classes) if v != base]
+    cells = list(cells)
+    assert len(set(cells)) == len(cells) <= CELL * CELL * len(odd)
+    lab = np.full((h, w), base, np.int64)
+    for k, (cy, cx) in enumerate(cells):
+        dy, dx = divmod((k // len(odd)) % (CELL * CELL), CELL)
+        assert 0 <= cy < h // CELL and 0 <= cx < w // CELL
+        lab[cy * CELL + dy, cx * CELL + dx] = odd[k % len(odd)]
+    return lab
+
+
+def record_bytes(seg, stream_off, packed_u8=False):
+    """bytes of the map's compact record (csrc/host_pack.hpp): the table and the coarse level (stream_off, which the host hook
+    tells) and one 16-byte block per cell whose coarse byte is 255"""
+    return int(stream_off) + 16 * int((coarse_cells(bins_of(seg, packed_u8)) == 255).sum())
 
 
 def as_dtype(lab, dtype):

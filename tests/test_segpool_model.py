@@ -2,7 +2,11 @@
 trusts - oracle.pack_map_numpy on the tiled + coarse layout, and the host packer (labeler.host_pack, which writes into a zeroed
 buffer: equality over the whole array pins its padding too) on all four layouts and seg dtypes - at the shapes the GPU tests of
 tests/test_segpack_gpu.py use.  The model is written on its own; what these tests show is that three independent statements of
-the layout agree byte for byte."""
+the layout agree byte for byte.
+
+The maps of tests/test_handover_expand_gpu.py go through the host chain here: the host packer's compact record, expanded by
+oracle.expand_compact_numpy, is the model's map at 1, 3 and 16 packer threads, and its size is the model's record_bytes.  So a
+mismatch on the GPU is the expansion's or the driver's, not the inputs'."""
 import importlib
 
 import numpy as np
@@ -10,6 +14,7 @@ import pytest
 
 import oracle
 import segpool_model as M
+from segpool_rig import compact_layout, compact_record
 
 labeler = importlib.import_module("3d_gaussian_splatting_project_amd.labeler")
 
@@ -93,3 +98,79 @@ def test_mismatch_report_names_the_kind_of_byte():
         M.pool_bytes(np.full((4, 4), N_CLASSES, np.int32), N_CLASSES)
     with pytest.raises(ValueError):
         M.pool_bytes(np.full((4, 4), -2, np.int32), N_CLASSES)
+
+
+# ---- the compact hand-over's inputs (tests/test_handover_expand_gpu.py), through the host chain -------------------------------------
+def test_mixed_cells_map_and_record_bytes():
+    """mixed_cells_map mixes exactly the listed cells, each with a (label, place) of its own; record_bytes counts them"""
+    w, h = M.RANK_SHAPE
+    assert len(M.RANK_CASES) == len(M.RANK_BLOCKS) == 8
+    _, _, so = compact_layout(w, h)
+    for case, blocks in zip(M.RANK_CASES, M.RANK_BLOCKS):
+        cells = M.rank_case_cells(case)
+        lab = M.mixed_cells_map(w, h, cells, 7)
+        mixed = M.coarse_cells(M.bins_of(lab)) == 255
+        assert len(cells) == blocks == mixed.sum() and all(mixed[cy, cx] for cy, cx in cells)
+        assert (M.coarse_cells(M.bins_of(lab))[~mixed] == 8).all()
+        odd = np.argwhere(lab != 7)
+        marks = {(int(lab[y, x]), y % 4, x % 4) for y, x in odd}
+        assert len(odd) == blocks == len(marks)                   # one odd pixel per cell, no two alike
+        assert M.record_bytes(lab, so) == so + 16 * blocks
+    assert M.record_bytes(np.full((9, 17), 3, np.int32), 512) == 512 + 16 * (5 + 3 - 1)      # the ragged last column and row of cells
+    with pytest.raises(AssertionError):
+        M.mixed_cells_map(17, 8, [(0, 0)], 7)
+    with pytest.raises(AssertionError):
+        M.mixed_cells_map(16, 8, [(0, 0), (0, 0)], 7)
+    with pytest.raises(AssertionError):
+        M.mixed_cells_map(16, 8, [(2, 0)], 7)
+
+
+def host_chain(arr, packed, what):
+    """host packer -> compact record -> oracle.expand_compact_numpy == the model's map, at 1, 3 and 16 packer threads"""
+    h, w = arr.shape
+    want = M.pool_bytes(arr, N_CLASSES, packed_u8=packed)[:M.geometry(w, h, N_CLASSES)["map_bytes"]]
+    for threads in (1, 3, 16):
+        rec, tb, so = compact_record(arr, packed, threads)
+        assert rec.size == M.record_bytes(arr, so, packed), (what, threads)
+        assert np.array_equal(oracle.expand_compact_numpy(rec, w, h, tb, so), want), (what, threads)
+
+
+def test_host_chain_at_the_rank_cases():
+    w, h = M.RANK_SHAPE
+    for i, case in enumerate(M.RANK_CASES):
+        host_chain(M.mixed_cells_map(w, h, M.rank_case_cells(case), 7).astype(np.int32), False, f"rank case {i + 1}")
+    for lab in maps_of(w, h + 1)[1:]:
+        host_chain(lab.astype(np.int32), False, f"{w}x{h + 1}")
+
+
+@pytest.mark.parametrize("w,h", M.UNIT_SHAPES + M.LONG_SHAPES, ids=lambda v: str(v))
+def test_host_chain_at_the_expansion_units(w, h):
+    for lab in maps_of(w, h):
+        host_chain(lab.astype(np.int32), False, f"{w}x{h}")
+
+
+def test_host_chain_at_the_cell_strip_and_band_edges():
+    for w in M.EDGE_WIDTHS:
+        for h in M.EDGE_HEIGHTS:
+            for lab in maps_of(w, h):
+                host_chain(lab.astype(np.int32), False, f"{w}x{h}")
+
+
+@pytest.mark.parametrize("dtype", M.DTYPES)
+def test_host_chain_of_every_dtype(dtype):
+    for w, h in M.DTYPE_SHAPES:
+        for lab in maps_of(w, h, lowest=0 if dtype == "u8" else -1):
+            arr, packed = M.as_dtype(lab, dtype)
+            host_chain(arr, packed, f"{dtype} {w}x{h}")
+
+
+def test_slot_sizes_the_group_tests_rely_on():
+    """64 x 32 and 32 x 64 have one record capacity (a change between them flushes without re-laying the ring); a uniform 64 x 32 map
+    travels as table + coarse level alone, an all-mixed one fills its capacity"""
+    K = labeler.segpack_constants()
+    assert (K["dma_batch"], K["compact_batch"]) == (4, 16)
+    cap, _, so = compact_layout(64, 32)
+    assert (cap, so) == (2560, 512) and compact_layout(32, 64)[0] == cap
+    assert compact_layout(17, 9)[0] != compact_layout(322, 181)[0]
+    assert M.record_bytes(np.zeros((32, 64), np.int32), so) == so
+    assert M.record_bytes(M.mixed_cells_map(64, 32, [(cy, cx) for cy in range(8) for cx in range(16)], 0), so) == cap
