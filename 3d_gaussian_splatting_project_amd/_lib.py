@@ -145,6 +145,12 @@ _SIGS = {
     "gsx_lift_finalize": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "gsx_lift_table": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gsx_debug_lift_constants": (C.c_int, [C.c_void_p]),
+    "gsx_label_view": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsx_label_map_device": (C.c_void_p, [C.c_void_p]),
+    "gsx_label_num_passes": (C.c_int64, [C.c_void_p]),
+    "gsx_label_num_single_tiles": (C.c_int64, [C.c_void_p]),
+    "gsx_debug_labelmap_constants": (C.c_int, [C.c_void_p]),
     "gsx_assoc_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
     "gsx_assoc_view": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p]),

@@ -540,6 +540,7 @@ int gsx_upload_splats(gsx_ctx* ctx, int64_t n, const float* xyz, const float* sc
                       const float* opacity, const float* f_dc, const int32_t* labels) {
     CTX_OR_FAIL(ctx);
     gsx::lift_end(c);  // a lift run's table belongs to the splats that go away here
+    gsx::label_new_upload(c, labels != nullptr);  // ... and so do the checked one-byte labels of the label frames
     return gsx::guard(c, __func__, [&] { return gsx::upload_splats(c, n, xyz, scale, rot, opacity, f_dc, labels); });
 }
 int gsx_upload_sh(gsx_ctx* ctx, const float* f_rest, int32_t sh_degree) {
@@ -766,6 +767,31 @@ int gsx_lift_finalize(gsx_ctx* ctx, double min_weight, int32_t* labels_out, doub
 int gsx_lift_table(gsx_ctx* ctx, uint64_t* table_out) {
     CTX_OR_FAIL(ctx);
     return gsx::guard(c, __func__, [&] { return gsx::lift_table(c, table_out); });
+}
+// ---- label frames (labelmap.hip) --------------------------------------------------------------------
+int gsx_label_view(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, int32_t n_classes, double min_weight,
+                   int32_t n_planes, const int32_t* plane_labels, int32_t* label_out, uint32_t* weight_out, uint32_t* total_out,
+                   uint32_t* planes_out) {
+    CTX_OR_FAIL(ctx);
+    const gsx::LabelViewArgs a{n_classes, min_weight, n_planes, plane_labels, label_out, weight_out, total_out, planes_out};
+    return gsx::guard(c, __func__, [&] { return gsx::label_view(c, cam, width, height, a); });
+}
+void* gsx_label_map_device(gsx_ctx* ctx) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return c ? c->labelmap.map.p : nullptr;
+}
+int64_t gsx_label_num_passes(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c ? (int64_t)c->labelmap.passes : 0;
+}
+int64_t gsx_label_num_single_tiles(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c ? (int64_t)c->labelmap.single : 0;
+}
+int gsx_debug_labelmap_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_labelmap_constants: NULL argument");
+    gsx::labelmap_constants(out);
+    return GSX_OK;
 }
 // ---- instance association (assoc.hip) --------------------------------------------------------------
 int gsx_assoc_begin(gsx_ctx* ctx, int32_t max_segments, int32_t max_instances, double min_overlap, int32_t min_size) {

@@ -212,7 +212,8 @@ struct FrameCounters {
     unsigned long long unused3[19];
     struct alignas(128) Slot {
         unsigned long long n;
-        unsigned long long atomics;       // lift_kernel: global atomics it issued (same line, same spreading)
+        unsigned long long atomics;       // lift_kernel: global atomics it issued (same line, same spreading); label_kernel: list walks
+        unsigned long long single;        // label_kernel: tiles whose list holds one label bin
     } consumed[kConsumedSlots];           // pairs the blend kernels staged: one counter per 128-B line (summed at the end of the frame)
 };
 static_assert(offsetof(FrameCounters, dropped) == 8 && offsetof(FrameCounters, pairs) == 24 && offsetof(FrameCounters, nvis) == 96 &&
@@ -493,6 +494,20 @@ struct LiftState {
     unsigned long long atomics = 0;    // global atomics lift_kernel issued for the last view
 };
 
+// State of the label frames (labelmap.hip): what gsx_label_view keeps between calls
+struct LabelMapState {
+    bool has_labels = false;           // the last gsx_upload_splats came with labels
+    int checked_classes = 0;           // bins8 holds the upload's labels, all within [-1, checked_classes - 1] (0: not checked yet)
+    DevBuf bins8;                      // u8 [n], importance order: bin = label + 1
+    DevBuf bad;                        // u32: the lowest upload row whose label is out of range (~0: none)
+    DevBuf map;                        // int32 [H][W]: the last view's map (gsx_label_map_device)
+    DevBuf weight, total;              // u32 [H][W]: the winner's sum and the pixel's total, when asked for
+    DevBuf planes;                     // u32 [n_planes][H][W]
+    DevBuf plane_bins;                 // u8 [256]: the bins of the planes asked for
+    unsigned long long passes = 0;     // list walks summed over the tiles of the last view
+    unsigned long long single = 0;     // tiles of the last view whose list held one label bin
+};
+
 // State of an association run (assoc.hip): gsx_assoc_begin .. the next gsx_upload_positions
 struct AssocState {
     bool begun = false;
@@ -538,6 +553,7 @@ struct Ctx {
     RenderOpts ropt;
     RenderFrame frame;
     LiftState lift;
+    LabelMapState labelmap;
     AssocState assoc;
     // gsx_render_views: further streams + per-frame buffers.  A twin is a whole Ctx because sort.hip, ProfScope and fail take
     // one; what it uses of it is stream, sort_hist, err, scene (aliases of this context's), ropt (a copy) and frame
@@ -743,6 +759,18 @@ int lift_finalize(Ctx* c, double min_weight, int32_t* labels_out, double* share_
 int lift_table(Ctx* c, uint64_t* table_out);
 void lift_end(Ctx* c);             // a new upload ends the run
 void lift_constants(int32_t out[8]);
+// labelmap.hip: the splats' labels as the class map of a view (the transpose of the lift)
+struct LabelViewArgs {
+    int32_t n_classes;
+    double min_weight;
+    int32_t n_planes;
+    const int32_t* plane_labels;
+    int32_t* label_out;
+    uint32_t *weight_out, *total_out, *planes_out;
+};
+int label_view(Ctx* c, const gsx_camera* cam, int W, int H, const LabelViewArgs& a);
+void label_new_upload(Ctx* c, bool has_labels);  // a new upload: the checked one-byte labels go away with the old splats
+void labelmap_constants(int32_t out[8]);
 // assoc.hip: per-view segment ids -> global instance ids through the Gaussians
 int assoc_begin(Ctx* c, int max_segments, int max_instances, double min_overlap, int min_size);
 int assoc_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h,

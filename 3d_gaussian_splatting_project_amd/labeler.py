@@ -66,6 +66,13 @@ def _seg_map_arg(seg_map, packed_u8):
     return seg, dt, h, w, device
 
 
+class _DeviceInts:
+    """Zero-copy int32 view of device memory owned by libgsx (via __cuda_array_interface__)."""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(int(s) for s in shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+
+
 class Context:
     """One GPU (gsx_ctx).  device: HIP ordinal; defaults to LOCAL_RANK or 0."""
 
@@ -82,6 +89,7 @@ class Context:
         self._ext = None        # the ctx stream as torch sees it (segmap_from_*)
         self._lift_bins, self._lift_keep = 1, []   # columns of the lift table; the device map a lift view may still read
         self._assoc_shape = (2, 2)                 # the association table's shape, set by assoc_begin
+        self._label_shape = None                   # (height, width) of the map at label_map_device()
 
     def close(self):
         if getattr(self, "h", None):
@@ -647,6 +655,55 @@ class Context:
         check(self._lib.gsx_lift_table(self.h, table.ctypes.data), self.h)
         return table
 
+    # -- label frames (include/gsx.h: gsx_label_*) --------------------------------------------------
+    def label_view(self, camera, width, height, n_classes, min_weight=0.0, planes=None, to_host=True, return_weights=False):
+        """The labels given to upload_splats as the class map of the view `camera` draws at width x height: per pixel the label
+        whose splats hold the largest share of the frame's alpha there, -1 where the total is under max(1, ceil(min_weight *
+        2^20)) units of 1 / 2^20 (gsx_label_view).  The camera's fx, fy refer to its own width, height and are scaled to the
+        frame as lift_view scales them to a map.  -> int32 (height, width), row 0 on top; with to_host=False nothing (the map
+        stays at label_map_device()).  return_weights: also uint32 (weight, total), the winner's sum and the pixel's total.
+        planes: labels whose summed weights are wanted -> also uint32 (len(planes), height, width).  The extras follow the
+        map in the order (map, weight, total, planes); with to_host=False they start the tuple."""
+        cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
+        w, h = int(width), int(height)
+        if (cam.width, cam.height) != (w, h) and cam.width > 0 and cam.height > 0:
+            scaled = Camera()
+            C.memmove(C.byref(scaled), C.byref(cam), C.sizeof(Camera))
+            scaled.fx, scaled.fy, scaled.width, scaled.height = cam.fx * (w / cam.width), cam.fy * (h / cam.height), w, h
+            cam = scaled
+        shape = (max(h, 0), max(w, 0))
+        out = np.empty(shape, np.int32) if to_host else None
+        weight = np.empty(shape, np.uint32) if return_weights else None
+        total = np.empty(shape, np.uint32) if return_weights else None
+        want = None if planes is None else np.ascontiguousarray(planes, dtype=np.int32).reshape(-1)
+        n_planes = 0 if want is None else len(want)
+        stack = np.empty((n_planes,) + shape, np.uint32) if 0 < n_planes <= 256 else None
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        check(self._lib.gsx_label_view(self.h, C.byref(cam), w, h, int(n_classes), float(min_weight), n_planes, ptr(want), ptr(out),
+                                       ptr(weight), ptr(total), ptr(stack)), self.h)
+        self._label_shape = (h, w)
+        res = ([out] if to_host else []) + ([weight, total] if return_weights else []) + ([stack] if want is not None else [])
+        return None if not res else res[0] if len(res) == 1 else tuple(res)
+
+    def label_map_device(self):
+        """The map of the last label_view as an int32 (height, width) torch tensor on this GPU: a zero-copy view of memory the
+        context owns, written on the ctx stream (label_view has waited for it), valid until the next label_view or close().
+        A class map for label_map_tables, vote_view and lift_view."""
+        import torch
+        p = self._lib.gsx_label_map_device(self.h)
+        if not p or self._label_shape is None:
+            raise RuntimeError("label_map_device: no label_view yet")
+        h, w = self._label_shape
+        return torch.as_tensor(_DeviceInts(p, (h, w)), device=torch.device("cuda", self.device))
+
+    def label_num_passes(self):
+        """walks of a tile's list summed over the tiles of the last label_view: ceil(labels in the list / window) per tile"""
+        return self._lib.gsx_label_num_passes(self.h)
+
+    def label_num_single_tiles(self):
+        """tiles of the last label_view whose list held exactly one label"""
+        return self._lib.gsx_label_num_single_tiles(self.h)
+
     # -- instance association (include/gsx.h: gsx_assoc_*) ------------------------------------------
     def assoc_begin(self, max_segments=254, max_instances=255, min_overlap=0.3, min_size=1):
         """Start an association run on the Gaussians of upload_positions: maps with segment ids -1 .. max_segments - 1 per
@@ -1105,6 +1162,21 @@ def assign_instances_from_maps(gaussians, cameras, segmaps, image_sizes=None, ma
             ctx.close()
 
 
+def label_maps_from_labels(splats, labels, cameras, sizes, n_classes, min_weight=0.0, ctx=None):
+    """The class maps a labelled scene shows: splats = (xyz, scale, rot, opacity, f_dc) as for Context.upload_splats, labels
+    int (N,) in [-1, n_classes - 1], cameras / sizes parallel lists of cameras.json dicts and (width, height) of the wanted
+    maps (the camera's fx, fy are scaled to that size).  The frames use the viewer's camera convention, as lift_view does.
+    Returns a list of int32 (height, width) maps (Context.label_view)."""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.upload_splats(*splats, labels=labels)
+        return [ctx.label_view(cam, int(size[0]), int(size[1]), n_classes, min_weight) for cam, size in zip(cameras, sizes)]
+    finally:
+        if own:
+            ctx.close()
+
+
 def host_pack(seg_map, n_classes, tiled=True, coarse=True, threads=1, packed_u8=False):
     """Test hook, no GPU: the packed form gsx_vote_view stages for a host map -> (bytes u8, coarse_off or -1, bad)."""
     seg = np.asarray(seg_map)
@@ -1312,6 +1384,15 @@ def smooth_constants():
     out = np.zeros(8, np.int32)
     check(_lib.lib().gsx_debug_smooth_constants(out.ctypes.data))
     names = ("list_max_k", "max_classes", "counter_bits", "lanes", "waves")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def labelmap_constants():
+    """Test hook, host only: the units the label-frame kernel is built on (gsx_debug_labelmap_constants); window = WL, the
+    labels a tile accumulates per walk of its list."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_labelmap_constants(out.ctypes.data))
+    names = ("one", "shift", "tile", "chunk", "window", "max_classes")
     return dict(zip(names, (int(v) for v in out)))
 
 

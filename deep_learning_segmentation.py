@@ -35,6 +35,15 @@ segments to the global instances most of their Gaussians already carry (a segmen
 Gaussians, default 0.3, carry the instance; segments of fewer than N Gaussians are left out; at most M instances, default 255).
 The relabelled map is voted or lifted with n_classes = M; the _segmap.npy side files stay the raw maps.  Single GPU: the
 association is ordered over the views.
+--label_maps_dir DIR and --reproject_iou (default off) go back from the finished labels - after --smooth_k - to the views:
+the splats are uploaded again with their labels and every camera that had a class map is rendered as a label frame
+(Context.label_view) at that map's own size, fx and fy scaled by map size / camera size as the lift scales them.
+--label_maps_dir writes the frames as <img_name>_labelmap.npy (int32, -1 = no label); --reproject_iou accumulates the
+contingency table of (rendered label map, input class map) over those views on the GPU and prints the IoU of every class
+present: how well the 3-D labelling reproduces the maps it was made from.  Both need the PLY's splat attributes, work with
+either labeler and run on one GPU.  The frames use the VIEWER's camera convention, as --labeler lift does, not the reference
+labeler's: for voted labels the table therefore also measures that mismatch.  Neither goes with --associate or --split_k,
+whose labels are not the maps' classes.
 """
 import argparse
 import importlib
@@ -265,6 +274,38 @@ def assign_labels(gaussians, cameras, input_dir, output_dir, model_type="mask2fo
             ctx.close()
 
 
+def reproject_labels(splats, labels, cameras, input_dir, map_dir, n_classes, label_maps_dir=None, reproject_iou=False):
+    """The finished labels as label frames of the cameras that had a class map (an image in input_dir; the map is
+    <img_name>_segmap.npy in map_dir), each at its map's size: written to label_maps_dir as <img_name>_labelmap.npy and / or
+    compared with the maps.  -> the contingency table int64 (n_classes + 1, n_classes + 1), row = rendered label + 1, column =
+    map label + 1, summed over the views (zeros without reproject_iou).  Prints one IoU line per class present."""
+    table = np.zeros((n_classes + 1, n_classes + 1), np.int64)
+    if label_maps_dir is not None:
+        os.makedirs(label_maps_dir, exist_ok=True)
+    with gsx.Context() as ctx:
+        ctx.upload_splats(*splats, labels=labels)
+        for camera in cameras:
+            if not os.path.exists(os.path.join(input_dir, camera["img_name"] + ".png")):
+                continue
+            seg_map = np.load(os.path.join(map_dir, camera["img_name"] + "_segmap.npy"))
+            h, w = seg_map.shape
+            frame = ctx.label_view(camera, w, h, n_classes, to_host=label_maps_dir is not None)
+            if label_maps_dir is not None:
+                np.save(os.path.join(label_maps_dir, camera["img_name"] + "_labelmap.npy"), frame)
+            if reproject_iou:
+                import torch
+                seg_dev = torch.from_numpy(np.ascontiguousarray(seg_map)).to(torch.device("cuda", ctx.device))
+                table += ctx.label_map_tables([ctx.label_map_device()], [seg_dev], n_classes, n_classes)[0]
+    if reproject_iou:
+        iou = gsx.iou_from_table(table)
+        print("Reprojection IoU (rendered label map against input class map):")
+        for b in range(n_classes + 1):
+            rendered, given = int(table[b].sum()), int(table[:, b].sum())
+            if rendered or given:
+                print(f"Class {b - 1}: IoU {iou[b, b]:.6f} ({rendered} rendered, {given} input pixels)")
+    return table
+
+
 def _shutdown(failed=False):
     """Leave a torch.distributed run.  After a failure on THIS rank the peers may be blocked in a collective this rank
     will never join: no barrier then, the process ends with a non-zero code and the launcher takes the others down."""
@@ -341,6 +382,10 @@ def make_parser():
                         "this fraction of its Gaussians already carry")
     parser.add_argument("--assoc_min_size", type=int, default=1, help="associate: segments of fewer Gaussians are left out")
     parser.add_argument("--assoc_max_instances", type=int, default=255, help="associate: at most this many instances (<= 255)")
+    parser.add_argument("--label_maps_dir", default=None, help="write the finished labels as label frames of the views, "
+                        "<img_name>_labelmap.npy at each class map's size (needs the splat attributes; single GPU)")
+    parser.add_argument("--reproject_iou", action="store_true", help="print the per-class IoU of those label frames against the "
+                        "input class maps (the viewer's camera convention, as --labeler lift)")
     return parser
 
 
@@ -376,16 +421,22 @@ def main(argv=None):
         parser.error("--split_max_dist, --split_min_size and --split_max_instances need --split_k")
     if not args.associate and (args.assoc_min_overlap != 0.3 or args.assoc_min_size != 1 or args.assoc_max_instances != 255):
         parser.error("--assoc_min_overlap, --assoc_min_size and --assoc_max_instances need --associate")
+    reproject = args.label_maps_dir is not None or args.reproject_iou
+    if reproject and (args.associate or args.split_k > 0):
+        raise ValueError("--label_maps_dir and --reproject_iou compare the labels with the maps' classes: not with --associate or --split_k")
+    if reproject and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--label_maps_dir and --reproject_iou run on one GPU")
 
     print("Loading cameras...")
     cameras = load_cameras(args.camera_file)
     print("Loading gaussians...")
     gaussians, plydata = load_gaussians(args.ply_file)
+    splats = load_splat_attributes(plydata) if args.labeler == "lift" or reproject else None
     print("Assigning labels...")
     try:
         labels = assign_labels(gaussians, cameras, args.input_dir, args.output_dir, model_type=args.model,
                                segmap_dir=args.segmap_dir, n_classes=args.n_classes, mask2former_map=args.mask2former_map,
-                               labeler=args.labeler, splats=load_splat_attributes(plydata) if args.labeler == "lift" else None,
+                               labeler=args.labeler, splats=splats if args.labeler == "lift" else None,
                                lift_min_weight=args.lift_min_weight, associate=args.associate,
                                assoc_min_overlap=args.assoc_min_overlap, assoc_min_size=args.assoc_min_size,
                                assoc_max_instances=args.assoc_max_instances)
@@ -401,6 +452,10 @@ def main(argv=None):
     if args.split_k > 0:
         print("Splitting labels into instances...")
         labels = split_labels(gaussians, labels, args.split_k, args.split_max_dist, args.split_min_size, args.split_max_instances)
+    if reproject:
+        print("Rendering label frames...")
+        reproject_labels(splats, labels, cameras, args.input_dir, args.segmap_dir if args.segmap_dir is not None else args.output_dir,
+                         args.n_classes or N_CLASSES[args.model], args.label_maps_dir, args.reproject_iou)
     print("Saving labeled PLY file...")
     save_labeled_ply(args.output_file, plydata, labels)
     print(f"Done! Labeled PLY file saved as {args.output_file}")

@@ -580,6 +580,62 @@ int gsx_lift_table(gsx_ctx* ctx, uint64_t* table_out);
 int gsx_debug_lift_constants(int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * label frames — the splats' labels as the class map of a view: which pixels of this view belong to label L?  The transpose
+ * of the lifting labeler: where a lift view adds a fragment's weight to table[splat][class of the pixel], a label view adds
+ * the same weight to plane[label of the splat][pixel] and takes the arg-max per pixel.
+ *
+ * The rule.  For a view (cam, width, height) the frame is walked exactly as gsx_lift_view walks it: the same pre pass, depth
+ * order and per-tile lists, ONE depth phase and no 32x32 bins, the same `discard` rule, the same opacity cut (a tile stops
+ * once every pixel has 1 - dst.a < 1e-5, voted after every 256 records of its list), nothing from the splats runSort drops,
+ * nothing from the epilogue's repeated draws of splat 0, the viewer's camera convention (R^T (x - p), fx and fy against
+ * width x height; scaling them to a smaller frame is the caller's job).  The k-th fragment at pixel p, made by splat i, has
+ *     w = (1 - dst.a) * B
+ * and adds q = rint(w * 2^20) (GSX_LIFT_ONE, the lift's fixed point) to plane[label[i] + 1][p]: n_classes + 1 bins per pixel,
+ * bin 0 = label -1, all accumulators uint32 (a pixel's total is at most 2^20 plus half a unit per fragment).  Per pixel:
+ *     total  = the sum over the bins;
+ *     total < max(1, ceil(min_weight * 2^20))  ->  label -1, weight 0;
+ *     else the bin with the largest sum, the lowest bin winning a tie (bin 0 = label -1 can win, as in the lift and the
+ *     vote); weight = the winner's sum.
+ * All comparisons are on the integers: a map is the same bits from run to run.  Both this kernel and the lift's sum the same
+ * integers q, so for any class map seg of the view
+ *     sum over {p: seg[p] = c} of plane[b][p]  ==  sum over {i: label[i] = b - 1} of gsx_lift_table[i][c + 1]     exactly.
+ * The output is a class map in the convention of every map this library takes: int32 in [-1, n_classes - 1], height x width,
+ * row 0 = the top row.  gsx_label_map_device hands it to gsx_iou_label_maps_device, gsx_vote_view_device or
+ * gsx_lift_view_device without leaving the GPU.
+ *
+ * The labels are those given to gsx_upload_splats; every one must lie in [-1, n_classes - 1] (checked by one kernel over the
+ * n labels, once per upload and n_classes; the device then holds them as one byte per splat in importance order).  To label
+ * the frame with other labels, upload again.
+ * ------------------------------------------------------------------------------------------- */
+/* label_out: height x width int32; weight_out, total_out: height x width uint32; planes_out: n_planes x height x width uint32,
+ * plane k = the summed q of label plane_labels[k], zero where that label has no fragment, written in full on every call.  All
+ * four are HOST pointers and any of them may be NULL (label_out = NULL leaves the map on the device only); 0 <= n_planes <= 256.
+ * The call waits for its results.
+ *   GSX_E_STATE        no gsx_upload_splats yet, splats uploaded without labels, a render edit state set (as for the lift),
+ *                      gsx_render_views running on this context
+ *   GSX_E_INVALID      cam NULL, width or height < 1, n_classes outside [1, 255], min_weight negative or not finite, n_planes
+ *                      outside [0, 256] or > 0 without plane_labels, a plane label outside [-1, n_classes - 1]
+ *   GSX_E_UNSUPPORTED  more than 4096 pixels per side
+ *   GSX_E_RANGE        an uploaded label outside [-1, n_classes - 1]: the message names the first such upload row, nothing
+ *                      else is launched
+ * A failing call leaves the previous map (gsx_label_map_device) as it was.  The pair buffers are handled as gsx_lift_view
+ * handles them: the host waits for the frame's pair count, the buffers grow and the lists are rebuilt before they are walked. */
+int gsx_label_view(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, int32_t n_classes, double min_weight,
+                   int32_t n_planes, const int32_t* plane_labels, int32_t* label_out, uint32_t* weight_out, uint32_t* total_out,
+                   uint32_t* planes_out);
+/* the height x width int32 map of the last successful gsx_label_view, device memory owned by the context, written on the ctx
+ * stream (NULL before the first); valid until the next gsx_label_view or gsx_destroy */
+void* gsx_label_map_device(gsx_ctx* ctx);
+/* statistics: walks of a tile's list summed over the tiles of the last view.  A tile whose list holds D label bins walks it
+ * ceil(D / WL) times, WL = labels per LDS window (gsx_debug_labelmap_constants); a tile without a list counts 0 */
+int64_t gsx_label_num_passes(const gsx_ctx* ctx);
+/* statistics: tiles of the last view whose list held exactly one label bin (they walk once and no label competes) */
+int64_t gsx_label_num_single_tiles(const gsx_ctx* ctx);
+/* test hook: out[8] = GSX_LIFT_ONE, its shift, the tile side, records per staged chunk, labels per window (WL), the largest
+ * n_classes (255), 0, 0 */
+int gsx_debug_labelmap_constants(int32_t* out);
+
+/* ---------------------------------------------------------------------------------------------
  * instance association — per-view segment ids made to mean the same object in every view.  A Mask2Former map numbers its
  * segments per image in acceptance order (dls.py:156-158): voted as they are, the ids mix objects.  A run walks the views in
  * order and keeps, per Gaussian, the global instance it was first given (a "memory bank"); a view's segment takes the
