@@ -151,6 +151,14 @@ _SIGS = {
     "gsx_label_num_passes": (C.c_int64, [C.c_void_p]),
     "gsx_label_num_single_tiles": (C.c_int64, [C.c_void_p]),
     "gsx_debug_labelmap_constants": (C.c_int, [C.c_void_p]),
+    "gsx_depth_view": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    "gsx_depth_surface_index_device": (C.c_void_p, [C.c_void_p]),
+    "gsx_depth_surface_key_device": (C.c_void_p, [C.c_void_p]),
+    "gsx_depth_num_surface": (C.c_int64, [C.c_void_p]),
+    "gsx_depth_key_to_z": (C.c_int, [C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gsx_depth_pick": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "gsx_debug_depth_constants": (C.c_int, [C.c_void_p]),
     "gsx_assoc_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
     "gsx_assoc_view": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p]),

@@ -541,6 +541,7 @@ int gsx_upload_splats(gsx_ctx* ctx, int64_t n, const float* xyz, const float* sc
     CTX_OR_FAIL(ctx);
     gsx::lift_end(c);  // a lift run's table belongs to the splats that go away here
     gsx::label_new_upload(c, labels != nullptr);  // ... and so do the checked one-byte labels of the label frames
+    gsx::depth_new_upload(c);                     // ... and the last depth view
     return gsx::guard(c, __func__, [&] { return gsx::upload_splats(c, n, xyz, scale, rot, opacity, f_dc, labels); });
 }
 int gsx_upload_sh(gsx_ctx* ctx, const float* f_rest, int32_t sh_degree) {
@@ -791,6 +792,37 @@ int64_t gsx_label_num_single_tiles(const gsx_ctx* ctx) {
 int gsx_debug_labelmap_constants(int32_t* out) {
     if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_labelmap_constants: NULL argument");
     gsx::labelmap_constants(out);
+    return GSX_OK;
+}
+// ---- depth frames (depthmap.hip) --------------------------------------------------------------------
+int gsx_depth_view(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, double quantile, uint32_t* total_out,
+                   int64_t* moment_out, int32_t* surface_key_out, int32_t* surface_index_out) {
+    CTX_OR_FAIL(ctx);
+    const gsx::DepthViewArgs a{quantile, total_out, moment_out, surface_key_out, surface_index_out};
+    return gsx::guard(c, __func__, [&] { return gsx::depth_view(c, cam, width, height, a); });
+}
+void* gsx_depth_surface_index_device(gsx_ctx* ctx) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return c && c->depthmap.valid ? c->depthmap.index.p : nullptr;
+}
+void* gsx_depth_surface_key_device(gsx_ctx* ctx) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return c && c->depthmap.valid ? c->depthmap.key.p : nullptr;
+}
+int64_t gsx_depth_num_surface(const gsx_ctx* ctx) {
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    return c && c->depthmap.valid ? (int64_t)c->depthmap.surfaces : 0;
+}
+int gsx_depth_key_to_z(const gsx_camera* cam, int32_t width, int32_t height, double* scale, double* offset) {
+    return gsx::guard(nullptr, __func__, [&] { return gsx::depth_key_to_z(cam, width, height, scale, offset); });
+}
+int gsx_depth_pick(gsx_ctx* ctx, double x, double y, int32_t* label_out, int64_t* index_out, double* z_out) {
+    CTX_OR_FAIL(ctx);
+    return gsx::guard(c, __func__, [&] { return gsx::depth_pick(c, x, y, label_out, index_out, z_out); });
+}
+int gsx_debug_depth_constants(int32_t* out) {
+    if (!out) return gsx::fail(nullptr, GSX_E_INVALID, "debug_depth_constants: NULL argument");
+    gsx::depth_constants(out);
     return GSX_OK;
 }
 // ---- instance association (assoc.hip) --------------------------------------------------------------

@@ -212,7 +212,8 @@ struct FrameCounters {
     unsigned long long unused3[19];
     struct alignas(128) Slot {
         unsigned long long n;
-        unsigned long long atomics;       // lift_kernel: global atomics it issued (same line, same spreading); label_kernel: list walks
+        unsigned long long atomics;       // lift_kernel: global atomics it issued (same line, same spreading); label_kernel: list walks;
+                                          // depth_kernel: pixels with a surface
         unsigned long long single;        // label_kernel: tiles whose list holds one label bin
     } consumed[kConsumedSlots];           // pairs the blend kernels staged: one counter per 128-B line (summed at the end of the frame)
 };
@@ -508,6 +509,19 @@ struct LabelMapState {
     unsigned long long single = 0;     // tiles of the last view whose list held one label bin
 };
 
+// State of the depth frames (depthmap.hip): what gsx_depth_view keeps between calls
+struct DepthMapState {
+    bool valid = false;                // index / key hold a view of the current upload (gsx_depth_pick, the device maps)
+    int W = 0, H = 0;                  // ... of this size
+    double scale = 0.0, offset = 0.0;  // ... whose camera gives z_view = key * scale + offset
+    DevBuf index, key;                 // int32 [H][W]: the surface's upload row (-1: none) and depth key
+    DevBuf total;                      // u32 [H][W], when asked for
+    DevBuf moment;                     // i64 [H][W], when asked for
+    DevBuf labels;                     // int32 [n]: the upload's exact labels by upload row (gsx_depth_pick)
+    bool labels_ready = false;         // ... filled since the last upload
+    unsigned long long surfaces = 0;   // pixels of the last view with a surface
+};
+
 // State of an association run (assoc.hip): gsx_assoc_begin .. the next gsx_upload_positions
 struct AssocState {
     bool begun = false;
@@ -554,6 +568,7 @@ struct Ctx {
     RenderFrame frame;
     LiftState lift;
     LabelMapState labelmap;
+    DepthMapState depthmap;
     AssocState assoc;
     // gsx_render_views: further streams + per-frame buffers.  A twin is a whole Ctx because sort.hip, ProfScope and fail take
     // one; what it uses of it is stream, sort_hist, err, scene (aliases of this context's), ropt (a copy) and frame
@@ -771,6 +786,18 @@ struct LabelViewArgs {
 int label_view(Ctx* c, const gsx_camera* cam, int W, int H, const LabelViewArgs& a);
 void label_new_upload(Ctx* c, bool has_labels);  // a new upload: the checked one-byte labels go away with the old splats
 void labelmap_constants(int32_t out[8]);
+// depthmap.hip: per-pixel depth sums, the surface splat and the pick on it
+struct DepthViewArgs {
+    double quantile;
+    uint32_t* total_out;
+    int64_t* moment_out;
+    int32_t *key_out, *index_out;
+};
+int depth_view(Ctx* c, const gsx_camera* cam, int W, int H, const DepthViewArgs& a);
+int depth_pick(Ctx* c, double x, double y, int32_t* label_out, int64_t* index_out, double* z_out);
+int depth_key_to_z(const gsx_camera* cam, int W, int H, double* scale, double* offset);  // host only
+void depth_new_upload(Ctx* c);     // a new upload invalidates the last view
+void depth_constants(int32_t out[8]);
 // assoc.hip: per-view segment ids -> global instance ids through the Gaussians
 int assoc_begin(Ctx* c, int max_segments, int max_instances, double min_overlap, int min_size);
 int assoc_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int seg_w, int seg_h, int img_w, int img_h,

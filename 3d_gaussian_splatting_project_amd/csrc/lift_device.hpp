@@ -1,6 +1,7 @@
-// lift_device.hpp - what the two kernels that walk a frame's blend for its weights share (lift.hip: weights onto the splats;
-// labelmap.hip: weights onto the pixels): the fixed-point unit, the tile and chunk geometry and the fragment arithmetic.  Both
-// units are compiled with -ffp-contract=off, like blend.hip whose operation order lift_fragment keeps.
+// lift_device.hpp - what the kernels that walk a frame's blend for its weights share (lift.hip: weights onto the splats;
+// labelmap.hip: weights onto the pixels; depthmap.hip: weights times depth keys onto the pixels): the fixed-point unit, the tile
+// and chunk geometry and the fragment arithmetic.  All three units are compiled with -ffp-contract=off, like blend.hip whose
+// operation order lift_fragment keeps.
 #pragma once
 #include <hip/hip_runtime.h>
 

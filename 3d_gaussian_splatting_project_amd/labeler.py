@@ -73,6 +73,54 @@ class _DeviceInts:
         self.__cuda_array_interface__ = {"shape": tuple(int(s) for s in shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
 
 
+def _scaled_camera(camera, w, h):
+    """the camera with fx, fy scaled from its own width, height to a w x h frame, as lift_view scales them to a map"""
+    cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
+    if (cam.width, cam.height) != (w, h) and cam.width > 0 and cam.height > 0:
+        scaled = Camera()
+        C.memmove(C.byref(scaled), C.byref(cam), C.sizeof(Camera))
+        scaled.fx, scaled.fy, scaled.width, scaled.height = cam.fx * (w / cam.width), cam.fy * (h / cam.height), w, h
+        cam = scaled
+    return cam
+
+
+class DepthFrame:
+    """What Context.depth_view returns: total uint32, moment int64, surface_key int32, surface_index int32 (upload rows, -1 =
+    no surface), all (height, width), row 0 on top, and the view's scale, offset with z_view = key * scale + offset.
+    expected_z = moment / total * scale + offset, NaN where total == 0; surface_z, NaN where the pixel has no surface; both
+    float64 (height, width), computed in numpy when first read.  total, moment and expected_z are None after a surface-only
+    view."""
+
+    def __init__(self, total, moment, surface_key, surface_index, scale, offset):
+        self.total, self.moment, self.surface_key, self.surface_index = total, moment, surface_key, surface_index
+        self.scale, self.offset = float(scale), float(offset)
+        self._surface_z = self._expected_z = None
+
+    @property
+    def surface_z(self):
+        if self._surface_z is None:
+            self._surface_z = np.where(self.surface_index >= 0, self.surface_key.astype(np.float64) * self.scale + self.offset, np.nan)
+        return self._surface_z
+
+    @property
+    def expected_z(self):
+        if self._expected_z is None and self.total is not None and self.moment is not None:
+            fed = self.total > 0
+            mean = np.divide(self.moment.astype(np.float64), self.total.astype(np.float64), out=np.zeros(self.total.shape), where=fed)
+            self._expected_z = np.where(fed, mean * self.scale + self.offset, np.nan)
+        return self._expected_z
+
+
+def depth_key_to_z(camera, width, height):
+    """host only: (scale, offset) with z_view = key * scale + offset for the depth keys of the view (camera, width, height) -
+    runSort's int32 keys, as depth_view and debug_render_pre report them (gsx_depth_key_to_z).  The camera is taken as given:
+    scale fx, fy first where the frame is not the camera's own size (they do not enter the result)."""
+    cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
+    scale, offset = C.c_double(), C.c_double()
+    check(_lib.lib().gsx_depth_key_to_z(C.byref(cam), int(width), int(height), C.byref(scale), C.byref(offset)))
+    return scale.value, offset.value
+
+
 class Context:
     """One GPU (gsx_ctx).  device: HIP ordinal; defaults to LOCAL_RANK or 0."""
 
@@ -90,6 +138,7 @@ class Context:
         self._lift_bins, self._lift_keep = 1, []   # columns of the lift table; the device map a lift view may still read
         self._assoc_shape = (2, 2)                 # the association table's shape, set by assoc_begin
         self._label_shape = None                   # (height, width) of the map at label_map_device()
+        self._depth_shape = None                   # ... and of the maps at depth_surface_*_device()
 
     def close(self):
         if getattr(self, "h", None):
@@ -704,6 +753,58 @@ class Context:
         """tiles of the last label_view whose list held exactly one label"""
         return self._lib.gsx_label_num_single_tiles(self.h)
 
+    # -- depth frames (include/gsx.h: gsx_depth_*) --------------------------------------------------
+    def depth_view(self, camera, width, height, quantile=0.5, to_host=True, surface_only=False):
+        """Per pixel of the view `camera` draws at width x height: the blend's expected depth and the surface, the first
+        fragment at which the accumulated alpha reaches `quantile` (gsx_depth_view).  The camera's fx, fy are scaled to the
+        frame as label_view scales them.  -> DepthFrame; surface_only: total, moment and expected_z stay None and a tile
+        stops at its last surface (the surface maps are the same bits); to_host=False: nothing is copied, the maps stay at
+        depth_surface_index_device() / depth_surface_key_device() - the sums have no device form, so this is a surface-only
+        walk as well - and None is returned."""
+        cam = _scaled_camera(camera, int(width), int(height))
+        w, h = int(width), int(height)
+        shape = (max(h, 0), max(w, 0))
+        full = to_host and not surface_only
+        total = np.empty(shape, np.uint32) if full else None
+        moment = np.empty(shape, np.int64) if full else None
+        key = np.empty(shape, np.int32) if to_host else None
+        index = np.empty(shape, np.int32) if to_host else None
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        check(self._lib.gsx_depth_view(self.h, C.byref(cam), w, h, float(quantile), ptr(total), ptr(moment), ptr(key), ptr(index)),
+              self.h)
+        self._depth_shape = (h, w)
+        if not to_host:
+            return None
+        scale, offset = depth_key_to_z(cam, w, h)
+        return DepthFrame(total, moment, key, index, scale, offset)
+
+    def _depth_map_device(self, fn, what):
+        import torch
+        p = fn(self.h)
+        if not p or self._depth_shape is None:
+            raise RuntimeError(f"{what}: no depth_view since the last upload_splats")
+        return torch.as_tensor(_DeviceInts(p, self._depth_shape), device=torch.device("cuda", self.device))
+
+    def depth_surface_index_device(self):
+        """The surface's upload rows (-1: none) of the last depth_view as an int32 (height, width) torch tensor on this GPU: a
+        zero-copy view of memory the context owns, valid until the next depth_view, upload_splats or close()."""
+        return self._depth_map_device(self._lib.gsx_depth_surface_index_device, "depth_surface_index_device")
+
+    def depth_surface_key_device(self):
+        """... and the surface's depth keys (0 where there is none)"""
+        return self._depth_map_device(self._lib.gsx_depth_surface_key_device, "depth_surface_key_device")
+
+    def depth_num_surface(self):
+        """pixels of the last depth_view with a surface"""
+        return self._lib.gsx_depth_num_surface(self.h)
+
+    def pick(self, x, y):
+        """The surface of the LAST depth_view under the canvas point (x, y), y from the bottom as hit_test takes it ->
+        (label or -999999, upload row or -1, view-space z or NaN).  Renders nothing (gsx_depth_pick)."""
+        label, index, z = C.c_int32(), C.c_int64(), C.c_double()
+        check(self._lib.gsx_depth_pick(self.h, float(x), float(y), C.byref(label), C.byref(index), C.byref(z)), self.h)
+        return label.value, index.value, z.value
+
     # -- instance association (include/gsx.h: gsx_assoc_*) ------------------------------------------
     def assoc_begin(self, max_segments=254, max_instances=255, min_overlap=0.3, min_size=1):
         """Start an association run on the Gaussians of upload_positions: maps with segment ids -1 .. max_segments - 1 per
@@ -1177,6 +1278,20 @@ def label_maps_from_labels(splats, labels, cameras, sizes, n_classes, min_weight
             ctx.close()
 
 
+def depth_maps(splats, cameras, sizes, quantile=0.5, ctx=None):
+    """The depth frames of a scene: splats = (xyz, scale, rot, opacity, f_dc) as for Context.upload_splats, cameras / sizes
+    parallel lists of cameras.json dicts and (width, height) of the wanted maps (the camera's fx, fy are scaled to that size).
+    The frames use the viewer's camera convention.  Returns a list of DepthFrame (Context.depth_view)."""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.upload_splats(*splats)
+        return [ctx.depth_view(cam, int(size[0]), int(size[1]), quantile) for cam, size in zip(cameras, sizes)]
+    finally:
+        if own:
+            ctx.close()
+
+
 def host_pack(seg_map, n_classes, tiled=True, coarse=True, threads=1, packed_u8=False):
     """Test hook, no GPU: the packed form gsx_vote_view stages for a host map -> (bytes u8, coarse_off or -1, bad)."""
     seg = np.asarray(seg_map)
@@ -1393,6 +1508,14 @@ def labelmap_constants():
     out = np.zeros(8, np.int32)
     check(_lib.lib().gsx_debug_labelmap_constants(out.ctypes.data))
     names = ("one", "shift", "tile", "chunk", "window", "max_classes")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def depth_constants():
+    """Test hook, host only: the units the depth-frame kernel is built on (gsx_debug_depth_constants)."""
+    out = np.zeros(8, np.int32)
+    check(_lib.lib().gsx_debug_depth_constants(out.ctypes.data))
+    names = ("one", "shift", "tile", "chunk")
     return dict(zip(names, (int(v) for v in out)))
 
 

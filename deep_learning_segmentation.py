@@ -44,6 +44,11 @@ present: how well the 3-D labelling reproduces the maps it was made from.  Both 
 either labeler and run on one GPU.  The frames use the VIEWER's camera convention, as --labeler lift does, not the reference
 labeler's: for voted labels the table therefore also measures that mismatch.  Neither goes with --associate or --split_k,
 whose labels are not the maps' classes.
+--depth_maps_dir DIR [--depth_quantile Q] (default off, Q = 0.5) renders the same views - every camera that had a class map, at
+that map's size, fx and fy scaled likewise - as depth frames (Context.depth_view): <img_name>_depth.npy is the float32
+view-space depth of the surface, the first fragment at which the accumulated alpha reaches Q (NaN = no surface), and
+<img_name>_surface.npy the int32 PLY row of the splat that is that surface (-1 = none).  Needs the PLY's splat attributes, not
+the labels; works with every other flag; one GPU; the VIEWER's camera convention.
 """
 import argparse
 import importlib
@@ -306,6 +311,26 @@ def reproject_labels(splats, labels, cameras, input_dir, map_dir, n_classes, lab
     return table
 
 
+def write_depth_maps(splats, cameras, input_dir, map_dir, depth_maps_dir, quantile=0.5):
+    """The depth frames (Context.depth_view) of the cameras that had a class map (an image in input_dir; the map is
+    <img_name>_segmap.npy in map_dir), each at its map's size, fx and fy scaled to it: <img_name>_depth.npy, float32 view-space
+    depth of the surface (the first fragment at which the accumulated alpha reaches `quantile`; NaN where there is none), and
+    <img_name>_surface.npy, int32 row of that splat in the PLY (-1: none).  -> the names written."""
+    os.makedirs(depth_maps_dir, exist_ok=True)
+    written = []
+    with gsx.Context() as ctx:
+        ctx.upload_splats(*splats)
+        for camera in cameras:
+            if not os.path.exists(os.path.join(input_dir, camera["img_name"] + ".png")):
+                continue
+            h, w = np.load(os.path.join(map_dir, camera["img_name"] + "_segmap.npy"), mmap_mode="r").shape
+            frame = ctx.depth_view(camera, w, h, quantile, surface_only=True)
+            np.save(os.path.join(depth_maps_dir, camera["img_name"] + "_depth.npy"), frame.surface_z.astype(np.float32))
+            np.save(os.path.join(depth_maps_dir, camera["img_name"] + "_surface.npy"), frame.surface_index)
+            written.append(camera["img_name"])
+    return written
+
+
 def _shutdown(failed=False):
     """Leave a torch.distributed run.  After a failure on THIS rank the peers may be blocked in a collective this rank
     will never join: no barrier then, the process ends with a non-zero code and the launcher takes the others down."""
@@ -386,6 +411,11 @@ def make_parser():
                         "<img_name>_labelmap.npy at each class map's size (needs the splat attributes; single GPU)")
     parser.add_argument("--reproject_iou", action="store_true", help="print the per-class IoU of those label frames against the "
                         "input class maps (the viewer's camera convention, as --labeler lift)")
+    parser.add_argument("--depth_maps_dir", default=None, help="write the depth frames of the views: <img_name>_depth.npy (float32 "
+                        "view-space depth of the surface) and <img_name>_surface.npy (int32 PLY row of the surface splat) at each "
+                        "class map's size (needs the splat attributes; single GPU)")
+    parser.add_argument("--depth_quantile", type=float, default=None, help="the surface is where the accumulated alpha reaches this "
+                        "(0 < q <= 1, default 0.5)")
     return parser
 
 
@@ -426,12 +456,19 @@ def main(argv=None):
         raise ValueError("--label_maps_dir and --reproject_iou compare the labels with the maps' classes: not with --associate or --split_k")
     if reproject and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--label_maps_dir and --reproject_iou run on one GPU")
+    if args.depth_quantile is not None and args.depth_maps_dir is None:
+        parser.error("--depth_quantile needs --depth_maps_dir")
+    quantile = 0.5 if args.depth_quantile is None else args.depth_quantile
+    if not 0.0 < quantile <= 1.0:
+        parser.error("--depth_quantile must be in (0, 1]")
+    if args.depth_maps_dir is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--depth_maps_dir runs on one GPU")
 
     print("Loading cameras...")
     cameras = load_cameras(args.camera_file)
     print("Loading gaussians...")
     gaussians, plydata = load_gaussians(args.ply_file)
-    splats = load_splat_attributes(plydata) if args.labeler == "lift" or reproject else None
+    splats = load_splat_attributes(plydata) if args.labeler == "lift" or reproject or args.depth_maps_dir is not None else None
     print("Assigning labels...")
     try:
         labels = assign_labels(gaussians, cameras, args.input_dir, args.output_dir, model_type=args.model,
@@ -456,6 +493,10 @@ def main(argv=None):
         print("Rendering label frames...")
         reproject_labels(splats, labels, cameras, args.input_dir, args.segmap_dir if args.segmap_dir is not None else args.output_dir,
                          args.n_classes or N_CLASSES[args.model], args.label_maps_dir, args.reproject_iou)
+    if args.depth_maps_dir is not None:
+        print("Rendering depth frames...")
+        write_depth_maps(splats, cameras, args.input_dir, args.segmap_dir if args.segmap_dir is not None else args.output_dir,
+                         args.depth_maps_dir, quantile)
     print("Saving labeled PLY file...")
     save_labeled_ply(args.output_file, plydata, labels)
     print(f"Done! Labeled PLY file saved as {args.output_file}")

@@ -636,6 +636,63 @@ int64_t gsx_label_num_single_tiles(const gsx_ctx* ctx);
 int gsx_debug_labelmap_constants(int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * depth frames — next to a frame's colour: how far away is the surface at a pixel, and which splat is that surface?
+ * gsx_hit_test (the reference's performHitTesting) picks the nearest projected CENTRE within 10 px whatever stands in front of
+ * it; gsx_depth_view + gsx_depth_pick pick what the frame shows.
+ *
+ * The rule.  The frame is gsx_label_view's and gsx_lift_view's, step for step: the same pre pass, depth order and per-tile
+ * lists, ONE depth phase and 16x16 tiles, the same `discard` rule, the same opacity cut (a tile stops once every pixel has
+ * 1 - dst.a < 1e-5, voted after every 256 records of its list), nothing from the splats runSort drops, nothing from the
+ * epilogue's repeated draws of splat 0, the viewer's camera convention.  For pixel p the fragments in walk order are
+ * k = 0, 1, ...; fragment k has the weight q_k = rint(w_k * 2^20) (the lift's fixed point, GSX_LIFT_ONE), is made by splat i_k,
+ * and has the depth key d_k = runSort's int32 key of i_k in this view, ((vp2 x + vp6 y + vp10 z) * 4096) | 0 (gs.js:436-441;
+ * gsx_debug_render_pre shows it).  Then
+ *     total[p]  = sum of q_k                      uint32: the very number gsx_label_view writes to total_out
+ *     moment[p] = sum of q_k * d_k                int64 (q <= 2^20, |d| < 2^31, a pixel's sum of q stays near 2^20)
+ *     cut       = max(1, ceil(quantile * 2^20)),  quantile in (0, 1]
+ *     the SURFACE of p is the first k with q_0 + ... + q_k >= cut:
+ *         surface_key[p]   = d_k
+ *         surface_index[p] = the UPLOAD row of i_k (as gsx_lift_finalize reports rows), not the importance row
+ *     a pixel whose total stays below the cut has no surface: index -1, key 0.
+ * A tile without a list writes 0, 0, 0, -1.  Everything is integer arithmetic on integers: the maps are the same bits from run
+ * to run, and for any class map seg of the view
+ *     sum over {p: seg[p] = c} of moment[p]  ==  sum over i of d_i * gsx_lift_table[i][c + 1]     exactly.
+ * The key is affine in view-space depth, key / 4096 = proj[10] * (z_view - view[14]) with the matrices gsx_render_view builds,
+ * so scene units are one fp64 multiply-add away (gsx_depth_key_to_z): expected depth = moment / total * scale + offset.
+ * The splats' labels are not needed.
+ * ------------------------------------------------------------------------------------------- */
+/* total_out: height x width uint32; moment_out: height x width int64; surface_key_out, surface_index_out: height x width
+ * int32.  All four are HOST pointers and any of them may be NULL.  total_out and moment_out both NULL selects the
+ * surface-only mode: a tile also stops once every pixel of the frame has its surface; the surface maps are bit for bit those
+ * of the full walk.  The call waits for its results.
+ *   GSX_E_STATE        no gsx_upload_splats yet, a render edit state set, gsx_render_views running on this context
+ *   GSX_E_INVALID      cam NULL, width or height < 1, quantile not in (0, 1] or not finite
+ *   GSX_E_UNSUPPORTED  more than 4096 pixels per side
+ * A failing call leaves the previous view's maps as they were.  The pair buffers are handled as gsx_label_view handles them. */
+int gsx_depth_view(gsx_ctx* ctx, const gsx_camera* cam, int32_t width, int32_t height, double quantile, uint32_t* total_out,
+                   int64_t* moment_out, int32_t* surface_key_out, int32_t* surface_index_out);
+/* the height x width int32 maps of the last successful gsx_depth_view since the last gsx_upload_splats (NULL without one):
+ * device memory owned by the context, written on the ctx stream; valid until the next gsx_depth_view, gsx_upload_splats or
+ * gsx_destroy */
+void* gsx_depth_surface_index_device(gsx_ctx* ctx);
+void* gsx_depth_surface_key_device(gsx_ctx* ctx);
+/* statistics: pixels of the last view with a surface */
+int64_t gsx_depth_num_surface(const gsx_ctx* ctx);
+/* host only, no context: z_view = key * scale + offset, from the view and projection matrices gsx_render_view builds for
+ * (cam, width, height); the key truncates, so the result lies within one key unit (= scale) of the exact depth.
+ * GSX_E_INVALID: a NULL argument, width or height < 1 */
+int gsx_depth_key_to_z(const gsx_camera* cam, int32_t width, int32_t height, double* scale, double* offset);
+/* the surface under a canvas point of the LAST depth view: x, y as gsx_hit_test takes them (y from the bottom): the pixel's
+ * column is floor(x), its row height - 1 - floor(y).  label_out: the exact int32 given to gsx_upload_splats for that splat
+ * (-999999, NO_SELECTION, when uploaded without labels); index_out: its upload row; z_out: key * scale + offset of that
+ * view's camera.  A point outside the frame or a pixel without a surface gives -999999, -1, NaN and GSX_OK, as gsx_hit_test
+ * does for a miss.  Copies a few bytes out of the device maps and renders nothing.  Any output may be NULL.
+ * GSX_E_STATE: no depth view since the last gsx_upload_splats */
+int gsx_depth_pick(gsx_ctx* ctx, double x, double y, int32_t* label_out, int64_t* index_out, double* z_out);
+/* test hook: out[8] = GSX_LIFT_ONE, its shift, the tile side, records per staged chunk, 0, 0, 0, 0 */
+int gsx_debug_depth_constants(int32_t* out);
+
+/* ---------------------------------------------------------------------------------------------
  * instance association — per-view segment ids made to mean the same object in every view.  A Mask2Former map numbers its
  * segments per image in acceptance order (dls.py:156-158): voted as they are, the ids mix objects.  A run walks the views in
  * order and keeps, per Gaussian, the global instance it was first given (a "memory bank"); a view's segment takes the
