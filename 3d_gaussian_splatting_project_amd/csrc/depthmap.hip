@@ -28,10 +28,11 @@ void depth_constants(int32_t out[8]) {
 }
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------------------
-// One workgroup per 16x16 tile, one pixel per lane, modelled on label_kernel: 256 records staged through LDS at a time, next to
-// s0 / s1 / sa their depth key and upload row, so that the walk reads LDS broadcasts only.  A lane carries dst.a, total, moment
-// and its surface in registers: no LDS accumulators, no atomics, no presence pass, one walk.  total is the running sum itself:
-// the surface is the fragment that takes it from below the cut to the cut or beyond (such a fragment has q > 0, as cut >= 1).
+// One workgroup per 16x16 tile, one pixel per lane, built from the pieces of lift_device.hpp that lift_kernel and label_kernel
+// walk with: 256 records staged through LDS at a time, next to s0 / s1 / sa their depth key and upload row, so that the walk
+// reads LDS broadcasts only.  A lane carries dst.a, total, moment and its surface in registers: no LDS accumulators, no
+// atomics, no presence pass, one walk.  total is the running sum itself: the surface is the fragment that takes it from below
+// the cut to the cut or beyond (such a fragment has q > 0, as cut >= 1).
 // Pixels outside the frame contribute 0, count as opaque and write nothing.  A tile without a list writes 0, 0, 0, -1 and
 // returns as a whole; in every other tile no lane leaves before the last barrier.
 //
@@ -54,11 +55,9 @@ __global__ __launch_bounds__(kLiftThreads) void depth_kernel(const int2* __restr
     const int tile = (int)blockIdx.x;
     const int2 range = ranges[tile];
     const int tid = (int)threadIdx.x;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int px = tx * kLiftTile + (tid & (kLiftTile - 1));
-    const int py = ty * kLiftTile + (tid >> 4);
-    const bool inside = px < W && py < H;
-    const size_t pix = (size_t)py * (size_t)W + (size_t)px;  // used only where inside
+    const LiftPixel p = lift_pixel(tile, tiles_x, W, H, tid);
+    const bool inside = p.inside;
+    const size_t pix = p.pix;
     if (range.y <= range.x) {  // (workgroup-uniform) nothing reaches this tile
         if (inside) {
             if (total_out) total_out[pix] = 0u;
@@ -68,9 +67,7 @@ __global__ __launch_bounds__(kLiftThreads) void depth_kernel(const int2* __restr
         }
         return;
     }
-    const float fxp = (float)px + 0.5f;               // pixel centre, GL window coordinates
-    const float fyp = (float)H - ((float)py + 0.5f);  // window y is up; image row py counts from the top
-    float a = 0.0f;                                   // gl.clear to (0,0,0,0): only dst.a is carried
+    float a = 0.0f;  // gl.clear to (0,0,0,0): only dst.a is carried
     uint32_t total = 0u;
     long long moment = 0ll;
     int surf_key = 0, surf_row = -1;
@@ -80,24 +77,20 @@ __global__ __launch_bounds__(kLiftThreads) void depth_kernel(const int2* __restr
         __syncthreads();
         if (tid < cnt) {
             const uint32_t id = vals[base + tid];
-            s0[tid] = rec[3 * (size_t)id];
-            s1[tid] = rec[3 * (size_t)id + 1];
-            sa[tid] = reinterpret_cast<const float2*>(rec + 3 * (size_t)id + 2)->y;
+            lift_stage(s0, s1, sa, rec, id, tid);
             skey[tid] = depth[id];
             srow[tid] = (int)order[id];
         }
         __syncthreads();
         for (int k = 0; k < cnt; ++k) {
-            const float w = lift_fragment(a, fxp, fyp, s0[k], s1[k], sa[k]);
-            const uint32_t q = inside && w > 0.0f ? (uint32_t)rintf(w * (float)kLiftOne) : 0u;  // <= 2^20: w <= 1
+            const uint32_t q = lift_weight(a, p, s0[k], s1[k], sa[k]);
             const uint32_t run = total + q;
             if (total < cut && run >= cut) surf_key = skey[k], surf_row = srow[k];
             total = run;
             if (full) moment += (long long)(int)q * (long long)skey[k];  // (workgroup-uniform)
         }
         staged += cnt;
-        // every further fragment is weighted by (1 - dst.a): the frame's rule, a tile stops once that is < 1e-5 on all of it
-        if (__syncthreads_and(!inside || a > 1.0f - 1.0e-5f)) break;
+        if (lift_tile_opaque(p, a)) break;
         if (!full && __syncthreads_and(!inside || total >= cut)) break;
     }
     if (inside) {
@@ -106,10 +99,10 @@ __global__ __launch_bounds__(kLiftThreads) void depth_kernel(const int2* __restr
         key_out[pix] = surf_key;
         index_out[pix] = surf_row;
     }
-    // statistics, spread over kConsumedSlots lines like the blend kernels': records staged, pixels with a surface
+    // statistics: records staged, pixels with a surface
     const int surfaces = __syncthreads_count(inside && surf_row >= 0);
     if (tid == 0) {
-        unsigned long long* slot = consumed + (blockIdx.x & (kConsumedSlots - 1)) * 16;
+        unsigned long long* slot = lift_stats_slot(consumed);
         atomicAdd(slot, (unsigned long long)staged);
         atomicAdd(slot + 1, (unsigned long long)surfaces);
     }
@@ -140,20 +133,15 @@ int depth_key_to_z(const gsx_camera* cam, int W, int H, double* scale, double* o
     return GSX_OK;
 }
 
-// One view.  The frame's front and the handling of the pair count are label_view's: the counters are read back once the lists
-// stand, the buffers grow and the lists are rebuilt until they fit, and only then depth_kernel walks them.
+// One view: a walked frame (render.hip: frame_walk_guard, frame_lists_that_fit), depth_kernel walks lists that fit.
 int depth_view(Ctx* c, const gsx_camera* cam, int W, int H, const DepthViewArgs& a) {
     GSX_HIP(c, hipSetDevice(c->device));
     DepthMapState& S = c->depthmap;
     const char* who = "depth_view";
     if (c->scene.rn <= 0) return fail(c, GSX_E_STATE, "%s: no splats uploaded (gsx_upload_splats)", who);
-    if (c->scene.edits_on)
-        return fail(c, GSX_E_STATE, "%s: a render edit state is set (gsx_render_set_edits): a depth frame through an edited frame is not defined", who);
-    if (c->frame.pre_ext >= 0 || c->frame.in_flight) return fail(c, GSX_E_STATE, "%s: gsx_render_views is running on this context", who);
-    if (!cam || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "%s: bad arguments (camera, width %d, height %d)", who, W, H);
+    int rc = frame_walk_guard(c, cam, W, H, who, "a depth frame");
+    if (rc) return rc;
     if (!(a.quantile > 0.0) || !(a.quantile <= 1.0)) return fail(c, GSX_E_INVALID, "%s: quantile = %g must be in (0, 1]", who, a.quantile);
-    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
-    if (tiles_x > 256 || tiles_y > 256) return fail(c, GSX_E_UNSUPPORTED, "%s: %dx%d exceeds 4096 pixels per side", who, W, H);
     const size_t npix = (size_t)W * (size_t)H;
     const bool full = a.total_out || a.moment_out;
     if (4 * npix > S.index.cap || 4 * npix > S.key.cap) S.valid = false;  // the maps are about to move: the last view goes with them
@@ -164,50 +152,26 @@ int depth_view(Ctx* c, const gsx_camera* cam, int W, int H, const DepthViewArgs&
     const uint32_t cut = (uint32_t)std::max(1.0, std::ceil(a.quantile * (double)kLiftOne));  // <= 2^20
     RenderFrame& f = c->frame;
     FramePlan fp;
-    int rc;
-    if ((rc = frame_plan(c, W, H, false, 1, fp))) return rc;
-    FrameCounters* fc = f.small.as<FrameCounters>();
-    FrameCounters stats;
-    for (int attempt = 0;; ++attempt) {
-        const size_t cap = f.pair_cap;
-        if ((rc = frame_depth_order(c, cam, fp))) return rc;
-        const uint32_t* vals = nullptr;
-        if ((rc = frame_phase_lists(c, fp, 0, 1, &vals))) return rc;
-        GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
-        GSX_HIP(c, hipStreamSynchronize(c->stream));
-        const unsigned long long P = stats.pairs[0];
-        if (P > 0x7fffffffull)
-            return fail(c, GSX_E_RANGE, "%s: %llu (tile, splat) pairs exceed 2^31-1 (a close-up of a very large scene)", who, P);
-        if (P > cap) {  // EMIT wrote nothing and the ranges are empty: grow, rebuild the lists
-            if (attempt >= 2) return fail(c, GSX_E_STATE, "%s: pair buffers overflowed three times in a row", who);
-            f.pair_cap = (size_t)(P + P / 4 + 4096);
-            continue;
-        }
-        f.P = P;
-        S.valid = false;  // from here on the maps are this view's, and it stands once its results have arrived
-        {
-            ProfScope ps(c, "depth");
-            hipLaunchKernelGGL(depth_kernel, dim3(fp.ntiles), dim3(kLiftThreads), 0, c->stream, f.ranges.as<int2>(), vals,
-                               f.cur->rec.as<float4>(), f.cur->depth.as<int>(), c->scene.order.as<uint32_t>(), W, H, tiles_x, cut,
-                               full ? 1 : 0, a.total_out ? S.total.as<uint32_t>() : nullptr,
-                               a.moment_out ? S.moment.as<long long>() : nullptr, S.key.as<int32_t>(), S.index.as<int32_t>(),
-                               &fc->consumed[0].n);
-        }
-        GSX_HIP(c, hipGetLastError());
-        break;
+    const uint32_t* vals = nullptr;
+    if ((rc = frame_lists_that_fit(c, cam, W, H, who, fp, &vals))) return rc;
+    S.valid = false;  // from here on the maps are this view's, and it stands once its results have arrived
+    {
+        ProfScope ps(c, "depth");
+        hipLaunchKernelGGL(depth_kernel, dim3(fp.ntiles), dim3(kLiftThreads), 0, c->stream, f.ranges.as<int2>(), vals,
+                           f.cur->rec.as<float4>(), f.cur->depth.as<int>(), c->scene.order.as<uint32_t>(), W, H, fp.tiles_x, cut,
+                           full ? 1 : 0, a.total_out ? S.total.as<uint32_t>() : nullptr,
+                           a.moment_out ? S.moment.as<long long>() : nullptr, S.key.as<int32_t>(), S.index.as<int32_t>(),
+                           &f.small.as<FrameCounters>()->consumed[0].n);
     }
-    GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipGetLastError());
+    FrameCounters stats;
+    if ((rc = frame_walk_stats_queue(c, stats))) return rc;
     if (a.total_out) GSX_HIP(c, hipMemcpyAsync(a.total_out, S.total.p, 4 * npix, hipMemcpyDeviceToHost, c->stream));
     if (a.moment_out) GSX_HIP(c, hipMemcpyAsync(a.moment_out, S.moment.p, 8 * npix, hipMemcpyDeviceToHost, c->stream));
     if (a.key_out) GSX_HIP(c, hipMemcpyAsync(a.key_out, S.key.p, 4 * npix, hipMemcpyDeviceToHost, c->stream));
     if (a.index_out) GSX_HIP(c, hipMemcpyAsync(a.index_out, S.index.p, 4 * npix, hipMemcpyDeviceToHost, c->stream));
     GSX_HIP(c, hipStreamSynchronize(c->stream));
-    f.consumed = 0;
-    S.surfaces = 0;
-    for (const FrameCounters::Slot& slot : stats.consumed) {
-        f.consumed += slot.n;
-        S.surfaces += slot.atomics;
-    }
+    frame_walk_stats_sum(c, stats, &S.surfaces, nullptr);
     S.W = W, S.H = H;
     (void)depth_key_to_z(cam, W, H, &S.scale, &S.offset);
     S.valid = true;

@@ -747,6 +747,12 @@ void render_release_twin(Ctx* c);
 int frame_plan(Ctx* c, int W, int H, bool allow_bin32, int phases, FramePlan& fp);
 int frame_depth_order(Ctx* c, const gsx_camera* cam, FramePlan& fp);
 int frame_phase_lists(Ctx* c, const FramePlan& fp, int p, int first_phase, const uint32_t** vals_sorted);
+// a walked frame (lift_view, label_view, depth_view): the frame-state and size checks; plan + lists of one depth phase, rebuilt
+// until they fit the pair buffers (nothing walked yet); the kernel's statistics, queued without a wait, summed after the caller's
+int frame_walk_guard(Ctx* c, const gsx_camera* cam, int W, int H, const char* who, const char* what);
+int frame_lists_that_fit(Ctx* c, const gsx_camera* cam, int W, int H, const char* who, FramePlan& fp, const uint32_t** vals);
+int frame_walk_stats_queue(Ctx* c, FrameCounters& stats);
+void frame_walk_stats_sum(Ctx* c, const FrameCounters& stats, unsigned long long* atomics, unsigned long long* single);  // -> c->frame.consumed too
 int debug_exclusive_scan(Ctx* c, const uint32_t* in, uint32_t* out, long long n, unsigned long long* grand_dev);  // test hook: exclusive_scan_u32
 int debug_ranges(Ctx* c, const uint32_t* keys, const unsigned long long* total_dev, long long cap, int nlists, int2* ranges);  // test hook: ranges_kernel as a frame launches it
 // bin_kernel COUNT -> exclusive_scan_u32 -> bin_kernel EMIT of one depth phase (device pointers): what render_view launches per
@@ -774,6 +780,7 @@ int lift_finalize(Ctx* c, double min_weight, int32_t* labels_out, double* share_
 int lift_table(Ctx* c, uint64_t* table_out);
 void lift_end(Ctx* c);             // a new upload ends the run
 void lift_constants(int32_t out[8]);
+unsigned long long lift_threshold(double min_weight);  // ceil(min_weight * 2^20), saturating at 2^64 - 1
 // labelmap.hip: the splats' labels as the class map of a view (the transpose of the lift)
 struct LabelViewArgs {
     int32_t n_classes;

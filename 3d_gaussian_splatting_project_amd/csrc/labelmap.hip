@@ -49,8 +49,9 @@ __global__ __launch_bounds__(kRB) void label_bins_kernel(const int* __restrict__
 }
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------------------
-// One workgroup per 16x16 tile, one pixel per lane, modelled on lift_kernel: 256 records staged through LDS at a time, every
-// pixel walks them carrying only dst.a, the opacity vote falls after every staged chunk.  Pixels outside the frame contribute
+// One workgroup per 16x16 tile, one pixel per lane, built from the pieces of lift_device.hpp that lift_kernel walks with: 256
+// records staged through LDS at a time, every pixel walks them carrying only dst.a, the opacity vote falls after every staged
+// chunk.  Pixels outside the frame contribute
 // 0, count as opaque and write nothing.  A tile without a list writes label -1 and zeros and returns as a whole; in every other
 // tile no lane leaves before the last barrier.
 __global__ __launch_bounds__(kLiftThreads) void label_kernel(const int2* __restrict__ ranges, const uint32_t* __restrict__ vals,
@@ -70,12 +71,9 @@ __global__ __launch_bounds__(kLiftThreads) void label_kernel(const int2* __restr
     const int tile = (int)blockIdx.x;
     const int2 range = ranges[tile];
     const int tid = (int)threadIdx.x;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int px = tx * kLiftTile + (tid & (kLiftTile - 1));
-    const int py = ty * kLiftTile + (tid >> 4);
-    const bool inside = px < W && py < H;
-    const size_t npix = (size_t)W * (size_t)H;
-    const size_t pix = (size_t)py * (size_t)W + (size_t)px;  // used only where inside
+    const LiftPixel p = lift_pixel(tile, tiles_x, W, H, tid);
+    const bool inside = p.inside;
+    const size_t npix = (size_t)W * (size_t)H, pix = p.pix;
     if (range.y <= range.x) {  // (workgroup-uniform) nothing reaches this tile
         if (inside) {
             label_out[pix] = -1;
@@ -85,8 +83,6 @@ __global__ __launch_bounds__(kLiftThreads) void label_kernel(const int2* __restr
         }
         return;
     }
-    const float fxp = (float)px + 0.5f;               // pixel centre, GL window coordinates
-    const float fyp = (float)H - ((float)py + 0.5f);  // window y is up; image row py counts from the top
     if (tid < 8) present[tid] = 0u;
     __syncthreads();
     // the bins of the tile's list, once: a 256-bit mask, a bin's slot = its rank
@@ -122,21 +118,17 @@ __global__ __launch_bounds__(kLiftThreads) void label_kernel(const int2* __restr
             __syncthreads();
             if (tid < cnt) {
                 const uint32_t id = vals[base + tid];
-                s0[tid] = rec[3 * (size_t)id];
-                s1[tid] = rec[3 * (size_t)id + 1];
-                sa[tid] = reinterpret_cast<const float2*>(rec + 3 * (size_t)id + 2)->y;
+                lift_stage(s0, s1, sa, rec, id, tid);
                 sslot[tid] = (uint8_t)rank256(pw, (uint32_t)bins8[id]);
             }
             __syncthreads();
             for (int k = 0; k < cnt; ++k) {
-                const float w = lift_fragment(a, fxp, fyp, s0[k], s1[k], sa[k]);
-                const uint32_t q = inside && w > 0.0f ? (uint32_t)rintf(w * (float)kLiftOne) : 0u;  // <= 2^20: w <= 1
-                const uint32_t s = (uint32_t)sslot[k] - (uint32_t)lo;  // (workgroup-uniform)
+                const uint32_t q = lift_weight(a, p, s0[k], s1[k], sa[k]);
+                const uint32_t s =(uint32_t)sslot[k] - (uint32_t)lo;  // (workgroup-uniform)
                 if (s < (uint32_t)kLabelWindow && q) atomicAdd(&acc[s * kLiftThreads + tid], q);  // no result used: one LDS add
             }
             if (win == 0) staged += cnt;
-            // every further fragment is weighted by (1 - dst.a): the frame's rule, a tile stops once that is < 1e-5 on all of it
-            if (__syncthreads_and(!inside || a > 1.0f - 1.0e-5f)) break;
+            if (lift_tile_opaque(p, a)) break;
         }
         // the window's sums: bins ascend with the slots, so a strict > keeps the lowest bin on a tie
         for (int s = 0; s < nslot; ++s) {
@@ -161,9 +153,9 @@ __global__ __launch_bounds__(kLiftThreads) void label_kernel(const int2* __restr
         if (weight_out) weight_out[pix] = keep ? best : 0u;
         if (total_out) total_out[pix] = total;
     }
-    // statistics, spread over kConsumedSlots lines like the blend kernels': records staged by the first walk, walks, one-label tiles
+    // statistics: records staged by the first walk, walks, one-label tiles
     if (tid == 0) {
-        unsigned long long* slot = consumed + (blockIdx.x & (kConsumedSlots - 1)) * 16;
+        unsigned long long* slot = lift_stats_slot(consumed);
         atomicAdd(slot, (unsigned long long)staged);
         atomicAdd(slot + 1, (unsigned long long)nwin);
         if (D == 1) atomicAdd(slot + 2, 1ull);
@@ -197,18 +189,15 @@ static int label_check(Ctx* c, int n_classes) {
     return GSX_OK;
 }
 
-// One view.  The frame's front and the handling of the pair count are lift_view's: the counters are read back once the lists
-// stand, the buffers grow and the lists are rebuilt until they fit, and only then label_kernel walks them.
+// One view: a walked frame (render.hip: frame_walk_guard, frame_lists_that_fit), label_kernel walks lists that fit.
 int label_view(Ctx* c, const gsx_camera* cam, int W, int H, const LabelViewArgs& a) {
     GSX_HIP(c, hipSetDevice(c->device));
     LabelMapState& S = c->labelmap;
     const char* who = "label_view";
     if (c->scene.rn <= 0) return fail(c, GSX_E_STATE, "%s: no splats uploaded (gsx_upload_splats)", who);
     if (!S.has_labels) return fail(c, GSX_E_STATE, "%s: the splats were uploaded without labels", who);
-    if (c->scene.edits_on)
-        return fail(c, GSX_E_STATE, "%s: a render edit state is set (gsx_render_set_edits): a label frame through an edited frame is not defined", who);
-    if (c->frame.pre_ext >= 0 || c->frame.in_flight) return fail(c, GSX_E_STATE, "%s: gsx_render_views is running on this context", who);
-    if (!cam || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "%s: bad arguments (camera, width %d, height %d)", who, W, H);
+    int rc = frame_walk_guard(c, cam, W, H, who, "a label frame");
+    if (rc) return rc;
     if (a.n_classes < 1 || a.n_classes > kLiftMaxBins - 1)
         return fail(c, GSX_E_INVALID, "%s: n_classes = %d must be in [1, %d]", who, a.n_classes, kLiftMaxBins - 1);
     if (!(a.min_weight >= 0.0) || !(a.min_weight <= 1.0e300)) return fail(c, GSX_E_INVALID, "%s: min_weight must be finite and >= 0", who);
@@ -222,10 +211,7 @@ int label_view(Ctx* c, const gsx_camera* cam, int W, int H, const LabelViewArgs&
             return fail(c, GSX_E_INVALID, "%s: plane %d asks for label %d, outside [-1, %d]", who, k, v, a.n_classes - 1);
         pb[k] = (uint8_t)(v + 1);
     }
-    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
-    if (tiles_x > 256 || tiles_y > 256) return fail(c, GSX_E_UNSUPPORTED, "%s: %dx%d exceeds 4096 pixels per side", who, W, H);
-    int rc = label_check(c, a.n_classes);
-    if (rc) return rc;
+    if ((rc = label_check(c, a.n_classes))) return rc;
     const size_t npix = (size_t)W * (size_t)H;
     const int n_planes = a.planes_out ? a.n_planes : 0;
     GSX_HIP(c, S.map.ensure(4 * npix));
@@ -239,54 +225,28 @@ int label_view(Ctx* c, const gsx_camera* cam, int W, int H, const LabelViewArgs&
             return fail(c, GSX_E_HIP, "%s: could not allocate %zu bytes for %d planes of %dx%d", who, 4 * npix * (size_t)n_planes, n_planes, W, H);
         }
     }
-    const double scaled = std::ceil(a.min_weight * (double)kLiftOne);
-    const unsigned long long threshold =
-        scaled >= 18446744073709551615.0 ? ~0ull : std::max(1ull, (unsigned long long)scaled);
+    const unsigned long long threshold = std::max(1ull, lift_threshold(a.min_weight));
     RenderFrame& f = c->frame;
     FramePlan fp;
-    if ((rc = frame_plan(c, W, H, false, 1, fp))) return rc;
-    FrameCounters* fc = f.small.as<FrameCounters>();
-    FrameCounters stats;
-    for (int attempt = 0;; ++attempt) {
-        const size_t cap = f.pair_cap;
-        if ((rc = frame_depth_order(c, cam, fp))) return rc;
-        const uint32_t* vals = nullptr;
-        if ((rc = frame_phase_lists(c, fp, 0, 1, &vals))) return rc;
-        GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
-        GSX_HIP(c, hipStreamSynchronize(c->stream));
-        const unsigned long long P = stats.pairs[0];
-        if (P > 0x7fffffffull)
-            return fail(c, GSX_E_RANGE, "%s: %llu (tile, splat) pairs exceed 2^31-1 (a close-up of a very large scene)", who, P);
-        if (P > cap) {  // EMIT wrote nothing and the ranges are empty: grow, rebuild the lists
-            if (attempt >= 2) return fail(c, GSX_E_STATE, "%s: pair buffers overflowed three times in a row", who);
-            f.pair_cap = (size_t)(P + P / 4 + 4096);
-            continue;
-        }
-        f.P = P;
-        {
-            ProfScope ps(c, "label");
-            hipLaunchKernelGGL(label_kernel, dim3(fp.ntiles), dim3(kLiftThreads), 0, c->stream, f.ranges.as<int2>(), vals,
-                               f.cur->rec.as<float4>(), S.bins8.as<uint8_t>(), W, H, tiles_x, threshold, n_planes,
-                               S.plane_bins.as<uint8_t>(), S.map.as<int32_t>(),
-                               a.weight_out ? S.weight.as<uint32_t>() : nullptr, a.total_out ? S.total.as<uint32_t>() : nullptr,
-                               n_planes ? S.planes.as<uint32_t>() : nullptr, &fc->consumed[0].n);
-        }
-        GSX_HIP(c, hipGetLastError());
-        break;
+    const uint32_t* vals = nullptr;
+    if ((rc = frame_lists_that_fit(c, cam, W, H, who, fp, &vals))) return rc;
+    {
+        ProfScope ps(c, "label");
+        hipLaunchKernelGGL(label_kernel, dim3(fp.ntiles), dim3(kLiftThreads), 0, c->stream, f.ranges.as<int2>(), vals,
+                           f.cur->rec.as<float4>(), S.bins8.as<uint8_t>(), W, H, fp.tiles_x, threshold, n_planes,
+                           S.plane_bins.as<uint8_t>(), S.map.as<int32_t>(),
+                           a.weight_out ? S.weight.as<uint32_t>() : nullptr, a.total_out ? S.total.as<uint32_t>() : nullptr,
+                           n_planes ? S.planes.as<uint32_t>() : nullptr, &f.small.as<FrameCounters>()->consumed[0].n);
     }
-    GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+    GSX_HIP(c, hipGetLastError());
+    FrameCounters stats;
+    if ((rc = frame_walk_stats_queue(c, stats))) return rc;
     if (a.label_out) GSX_HIP(c, hipMemcpyAsync(a.label_out, S.map.p, 4 * npix, hipMemcpyDeviceToHost, c->stream));
     if (a.weight_out) GSX_HIP(c, hipMemcpyAsync(a.weight_out, S.weight.p, 4 * npix, hipMemcpyDeviceToHost, c->stream));
     if (a.total_out) GSX_HIP(c, hipMemcpyAsync(a.total_out, S.total.p, 4 * npix, hipMemcpyDeviceToHost, c->stream));
     if (n_planes) GSX_HIP(c, hipMemcpyAsync(a.planes_out, S.planes.p, 4 * npix * (size_t)n_planes, hipMemcpyDeviceToHost, c->stream));
     GSX_HIP(c, hipStreamSynchronize(c->stream));
-    f.consumed = 0;
-    S.passes = S.single = 0;
-    for (const FrameCounters::Slot& slot : stats.consumed) {
-        f.consumed += slot.n;
-        S.passes += slot.atomics;
-        S.single += slot.single;
-    }
+    frame_walk_stats_sum(c, stats, &S.passes, &S.single);
     return GSX_OK;
 }
 

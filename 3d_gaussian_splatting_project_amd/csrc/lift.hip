@@ -74,11 +74,10 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     return v;
 }
 
-// (the fragment arithmetic lift_fragment and rank256 live in lift_device.hpp: labelmap.hip walks the same fragments)
-
 // One workgroup per 16x16 tile, modelled on blend_kernel: 256 records staged through LDS at a time, every pixel walks them
-// carrying only dst.a; the opacity vote falls after every staged chunk.  Pixels outside the frame contribute 0 and count as
-// opaque.  A chunk is walked in ROUNDS of `sub` records, sub * (classes in the tile) <= kLiftCells accumulators: up to 8
+// carrying only dst.a; the opacity vote falls after every staged chunk.  The walk's pieces - pixel, staging, weight, vote,
+// statistics slot - and rank256 live in lift_device.hpp: labelmap.hip and depthmap.hip walk the same fragments with them.
+// Pixels outside the frame contribute 0 and count as opaque.  A chunk is walked in ROUNDS of `sub` records, sub * (classes in the tile) <= kLiftCells accumulators: up to 8
 // classes in a tile a round is the whole chunk; the worst case (255 classes in 256 pixels) walks 8 records per round - correct,
 // slow.  No lane leaves before the last barrier: a tile without a list returns as a whole, before the first one.
 __global__ __launch_bounds__(kLiftThreads) void lift_kernel(const int2* __restrict__ ranges, const uint32_t* __restrict__ vals,
@@ -99,18 +98,14 @@ __global__ __launch_bounds__(kLiftThreads) void lift_kernel(const int2* __restri
     const int2 range = ranges[tile];
     if (range.y <= range.x) return;  // (workgroup-uniform)
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int px = tx * kLiftTile + (tid & (kLiftTile - 1));
-    const int py = ty * kLiftTile + (tid >> 4);
-    const bool inside = px < W && py < H;
-    const float fxp = (float)px + 0.5f;               // pixel centre, GL window coordinates
-    const float fyp = (float)H - ((float)py + 0.5f);  // window y is up; image row py counts from the top
+    const LiftPixel p = lift_pixel(tile, tiles_x, W, H, tid);
+    const bool inside = p.inside;
     if (tid < 8) present[tid] = 0u;
     if (tid == 0) natom = 0u;
     for (int i = tid; i < kLiftCells; i += kLiftThreads) cells[i] = 0u;
     __syncthreads();
     // the tile's classes, once: a 256-bit mask of the bins present, a pixel's class index = the rank of its bin
-    const uint32_t b = inside ? (uint32_t)bins[(size_t)py * W + px] : 0u;
+    const uint32_t b = inside ? (uint32_t)bins[p.pix] : 0u;
     if (inside) atomicOr(&present[b >> 5], 1u << (b & 31u));
     __syncthreads();
     uint32_t pw[8];
@@ -147,17 +142,14 @@ __global__ __launch_bounds__(kLiftThreads) void lift_kernel(const int2* __restri
         __syncthreads();
         if (tid < cnt) {
             const uint32_t id = vals[base + tid];
-            s0[tid] = rec[3 * (size_t)id];
-            s1[tid] = rec[3 * (size_t)id + 1];
-            sa[tid] = reinterpret_cast<const float2*>(rec + 3 * (size_t)id + 2)->y;
+            lift_stage(s0, s1, sa, rec, id, tid);
             sid[tid] = id;
         }
         __syncthreads();
         for (int r0 = 0; r0 < cnt; r0 += sub) {
             const int r1 = min(cnt, r0 + sub);
             for (int k = r0; k < r1; ++k) {
-                const float w = lift_fragment(a, fxp, fyp, s0[k], s1[k], sa[k]);
-                const uint32_t q = inside && w > 0.0f ? (uint32_t)rintf(w * (float)kLiftOne) : 0u;  // <= 2^20: w <= 1
+                const uint32_t q = lift_weight(a, p, s0[k], s1[k], sa[k]);
                 if (__ballot(q != 0u) == 0ull) continue;  // (wave-uniform) the record puts nothing on this wave's pixels
                 uint32_t* row = cells + (k - r0) * D;
                 if (uniform) {
@@ -188,14 +180,13 @@ __global__ __launch_bounds__(kLiftThreads) void lift_kernel(const int2* __restri
             __syncthreads();
         }
         staged += cnt;
-        // every further fragment is weighted by (1 - dst.a): the frame's rule, a tile stops once that is < 1e-5 on all of it
-        if (__syncthreads_and(!inside || a > 1.0f - 1.0e-5f)) break;
+        if (lift_tile_opaque(p, a)) break;
     }
-    // statistics, spread over kConsumedSlots lines like the blend kernels': records staged, global atomics issued
+    // statistics: records staged, global atomics issued
     if (my_atoms) atomicAdd(&natom, my_atoms);
     __syncthreads();
     if (tid == 0) {
-        unsigned long long* slot = consumed + (blockIdx.x & (kConsumedSlots - 1)) * 16;
+        unsigned long long* slot = lift_stats_slot(consumed);
         atomicAdd(slot, (unsigned long long)staged);
         if (natom) atomicAdd(slot + 1, (unsigned long long)natom);
     }
@@ -265,21 +256,17 @@ static int lift_narrow(Ctx* c, const void* seg_dev, int seg_dtype, long long npi
     return GSX_OK;
 }
 
-// One view.  The frame's front is render_view's; what differs is WHEN the host learns the pair count.  render_view reads it at
-// the end of the frame and redoes a frame whose lists overflowed the pair buffers - a lift view must never count a frame twice
-// or count a truncated list, so the counters are read back once the lists stand (one host wait) and lift_kernel only runs on
-// lists that fit; until then the buffers grow and the lists are rebuilt.  A second read at the end fetches the statistics.
+// One view: a walked frame (render.hip: frame_walk_guard, frame_lists_that_fit - lift_kernel only runs on lists that fit, so no
+// frame is counted twice and no truncated list is counted).  A second read at the end fetches the statistics.
 int lift_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int W, int H, bool device) {
     GSX_HIP(c, hipSetDevice(c->device));
     LiftState& L = c->lift;
     const char* who = device ? "lift_view_device" : "lift_view";
     if (!L.begun) return fail(c, GSX_E_STATE, "%s: call gsx_lift_begin first", who);
-    if (c->scene.edits_on) return fail(c, GSX_E_STATE, "%s: a render edit state is set (gsx_render_set_edits): lifting through an edited frame is not defined", who);
-    if (!cam || !seg || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "%s: bad arguments", who);
+    int rc = frame_walk_guard(c, cam, W, H, who, "lifting");
+    if (rc) return rc;
+    if (!seg) return fail(c, GSX_E_INVALID, "%s: bad arguments (the map is NULL)", who);
     if (!seg_dtype_known(seg_dtype)) return fail(c, GSX_E_INVALID, "%s: unknown seg_dtype %d", who, seg_dtype);
-    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
-    if (tiles_x > 256 || tiles_y > 256) return fail(c, GSX_E_UNSUPPORTED, "%s: %dx%d exceeds 4096 pixels per side", who, W, H);
-    if (c->frame.pre_ext >= 0 || c->frame.in_flight) return fail(c, GSX_E_STATE, "%s: gsx_render_views is running on this context", who);
     const size_t elem = seg_elem_size(seg_dtype);
     if (seg_misaligned(seg, (int)elem)) return fail(c, GSX_E_INVALID, "%s: the map is not aligned to its element", who);
     const long long npix = (long long)W * H;
@@ -296,47 +283,23 @@ int lift_view(Ctx* c, const gsx_camera* cam, const void* seg, int seg_dtype, int
         GSX_HIP(c, hipMemcpyAsync(L.raw.p, seg, elem * (size_t)npix, hipMemcpyHostToDevice, c->stream));
         seg_dev = L.raw.p;
     }
-    int rc = lift_narrow(c, seg_dev, seg_dtype, npix);
-    if (rc) return rc;
+    if ((rc = lift_narrow(c, seg_dev, seg_dtype, npix))) return rc;
     if (!device) GSX_HIP(c, hipStreamSynchronize(c->stream));  // the caller's map has been read when the call returns
     RenderFrame& f = c->frame;
     FramePlan fp;
-    if ((rc = frame_plan(c, W, H, false, 1, fp))) return rc;
-    FrameCounters* fc = f.small.as<FrameCounters>();
+    const uint32_t* vals = nullptr;
+    if ((rc = frame_lists_that_fit(c, cam, W, H, who, fp, &vals))) return rc;
+    {
+        ProfScope ps(c, "lift");
+        hipLaunchKernelGGL(lift_kernel, dim3(fp.ntiles), dim3(kLiftThreads), 0, c->stream, f.ranges.as<int2>(), vals,
+                           f.cur->rec.as<float4>(), L.bins.as<uint8_t>(), W, H, fp.tiles_x, L.n_classes + 1,
+                           L.table.as<unsigned long long>(), &f.small.as<FrameCounters>()->consumed[0].n);
+    }
+    GSX_HIP(c, hipGetLastError());
     FrameCounters stats;
-    for (int attempt = 0;; ++attempt) {
-        const size_t cap = f.pair_cap;
-        if ((rc = frame_depth_order(c, cam, fp))) return rc;
-        const uint32_t* vals = nullptr;
-        if ((rc = frame_phase_lists(c, fp, 0, 1, &vals))) return rc;
-        GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
-        GSX_HIP(c, hipStreamSynchronize(c->stream));
-        const unsigned long long P = stats.pairs[0];
-        if (P > 0x7fffffffull)
-            return fail(c, GSX_E_RANGE, "%s: %llu (tile, splat) pairs exceed 2^31-1 (a close-up of a very large scene)", who, P);
-        if (P > cap) {  // EMIT wrote nothing and the ranges are empty: grow, rebuild the lists
-            if (attempt >= 2) return fail(c, GSX_E_STATE, "%s: pair buffers overflowed three times in a row", who);
-            f.pair_cap = (size_t)(P + P / 4 + 4096);
-            continue;
-        }
-        f.P = P;
-        {
-            ProfScope ps(c, "lift");
-            hipLaunchKernelGGL(lift_kernel, dim3(fp.ntiles), dim3(kLiftThreads), 0, c->stream, f.ranges.as<int2>(), vals,
-                               f.cur->rec.as<float4>(), L.bins.as<uint8_t>(), W, H, tiles_x, L.n_classes + 1,
-                               L.table.as<unsigned long long>(), &fc->consumed[0].n);
-        }
-        GSX_HIP(c, hipGetLastError());
-        break;
-    }
-    GSX_HIP(c, hipMemcpyAsync(&stats, fc, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = frame_walk_stats_queue(c, stats))) return rc;
     GSX_HIP(c, hipStreamSynchronize(c->stream));
-    f.consumed = 0;
-    L.atomics = 0;
-    for (const FrameCounters::Slot& slot : stats.consumed) {
-        f.consumed += slot.n;
-        L.atomics += slot.atomics;
-    }
+    frame_walk_stats_sum(c, stats, &L.atomics, nullptr);
     ++L.views;
     return GSX_OK;
 }
@@ -350,6 +313,11 @@ static int lift_check_maps(Ctx* c, const char* who) {
     return GSX_OK;
 }
 
+unsigned long long lift_threshold(double min_weight) {
+    const double scaled = std::ceil(min_weight * (double)kLiftOne);
+    return scaled >= 18446744073709551615.0 ? ~0ull : (unsigned long long)scaled;
+}
+
 int lift_finalize(Ctx* c, double min_weight, int32_t* labels_out, double* share_out) {
     GSX_HIP(c, hipSetDevice(c->device));
     LiftState& L = c->lift;
@@ -358,8 +326,7 @@ int lift_finalize(Ctx* c, double min_weight, int32_t* labels_out, double* share_
     if (!(min_weight >= 0.0) || !(min_weight <= 1.0e300)) return fail(c, GSX_E_INVALID, "lift_finalize: min_weight must be finite and >= 0");
     int rc = lift_check_maps(c, "lift_finalize");
     if (rc) return rc;
-    const double scaled = std::ceil(min_weight * (double)kLiftOne);
-    const unsigned long long threshold = scaled >= 18446744073709551615.0 ? ~0ull : (unsigned long long)scaled;
+    const unsigned long long threshold = lift_threshold(min_weight);
     const size_t n = (size_t)c->scene.rn;
     GSX_HIP(c, L.out.ensure(12 * n + 8));
     double* share = L.out.as<double>();

@@ -453,6 +453,64 @@ int frame_phase_lists(Ctx* c, const FramePlan& fp, int p, int first_phase, const
     return GSX_OK;
 }
 
+// ---- a walked frame ---------------------------------------------------------------------------------------------------------
+// A view that walks a frame's per-tile lists for the fragments' weights (lift_view, label_view, depth_view) is frame_walk_guard
+// + frame_lists_that_fit + a kernel built from the pieces of lift_device.hpp + the statistics pair below.  The guard: the state
+// a walked frame needs and the sizes it takes, in one order for all of them.  `what`: the noun of the edit-state message.
+int frame_walk_guard(Ctx* c, const gsx_camera* cam, int W, int H, const char* who, const char* what) {
+    if (c->scene.edits_on)
+        return fail(c, GSX_E_STATE, "%s: a render edit state is set (gsx_render_set_edits): %s through an edited frame is not defined", who, what);
+    if (c->frame.pre_ext >= 0 || c->frame.in_flight) return fail(c, GSX_E_STATE, "%s: gsx_render_views is running on this context", who);
+    if (!cam || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "%s: bad arguments (camera, width %d, height %d)", who, W, H);
+    if (W > 4096 || H > 4096) return fail(c, GSX_E_UNSUPPORTED, "%s: %dx%d exceeds 4096 pixels per side", who, W, H);
+    return GSX_OK;
+}
+
+// The frame's front is render_view's; what differs is WHEN the host learns the pair count.  render_view reads it at the end of
+// the frame and redoes a frame whose lists overflowed the pair buffers - a walk must never count a frame twice or count a
+// truncated list, so the counters are read back once the lists stand (one host wait); until they fit, the buffers grow and the
+// lists are rebuilt.  -> per-tile lists of all pairs (one depth phase) that fit, nothing walked yet.
+int frame_lists_that_fit(Ctx* c, const gsx_camera* cam, int W, int H, const char* who, FramePlan& fp, const uint32_t** vals) {
+    RenderFrame& f = c->frame;
+    int rc = frame_plan(c, W, H, false, 1, fp);
+    if (rc) return rc;
+    for (int attempt = 0;; ++attempt) {
+        const size_t cap = f.pair_cap;
+        if ((rc = frame_depth_order(c, cam, fp))) return rc;
+        if ((rc = frame_phase_lists(c, fp, 0, 1, vals))) return rc;
+        FrameCounters stats;
+        GSX_HIP(c, hipMemcpyAsync(&stats, f.small.p, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+        GSX_HIP(c, hipStreamSynchronize(c->stream));
+        const unsigned long long P = stats.pairs[0];
+        if (P > 0x7fffffffull)
+            return fail(c, GSX_E_RANGE, "%s: %llu (tile, splat) pairs exceed 2^31-1 (a close-up of a very large scene)", who, P);
+        if (P <= cap) {
+            f.P = P;
+            return GSX_OK;
+        }
+        // EMIT wrote nothing and the ranges are empty: grow, rebuild the lists
+        if (attempt >= 2) return fail(c, GSX_E_STATE, "%s: pair buffers overflowed three times in a row", who);
+        f.pair_cap = (size_t)(P + P / 4 + 4096);
+    }
+}
+
+// The end of a walked view: the kernel's statistics are queued for `stats` behind it (no wait), and once the caller has waited
+// for the stream, summed: f.consumed, and the kernel's own two counters of FrameCounters::Slot.
+int frame_walk_stats_queue(Ctx* c, FrameCounters& stats) {
+    GSX_HIP(c, hipMemcpyAsync(&stats, c->frame.small.p, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+    return GSX_OK;
+}
+
+void frame_walk_stats_sum(Ctx* c, const FrameCounters& stats, unsigned long long* atomics, unsigned long long* single) {
+    c->frame.consumed = *atomics = 0;
+    if (single) *single = 0;
+    for (const FrameCounters::Slot& slot : stats.consumed) {
+        c->frame.consumed += slot.n;
+        *atomics += slot.atomics;
+        if (single) *single += slot.single;
+    }
+}
+
 int render_view(Ctx* c, const gsx_camera* cam, int W, int H, float* rgba_out) {
     GSX_HIP(c, hipSetDevice(c->device));
     if (!cam || W < 1 || H < 1) return fail(c, GSX_E_INVALID, "render_view: bad arguments");

@@ -73,13 +73,14 @@ class _DeviceInts:
         self.__cuda_array_interface__ = {"shape": tuple(int(s) for s in shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
 
 
-def _scaled_camera(camera, w, h):
-    """the camera with fx, fy scaled from its own width, height to a w x h frame, as lift_view scales them to a map"""
+def _scaled_camera(camera, w, h, image_size=None):
+    """the camera with fx, fy scaled to a w x h frame from the (width, height) they refer to: image_size, or the camera's own"""
     cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
-    if (cam.width, cam.height) != (w, h) and cam.width > 0 and cam.height > 0:
+    iw, ih = (cam.width, cam.height) if image_size is None else (int(image_size[0]), int(image_size[1]))
+    if (iw, ih) != (w, h) and iw > 0 and ih > 0:
         scaled = Camera()
         C.memmove(C.byref(scaled), C.byref(cam), C.sizeof(Camera))
-        scaled.fx, scaled.fy, scaled.width, scaled.height = cam.fx * (w / cam.width), cam.fy * (h / cam.height), w, h
+        scaled.fx, scaled.fy, scaled.width, scaled.height = cam.fx * (w / iw), cam.fy * (h / ih), w, h
         cam = scaled
     return cam
 
@@ -668,14 +669,8 @@ class Context:
         the frame gsx_render_view draws from `camera` at the MAP's size.  image_size: (width, height) the camera's fx, fy
         refer to (default: the camera's own width, height); they are scaled by map size / image size, which is the caller's
         job at the C level.  Host maps are range-checked here (ValueError); device maps when the table is fetched."""
-        cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
         seg, dt, h, w, device = _seg_map_arg(seg_map, packed_u8)
-        iw, ih = (cam.width, cam.height) if image_size is None else (int(image_size[0]), int(image_size[1]))
-        if (iw, ih) != (w, h) and iw > 0 and ih > 0:
-            scaled = Camera()
-            C.memmove(C.byref(scaled), C.byref(cam), C.sizeof(Camera))
-            scaled.fx, scaled.fy, scaled.width, scaled.height = cam.fx * (w / iw), cam.fy * (h / ih), w, h
-            cam = scaled
+        cam = _scaled_camera(camera, w, h, image_size)
         if device:
             check(self._lib.gsx_lift_view_device(self.h, C.byref(cam), seg.data_ptr(), dt, w, h), self.h)
             self._lift_keep = [seg]          # the call waits for the frame: the previous map has been read
@@ -713,13 +708,8 @@ class Context:
         stays at label_map_device()).  return_weights: also uint32 (weight, total), the winner's sum and the pixel's total.
         planes: labels whose summed weights are wanted -> also uint32 (len(planes), height, width).  The extras follow the
         map in the order (map, weight, total, planes); with to_host=False they start the tuple."""
-        cam = camera if isinstance(camera, Camera) else Camera.from_dict(camera)
         w, h = int(width), int(height)
-        if (cam.width, cam.height) != (w, h) and cam.width > 0 and cam.height > 0:
-            scaled = Camera()
-            C.memmove(C.byref(scaled), C.byref(cam), C.sizeof(Camera))
-            scaled.fx, scaled.fy, scaled.width, scaled.height = cam.fx * (w / cam.width), cam.fy * (h / cam.height), w, h
-            cam = scaled
+        cam = _scaled_camera(camera, w, h)
         shape = (max(h, 0), max(w, 0))
         out = np.empty(shape, np.int32) if to_host else None
         weight = np.empty(shape, np.uint32) if return_weights else None
